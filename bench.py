@@ -24,7 +24,14 @@ ranks as a CHILD process and relays its result line and exit status; it never
 counts replicas that did not run. Under a launcher, ``--gpus`` must equal
 WORLD_SIZE.
 
-After the timed region of a multi-GPU run (its engines freed) the node measures
+A plain run sets up, warms up, times ``--steps`` steps and prints the result
+line; ``ms_per_step`` is the time of one timed step. ``--dump-outputs DIR``
+also writes the generated token ids of the last timed step (one row per
+request) to ``DIR/output_token_ids.npy``; prompts, weights and sampling seeds
+are seeded, so two builds can be compared output for output.
+
+Everything else is behind ``--full``. With it, after the timed region of a
+multi-GPU run (its engines freed) the node measures
 BASELINE configs 3 and 4 and the links they use (``notes.cross_gpu``, status
 also at the top level as ``cross_gpu_status``): cross-GPU transports
 (src/parallel/xgpu_probe.py), 8B disaggregated serving with prefill on rank 2k
@@ -37,6 +44,7 @@ result with ``cross_gpu_status: "stalled ..."`` and exits 3.
 
     python bench.py                      # 1 GPU, 3 timed steps, 1 warmup
     python bench.py --gpus 8 --steps 3   # spawns the 8-rank launcher itself
+    python bench.py --gpus 8 --steps 3 --full   # ... and runs the node section afterwards
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 3 --warmup 1
 """
@@ -109,9 +117,9 @@ def parse(argv=None):
                         "for one wave, so the ranks sharing the GPU do not each claim its HBM)")
     p.add_argument("--same-device", action="store_true",
                    help="rehearsal: every rank on cuda:0, gloo coordinates (no RCCL; numbers are not a scaling point)")
-    # the post-timed-region node section (configs 3 / 4 and the cross-GPU transports)
+    # the post-timed-region node section (configs 3 / 4 and the cross-GPU transports), under --full
     p.add_argument("--cross-gpu", choices=["auto", "on", "off"], default="auto",
-                   help="auto: on for multi-rank GPU runs; on: also on CPU (plumbing tests)")
+                   help="with --full. auto: on for multi-rank GPU runs; on: also on CPU (plumbing tests)")
     p.add_argument("--cross-gpu-budget-s", type=float, default=720.0, help="watchdog for the whole node section")
     p.add_argument("--disagg-preset", default=None, help="config 3 model (default: --preset)")
     p.add_argument("--tp-wave-preset", default="llama3-70b", help="config 4 model")
@@ -122,8 +130,40 @@ def parse(argv=None):
     p.add_argument("--no-lb-serving", action="store_true", help="skip the config-5 part of the node section")
     p.add_argument("--node-section-only", action="store_true",
                    help="internal: the node section alone (the child run that rank 0 of a multi-rank run starts)")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the node section after the timed region "
+                        "of a multi-rank run (--cross-gpu). Off: set up, warm up, time the steps, print the line")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last step returned to its callers as DIR/<name>.npy")
     p.add_argument("--verbose", action="store_true")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    return args
+
+
+# ------------------------------------------------------------------------------------------------ outputs
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, outs) -> dict:
+    """The last timed wave's generated token ids, one row per request in submission order (replica by replica),
+    as ``path/output_token_ids.npy`` (float32: ids are far below 2**24, so exact). Above DUMP_LIMIT_BYTES a
+    fixed, seeded sample of the rows is written, with their indices in ``output_token_rows.npy``."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    a = np.asarray(outs, dtype=np.float32)
+    written = {}
+    max_rows = max(1, DUMP_LIMIT_BYTES // (a[0].nbytes + 8))  # a row and its float64 index
+    if a.shape[0] > max_rows:
+        rows = np.sort(np.random.default_rng(0).choice(a.shape[0], size=max_rows, replace=False))
+        a = a[rows]
+        np.save(os.path.join(path, "output_token_rows.npy"), rows.astype(np.float64))
+        written["output_token_rows"] = [int(rows.shape[0])]
+    np.save(os.path.join(path, "output_token_ids.npy"), a)
+    written["output_token_ids"] = list(a.shape)
+    return written
 
 
 # ------------------------------------------------------------------------------------------------ launch guard
@@ -179,9 +219,11 @@ async def serve_wave(batcher, prompts, gen_len, temperature):
         seq = await fut
         lat[i] = time.perf_counter() - t0[i]
         assert len(seq.output_ids) == gen_len, (len(seq.output_ids), seq.finish_reason)
+        outs[i] = seq.output_ids
 
+    outs = [None] * n
     await asyncio.gather(*(one(i) for i in range(n)))
-    return lat
+    return lat, outs
 
 
 def serve_timed(args, rank, world, dev, on_gpu):
@@ -224,7 +266,7 @@ def serve_timed(args, rank, world, dev, on_gpu):
             obj.follower_loop()
             sync()
             dist.barrier()
-            return {"elapsed": 0.0, "lats": [], "follower": True}
+            return {"elapsed": 0.0, "lats": [], "outs": [], "follower": True}
         engine = obj
     else:
         engine = LLMEngine.from_preset(args.preset, device=dev, cfg=cfg, max_model_len=args.max_model_len,
@@ -263,9 +305,10 @@ def serve_timed(args, rank, world, dev, on_gpu):
         prof_marker()
         stats0 = dict(engine.stats)
         t0 = time.perf_counter()
-        lats = []
+        lats, outs = [], []
         for s in range(args.steps):
-            lats += await serve_wave(batcher, waves[s], args.gen_len, args.temperature)
+            lat, outs = await serve_wave(batcher, waves[s], args.gen_len, args.temperature)
+            lats += lat
             if args.verbose and rank == 0:
                 print(f"step {s}: {time.perf_counter() - t0:.2f}s", file=sys.stderr, flush=True)
         prof_marker()
@@ -277,12 +320,12 @@ def serve_timed(args, rank, world, dev, on_gpu):
         sync()
         elapsed = time.perf_counter() - t0
         await batcher.stop()
-        return elapsed, lats, stats0
+        return elapsed, lats, outs, stats0
 
-    elapsed, lats, stats0 = asyncio.run(run())
+    elapsed, lats, outs, stats0 = asyncio.run(run())
     aeng.stop()
     st = engine.stats
-    return {"elapsed": elapsed, "lats": lats, "init_s": init_s,
+    return {"elapsed": elapsed, "lats": lats, "outs": outs, "init_s": init_s,
             "gen_tok": st["generated_tokens"] - stats0["generated_tokens"],
             "prefill_s": st["prefill_time"] - stats0["prefill_time"],
             "decode_s": st["decode_time"] - stats0["decode_time"]}
@@ -494,6 +537,9 @@ def main(argv=None) -> int:
         gathered = [None] * world
         dist.all_gather_object(gathered, lats)
         lats = [x for g in gathered for x in g]
+        if args.dump_outputs:
+            dist.all_gather_object(gathered, m["outs"])
+            m["outs"] = [x for g in gathered for x in g]
         idents = [None] * world
         dist.all_gather_object(idents, ident)
     tp = args.tp if args.tp > 1 else None
@@ -548,8 +594,11 @@ def main(argv=None) -> int:
             res["notes"]["rehearsal"] = "every rank on cuda:0: not a scaling point"
         if world > 1 and tp is None:  # the value uses the slowest replica; the spread shows stragglers
             res["notes"]["rank_elapsed_s"] = [round(x, 3) for x in rank_elapsed]
+        if args.dump_outputs:
+            res["notes"]["dumped_outputs"] = dump_outputs(args.dump_outputs, m["outs"])
     m = None
-    run_node = world > 1 and tp is None and (args.cross_gpu == "on" or (args.cross_gpu == "auto" and on_gpu))
+    run_node = (args.full and world > 1 and tp is None
+                and (args.cross_gpu == "on" or (args.cross_gpu == "auto" and on_gpu)))
     dog = None
     rc = 0
     cpu = None

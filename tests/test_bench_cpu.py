@@ -59,6 +59,35 @@ def test_bench_json_contract(nproc, extra, par, replicas):
     assert res["p50_latency_ms"] > 0
 
 
+def test_bench_dump_outputs_is_the_last_step_and_repeats(tmp_path):
+    """``--dump-outputs DIR`` writes the last timed step's generated token ids (one float32 row per request) and
+    says so in the line; the inputs are seeded, so a second run with the same arguments writes the same array."""
+    import numpy as np
+
+    arrays = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        res = _run(1, ["--dump-outputs", str(d)])
+        assert res["steps"] == 2 and res["notes"]["dumped_outputs"] == {"output_token_ids": [4, 4]}
+        assert sorted(p.name for p in d.iterdir()) == ["output_token_ids.npy"]
+        arrays.append(np.load(d / "output_token_ids.npy"))
+    a, b = arrays
+    assert a.dtype == np.float32 and a.shape == (4, 4)  # --batch 4 requests x --gen-len 4 tokens
+    assert np.array_equal(a, np.round(a)) and a.min() >= 0
+    assert np.array_equal(a, b)
+
+
+def test_bench_plain_run_skips_the_node_section(tmp_path):
+    """Without ``--full`` a multi-rank run does only what the headline figure needs: no node section even with
+    ``--cross-gpu on``. Its dump holds every replica's rows, rank by rank."""
+    import numpy as np
+
+    res = _run(2, ["--cross-gpu", "on", "--dump-outputs", str(tmp_path)])
+    assert "cross_gpu_status" not in res and "cross_gpu" not in res["notes"]
+    assert KEYS <= set(res) and res["config"]["parallelism"] == "dp2"
+    assert np.load(tmp_path / "output_token_ids.npy").shape == (8, 4)
+
+
 def test_bench_watchdog_prints_the_line_once_and_ends_a_stalled_rank():
     """bench.py's watchdog around the post-timed-region node section: a stall still prints rank 0's result line
     once, says so at the top level (``cross_gpu_status``) and in the section (``status`` 3, the stalled part),
@@ -124,7 +153,7 @@ def test_bench_node_section_configs_3_4_5_on_cpu():
     rank behind one coordinator on rank 0: least_latency then round_robin, mixed lengths with shared prefixes,
     small KV pools that evict) and config 4 (a TP=2 engine over both ranks) all serve; their status reaches the top
     level."""
-    r = _self_launched(2, ["--cross-gpu", "on", "--tp-wave-min-world", "2", "--tp-wave-preset", "llama-tiny",
+    r = _self_launched(2, ["--full", "--cross-gpu", "on", "--tp-wave-min-world", "2", "--tp-wave-preset", "llama-tiny",
                            "--lb-preset", "mixtral-tiny", "--lb-kv-blocks", "64", "--lb-requests-per-worker", "6"])
     assert r.returncode == 0, r.stderr[-3000:]
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])

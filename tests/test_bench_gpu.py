@@ -25,7 +25,7 @@ def test_bench_node_section_rehearsal_two_ranks_one_gpu():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--same-device", "--preset", "llama-mini", "--batch", "8",
+    cmd = [sys.executable, "bench.py", "--full", "--gpus", "2", "--same-device", "--preset", "llama-mini", "--batch", "8",
            "--prompt-len", "64", "--gen-len", "16", "--max-model-len", "256", "--steps", "1", "--warmup", "1",
            "--tp-wave-min-world", "2", "--tp-wave-preset", "llama-mini", "--lb-preset", "mixtral-tiny",
            "--lb-kv-blocks", "64", "--lb-requests-per-worker", "8", "--cross-gpu-budget-s", "200", "--verbose"]
