@@ -342,6 +342,36 @@ void sample(Tensor out, Tensor logits, c10::optional<Tensor> temperature, c10::o
                              lp, lparts));
 }
 
+// Log-probabilities of the raw distribution for targets [rows] int64: lp fp32 / rank int32 [>= rows], and the
+// top_n most likely tokens into top_lp fp32 / top_id int32 [>= rows, >= top_n] (same row stride, unit column stride).
+void token_logprobs(Tensor lp, Tensor rank, Tensor top_lp, Tensor top_id, Tensor logits, Tensor targets,
+                    int64_t top_n) {
+  CHK_CUDA(logits);
+  CHK_BF16(logits);
+  check_rows(logits, "logits");
+  const int64_t rows = logits.size(0);
+  TORCH_CHECK(targets.is_cuda() && targets.scalar_type() == at::kLong && targets.is_contiguous() &&
+                  targets.numel() >= rows, "token_logprobs: targets [rows] int64");
+  TORCH_CHECK(lp.is_cuda() && lp.scalar_type() == at::kFloat && lp.is_contiguous() && lp.numel() >= rows &&
+                  rank.is_cuda() && rank.scalar_type() == at::kInt && rank.is_contiguous() && rank.numel() >= rows,
+              "token_logprobs: lp fp32 [rows], rank int32 [rows]");
+  int64_t top_stride = 0;
+  if (top_n > 0) {
+    TORCH_CHECK(top_lp.is_cuda() && top_lp.scalar_type() == at::kFloat && top_id.is_cuda() &&
+                    top_id.scalar_type() == at::kInt && top_lp.dim() == 2 && top_id.dim() == 2 &&
+                    top_lp.size(0) >= rows && top_id.size(0) >= rows && top_lp.size(1) >= top_n &&
+                    top_id.size(1) >= top_n && top_lp.stride(1) == 1 && top_id.stride(1) == 1 &&
+                    top_lp.stride(0) == top_id.stride(0) && top_lp.stride(0) >= top_lp.size(1),
+                "token_logprobs: top_lp fp32 / top_id int32 [rows, >= top_n] with the same row stride");
+    top_stride = top_lp.stride(0);
+  }
+  HIP_OK(die::launch_token_logprobs(lp.data_ptr<float>(), rank.data_ptr<int>(),
+                                     top_n > 0 ? top_lp.data_ptr<float>() : nullptr,
+                                     top_n > 0 ? top_id.data_ptr<int>() : nullptr, top_stride, bf(logits),
+                                     logits.stride(0), (int)rows, (int)logits.size(1), targets.data_ptr<int64_t>(),
+                                     (int)std::min<int64_t>(std::max<int64_t>(top_n, -1), 1 << 20), cur_stream()));
+}
+
 // A decode step's sampling from the LM head's candidates (sample(..., lm_part)) that also advances the step's
 // inputs as decode_advance does (ids / pos / ctx / slots / step, the window's token row, the step counter cnt[0]),
 // one workgroup per row; ticket: int32 [1], zero, re-armed by the kernel.
@@ -1031,6 +1061,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("steps") = py::none(), py::arg("part") = py::none(), py::arg("cnt") = py::none(),
         py::arg("lm_part") = py::none());
   m.def("copy_blocks", &copy_blocks);
+  m.def("token_logprobs", &token_logprobs);
   m.def("sample_advance", &sample_advance);
   m.def("move_blocks", &move_blocks);
   m.def("gather_blocks_rows", &gather_blocks_rows);

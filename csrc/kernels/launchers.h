@@ -98,6 +98,13 @@ hipError_t launch_sample(int64_t* out, const bf16_t* logits, int64_t stride, int
                          const int64_t* steps, hipStream_t s, uint32_t* part = nullptr, int* cnt = nullptr,
                          int splits = 1, const uint32_t* lm_part = nullptr, int lm_parts = 0,
                          const SampleAdvance& adv = SampleAdvance{});
+// log-probabilities of the raw distribution (fp32 log_softmax of the bf16 row): lp / rank [rows] of targets[r]
+// (outside [0, vocab): -inf and vocab), and the top_n (<= LOGPROBS_MAX_TOP) most likely tokens in the order
+// "larger logit, then lower id" into top_lp / top_id [rows, top_stride]
+constexpr int LOGPROBS_MAX_TOP = 20;
+hipError_t launch_token_logprobs(float* lp, int* rank, float* top_lp, int* top_id, int64_t top_stride,
+                                 const bf16_t* logits, int64_t stride, int rows, int vocab, const int64_t* targets,
+                                 int top_n, hipStream_t s);
 
 hipError_t launch_topk_softmax(float* w, int* ids, const bf16_t* gating, int T, int E, int K, bool renorm,
                                hipStream_t s);

@@ -326,4 +326,243 @@ hipError_t launch_sample(int64_t* out, const bf16_t* logits, int64_t stride, int
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Per-token log-probabilities of the RAW distribution (log_softmax of the bf16 row in fp32, before temperature
+// and filters): the target's logprob and rank and the top_n most likely tokens, one workgroup per row.
+// Total order: larger logit first, then lower token id (better()). Passes over the row (from L2):
+//   1. row max (row_argmax);  2. sum of exp(z - max) and the count of entries before the target — and, for
+//      top_n > 0, a histogram of the entries whose key is among the 256 bf16 values just below the max's (a bf16
+//      entry's 32-bit key is fixed by its upper 16 bits, so this window is two octaves of logit values);
+//   3. the key T of the top_n-th largest entry: a wave's prefix scan over that window — no pass over the row.
+//      Only when the window holds fewer than top_n entries (e.g. one outlier above a flat row) does
+//      radix_threshold<false> find T in four more passes;
+//   4. one walk with contiguous slabs per wave: entries above T go to an LDS list (fewer than top_n), entries
+//      equal to T are numbered in index order inside each wave (prefix scan of the lanes' counts); the places
+//      left go to the waves' ties in wave order;  5. wave 0 ranks the top_n entries among themselves.
+// Every id written is an index the walk visited (or the slot number, if a row of NaN keys yields fewer
+// entries than asked), so it is inside [0, vocab) whatever the row holds.
+
+// f2key with -0.0 == +0.0, as a float compare (and the sort of the reference) has it
+__device__ __forceinline__ uint32_t lp_key(float f) {
+  return f2key(__float_as_uint(f) == 0x80000000u ? 0.f : f);
+}
+
+__device__ int block_sumi(int v, int* red) {
+  v = wave_sum(v);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  if (lane == 0) red[wid] = v;
+  __syncthreads();
+  int t = 0;
+  for (int w = 0; w < SNT / 64; ++w) t += red[w];
+  __syncthreads();
+  return t;
+}
+
+__global__ void __launch_bounds__(SNT) token_logprobs_kernel(float* __restrict__ lp, int* __restrict__ rank,
+                                                             float* __restrict__ top_lp, int* __restrict__ top_id,
+                                                             int64_t top_stride, const bf16_t* __restrict__ logits,
+                                                             int64_t stride, int vocab,
+                                                             const int64_t* __restrict__ targets, int top_n) {
+  constexpr int NW = SNT / 64;
+  __shared__ ArgMax red[NW];
+  __shared__ float redf[NW];
+  __shared__ int redi[NW];
+  __shared__ float hist[256];
+  __shared__ uint32_t sh[2];
+  __shared__ uint32_t whist[256];  // entries per 16-bit key, from the max's key downwards
+  __shared__ uint32_t l_key[LOGPROBS_MAX_TOP];  // entries above the threshold, unordered
+  __shared__ int l_id[LOGPROBS_MAX_TOP];
+  __shared__ int n_above;
+  __shared__ int w_tie[NW][LOGPROBS_MAX_TOP];   // each wave's first ties, in index order
+  __shared__ int w_ntie[NW];
+  const int r = blockIdx.x, lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const bf16_t* row = logits + (int64_t)r * stride;
+  const int64_t t64 = targets[r];
+  const bool t_ok = t64 >= 0 && t64 < vocab;
+  const int ti = t_ok ? (int)t64 : 0;
+  const float zt = t_ok ? bf2f(row[ti]) : 0.f;
+  const uint32_t kt = lp_key(zt);
+
+  if (threadIdx.x < 256) whist[threadIdx.x] = 0u;  // row_argmax's barrier orders this before the adds below
+  const float m = row_argmax(row, 0, vocab, red).v;
+  const uint32_t kmax16 = lp_key(m) >> 16;
+
+  constexpr int AU = 4;
+  float s = 0.f;
+  int before = 0;
+  for (int i0 = threadIdx.x * 8; i0 < vocab; i0 += SNT * 8 * AU) {
+    uint4 v[AU];
+#pragma unroll
+    for (int u = 0; u < AU; ++u) {
+      const int i = i0 + u * SNT * 8;
+      v[u] = i < vocab ? *reinterpret_cast<const uint4*>(row + i) : make_uint4(0u, 0u, 0u, 0u);
+    }
+#pragma unroll
+    for (int u = 0; u < AU; ++u) {
+      const int i = i0 + u * SNT * 8;
+      if (i < vocab) {
+        float z[8];
+        unpack8(v[u], z);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          s += __expf(z[j] - m);
+          const uint32_t k = lp_key(z[j]);
+          before += (k > kt || (k == kt && i + j < ti)) ? 1 : 0;
+          const uint32_t d = kmax16 - (k >> 16);  // wraps to a large value for a (NaN) key above the max's
+          if (top_n > 0 && d < 256u) atomicAdd(&whist[d], 1u);
+        }
+      }
+    }
+  }
+  s = block_sumf(s, redf);
+  before = block_sumi(before, redi);
+  const float lse = logf(s);
+  if (threadIdx.x == 0) {
+    lp[r] = t_ok ? (zt - m) - lse : -INFINITY;
+    rank[r] = t_ok ? before : vocab;
+  }
+  if (top_n <= 0) return;
+
+  // wave 0: lane l sums window bins [4l, 4l + 4), a prefix scan finds the bin that holds the top_n-th entry
+  if (wid == 0) {
+    uint32_t c4[4], mine = 0u;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      c4[q] = whist[lane * 4 + q];
+      mine += c4[q];
+    }
+    uint32_t incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const uint32_t y = __shfl_up(incl, o, 64);
+      if (lane >= o) incl += y;
+    }
+    uint32_t cum = incl - mine;
+    if (lane == 63 && incl < (uint32_t)top_n) sh[0] = 0xffffffffu;
+    if (cum < (uint32_t)top_n && incl >= (uint32_t)top_n) {  // exactly one lane
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if (cum < (uint32_t)top_n && cum + c4[q] >= (uint32_t)top_n) sh[0] = (uint32_t)(lane * 4 + q);
+        cum += c4[q];
+      }
+    }
+  }
+  __syncthreads();
+  const uint32_t bin = sh[0];
+  __syncthreads();  // sh is reused by radix_threshold
+  uint32_t T;
+  if (bin != 0xffffffffu) {
+    const uint32_t t16 = kmax16 - bin;  // a bf16 entry's key: its upper 16 bits, then all zeros (>= 0) or all ones
+    T = (t16 << 16) | ((t16 & 0x8000u) ? 0u : 0xffffu);
+  } else {
+    T = radix_threshold<false>(row, vocab, 1.f, m, 0u, (float)top_n, hist, sh);
+    if (T == 0x7fffffffu) T = 0x80000000u;  // the key of -0.0: lp_key() files those under +0.0
+  }
+  if (threadIdx.x < LOGPROBS_MAX_TOP) {
+    l_key[threadIdx.x] = 0u;
+    l_id[threadIdx.x] = threadIdx.x < vocab ? threadIdx.x : 0;
+  }
+  if (threadIdx.x < NW) w_ntie[threadIdx.x] = 0;
+  if (threadIdx.x == 0) n_above = 0;
+  __syncthreads();
+
+  // wave `wid` owns row[lo, hi): its ties are met in index order (chunk by chunk, lane by lane, entry by entry)
+  const int slab = ((vocab / 8 + NW - 1) / NW) * 8;
+  const int lo = min(vocab, wid * slab), hi = min(vocab, lo + slab);
+  int c = 0;  // this wave's ties so far (wave-uniform)
+  for (int i0 = lo; i0 < hi; i0 += 512 * AU) {
+    uint4 v[AU];
+#pragma unroll
+    for (int u = 0; u < AU; ++u) {
+      const int i = i0 + u * 512 + lane * 8;
+      v[u] = i < hi ? *reinterpret_cast<const uint4*>(row + i) : make_uint4(0u, 0u, 0u, 0u);
+    }
+#pragma unroll
+    for (int u = 0; u < AU; ++u) {
+      const int i = i0 + u * 512 + lane * 8;
+      uint32_t tie = 0u;
+      if (i < hi) {
+        float z[8];
+        unpack8(v[u], z);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const uint32_t k = lp_key(z[j]);
+          if (k > T) {
+            const int slot = atomicAdd(&n_above, 1);
+            if (slot < LOGPROBS_MAX_TOP) {
+              l_key[slot] = k;
+              l_id[slot] = i + j;
+            }
+          }
+          tie |= (k == T ? 1u : 0u) << j;
+        }
+      }
+      if (c < top_n && __ballot(tie != 0u) != 0ull) {  // wave-uniform
+        const int cnt = __popc(tie);
+        int incl = cnt;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+          const int y = __shfl_up(incl, o, 64);
+          if (lane >= o) incl += y;
+        }
+        int ord = c + incl - cnt;
+        for (int j = 0; j < 8; ++j) {
+          if ((tie >> j) & 1u) {
+            if (ord < LOGPROBS_MAX_TOP) w_tie[wid][ord] = i + j;
+            ++ord;
+          }
+        }
+        c += __shfl(incl, 63, 64);
+      }
+    }
+  }
+  if (lane == 0) w_ntie[wid] = min(c, LOGPROBS_MAX_TOP);
+  __syncthreads();
+  if (wid != 0) return;
+
+  const int above = min(n_above, top_n);
+  uint32_t key = 0u;
+  int id = lane < vocab ? lane : 0;
+  if (lane < above) {
+    key = l_key[lane];
+    id = l_id[lane];
+  } else if (lane < top_n) {
+    int q = lane - above;
+    for (int w = 0; w < NW; ++w) {
+      const int nw = w_ntie[w];
+      if (q < nw) {
+        key = T;
+        id = w_tie[w][q];
+        break;
+      }
+      q -= nw;
+    }
+  }
+  // place = the number of entries that come before this one (the lane breaks a tie of equal pairs, which only a
+  // short-filled list can hold, so the places are always a permutation)
+  int place = 0;
+  for (int o = 0; o < top_n; ++o) {
+    const uint32_t ko = __shfl(key, o, 64);
+    const int io = __shfl(id, o, 64);
+    place += (ko > key || (ko == key && (io < id || (io == id && o < lane)))) ? 1 : 0;
+  }
+  if (lane < top_n) {
+    top_lp[(int64_t)r * top_stride + place] = (key2f(key) - m) - lse;
+    top_id[(int64_t)r * top_stride + place] = id;
+  }
+}
+
+hipError_t launch_token_logprobs(float* lp, int* rank, float* top_lp, int* top_id, int64_t top_stride,
+                                 const bf16_t* logits, int64_t stride, int rows, int vocab, const int64_t* targets,
+                                 int top_n, hipStream_t s) {
+  if (rows == 0) return hipSuccess;
+  if (rows < 0 || vocab <= 0 || vocab % 8 || stride < vocab || stride % 8 || top_n < 0 || top_n > LOGPROBS_MAX_TOP ||
+      top_n > vocab || lp == nullptr || rank == nullptr || targets == nullptr || logits == nullptr)
+    return hipErrorInvalidValue;
+  if (top_n > 0 && (top_lp == nullptr || top_id == nullptr || top_stride < top_n)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(token_logprobs_kernel, dim3(rows), dim3(SNT), 0, s, lp, rank, top_lp, top_id, top_stride, logits,
+                     stride, vocab, targets, top_n);
+  return hipGetLastError();
+}
+
 }  // namespace die

@@ -5,6 +5,7 @@
     python examples/example_client.py --model llama --prompt "Hello" --max-tokens 32
     python examples/example_client.py --model llama --prompt "Hi" -n 64 --concurrency 32   # mini load test
     python examples/example_client.py --model llama --prompt "Hello" --max-tokens 64 --stream  # token stream
+    python examples/example_client.py --model llama --prompt "Hello" --logprobs 5   # per-token logprobs + top 5
 """
 
 import argparse
@@ -28,6 +29,8 @@ async def main():
     ap.add_argument("--prompt", default=None)
     ap.add_argument("--max-tokens", type=int, default=16)
     ap.add_argument("--temperature", type=float, default=0.0)
+    ap.add_argument("--logprobs", type=int, default=None, metavar="N",
+                    help="per-token logprobs of the raw distribution: 0 = the chosen token's, 1..20 = also the top N")
     ap.add_argument("--request-key", default=None, help="session key for shard affinity")
     ap.add_argument("-n", type=int, default=1)
     ap.add_argument("--concurrency", type=int, default=1)
@@ -36,6 +39,8 @@ async def main():
     a = ap.parse_args()
     if a.prompt is not None:
         inputs = {"prompt": a.prompt, "max_tokens": a.max_tokens, "temperature": a.temperature}
+        if a.logprobs is not None:
+            inputs["logprobs"] = a.logprobs
     else:
         inputs = json.loads(a.inputs) if a.inputs else {"text": "hello"}
     c = InferenceClient(a.address)
@@ -43,7 +48,9 @@ async def main():
         t0 = time.perf_counter()
         async for frame in c.infer_stream(a.model, inputs, request_key=a.request_key):
             if frame.get("done") is False:
-                print(f"[{1e3 * (time.perf_counter() - t0):8.1f} ms] +{frame['delta_token_ids']}", flush=True)
+                lps = (frame.get("delta_logprobs") or {}).get("token_logprobs")
+                print(f"[{1e3 * (time.perf_counter() - t0):8.1f} ms] +{frame['delta_token_ids']}"
+                      + (f" logprobs {[round(v, 3) for v in lps]}" if lps else ""), flush=True)
             else:
                 print(json.dumps(frame, indent=2)[:4000])
         c.close()

@@ -38,7 +38,10 @@ class InferenceClient:
     async def infer_stream(self, model: str, inputs: Any, version: Optional[str] = None,
                            request_key: Optional[str] = None, **extra):
         """Streamed generation: yields ``{"delta_token_ids": [...], "done": False}`` frames as tokens are
-        produced, then the final response (``"done": True``, same shape as :meth:`infer`'s reply)."""
+        produced, then the final response (``"done": True``, same shape as :meth:`infer`'s reply). With
+        ``inputs["logprobs"]`` every frame also carries ``"delta_logprobs"`` for its tokens and the final
+        outputs ``"logprobs"`` (``"prompt_logprobs"`` with ``inputs["prompt_logprobs"]``), passed through as the
+        backend built them."""
         inputs = dict(inputs, stream=True)
         msg: Dict[str, Any] = {"op": "infer", "model": model, "inputs": inputs, "cache": False}
         if version:

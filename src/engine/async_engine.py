@@ -61,7 +61,8 @@ class AsyncLLMEngine:
                on_token: Optional[Callable[[int], None]] = None) -> asyncio.Future:
         """Thread-safe; call from the event loop. The future resolves to the
         finished :class:`Sequence` (or raises if the engine failed). ``on_token(tok)`` (streaming)
-        runs on the event loop for every generated token, in order, before the future resolves."""
+        runs on the event loop for every generated token, in order, before the future resolves; for a request
+        with ``sampling.logprobs`` its argument is the pair ``(tok, logprob entry)``."""
         loop = loop or asyncio.get_running_loop()
         fut = loop.create_future()
         if self.error is not None:
@@ -144,8 +145,9 @@ class AsyncLLMEngine:
 
             on_tok = None
             if isinstance(ud, dict) and ud.get("on_token") is not None and loop is not None:
-                def on_tok(seq: Sequence, tok: int, cb=ud["on_token"], loop=loop):
-                    loop.call_soon_threadsafe(cb, tok)
+                def on_tok(seq: Sequence, tok: int, entry=None, cb=ud["on_token"], loop=loop):
+                    # a request with logprobs streams (token, its logprob entry) pairs, any other one bare tokens
+                    loop.call_soon_threadsafe(cb, tok if seq.sampling.logprobs is None else (tok, entry))
             try:
                 if isinstance(ud, dict) and ud.get("import_packet") is not None:
                     self.engine.add_imported(ud["import_packet"], sp, on_finish=done)

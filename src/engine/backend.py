@@ -23,7 +23,7 @@ import torch
 from src.config import EngineConfig, ModelConfig
 from src.engine.async_engine import AsyncLLMEngine
 from src.engine.llm_engine import LLMEngine
-from src.postproc import build_llm_output
+from src.postproc import build_llm_output, logprobs_block
 from src.preproc import ByteTokenizer, load_tokenizer, normalize_request
 
 logger = logging.getLogger(__name__)
@@ -135,6 +135,34 @@ class LLMBackend:
         out["text"] = await self.preproc.decode_one(ids)
         return out
 
+    async def _token_strings(self, seqs: List[List[int]]) -> List[str]:
+        """One string per id list (the post-processing pool's batch call where there is one)."""
+        if not seqs:
+            return []
+        if self.preproc is not None:
+            return list(await self.preproc.decode(seqs))
+        return [self.tokenizer.decode(s) for s in seqs]
+
+    async def _logprobs_out(self, entries: List[Optional[dict]], ids: List[int], return_text: bool) -> Dict[str, Any]:
+        """logprobs_block for `ids`; with return_text also "tokens" and "top_tokens" (per-token strings)."""
+        blk = logprobs_block(entries)
+        if return_text:
+            blk["tokens"] = await self._token_strings([[int(t)] for t in ids])
+            flat = [[t] for row in blk["top_token_ids"] if row is not None for t in row]
+            strs = iter(await self._token_strings(flat))
+            blk["top_tokens"] = [None if row is None else [next(strs) for _ in row] for row in blk["top_token_ids"]]
+        return blk
+
+    async def _add_logprobs(self, out: Dict[str, Any], seq, sampling, return_text: bool) -> Dict[str, Any]:
+        """The request's logprobs (and prompt logprobs), when it asked for them, into a final output."""
+        if sampling.logprobs is not None:
+            entries = list(seq.output_logprobs)
+            entries += [None] * (len(seq.output_ids) - len(entries))
+            out["logprobs"] = await self._logprobs_out(entries[:len(seq.output_ids)], seq.output_ids, return_text)
+        if sampling.prompt_logprobs is not None and seq.prompt_logprobs_out is not None:
+            out["prompt_logprobs"] = await self._logprobs_out(seq.prompt_logprobs_out, seq.prompt_ids, return_text)
+        return out
+
     def healthy(self) -> bool:
         """False once the engine loop died (e.g. a HIP fault surfaced as an exception): the worker
         then reports itself unhealthy and fails requests as retryable elsewhere."""
@@ -197,8 +225,9 @@ class LLMBackend:
         lat = (time.perf_counter() - t0) * 1e3
         self.total_latency += lat / 1e3
         reason = "timeout" if timed_out and seq.finish_reason == "abort" else (seq.finish_reason or "length")
-        return await self._output(seq.output_ids, gi.return_text, prompt_len=seq.prompt_len, finish_reason=reason,
-                                  ttft_ms=seq.ttft_ms(), latency_ms=seq.latency_ms())
+        out = await self._output(seq.output_ids, gi.return_text, prompt_len=seq.prompt_len, finish_reason=reason,
+                                 ttft_ms=seq.ttft_ms(), latency_ms=seq.latency_ms())
+        return await self._add_logprobs(out, seq, gi.sampling, gi.return_text)
 
     async def predict_stream(self, inputs: Any, emit, request_id: Optional[str] = None) -> Dict[str, Any]:
         """Streaming generation: ``await emit({"delta_token_ids": [...], "done": False})`` as tokens are
@@ -216,9 +245,13 @@ class LLMBackend:
         text_sent = 0
         first = True
 
-        async def send(toks: List[int]) -> None:
+        async def send(items: list) -> None:
             nonlocal text_sent
+            # a request with logprobs streams (token, entry) pairs (AsyncEngine.submit)
+            toks = [x[0] if isinstance(x, tuple) else x for x in items]
             frame: Dict[str, Any] = {"delta_token_ids": toks, "done": False}
+            if items and isinstance(items[0], tuple):
+                frame["delta_logprobs"] = await self._logprobs_out([x[1] for x in items], toks, with_text)
             so_far.extend(toks)
             if with_text:  # incremental detokenisation: hold back a trailing partial character
                 text = self.tokenizer.decode(so_far)
@@ -293,11 +326,13 @@ class LLMBackend:
         if pseq.finish_reason == "stop":
             if slot is not None:
                 self._decode_link.revoke(slot)
-            return await self._output(pseq.output_ids, gi.return_text, prompt_len=pseq.prompt_len,
-                                      finish_reason="stop", ttft_ms=pseq.ttft_ms(), latency_ms=pseq.latency_ms())
+            out = await self._output(pseq.output_ids, gi.return_text, prompt_len=pseq.prompt_len,
+                                     finish_reason="stop", ttft_ms=pseq.ttft_ms(), latency_ms=pseq.latency_ms())
+            return await self._add_logprobs(out, pseq, gi.sampling, gi.return_text)
         packet = KVPacket(rid, gi.prompt_token_ids, pseq.output_ids[0], pseq.kv_export, self.engine.cfg.block_size,
                           sampling_to_dict(gi.sampling), ttft_ms=pseq.ttft_ms(),
-                          ready=getattr(pseq, "kv_export_ready", None))
+                          ready=getattr(pseq, "kv_export_ready", None),
+                          first_logprobs=pseq.output_logprobs[0] if pseq.output_logprobs else None)
         pseq.kv_export = None
         if slot is not None:
             rep = await self._decode_link.send_reserved(packet, slot.res)
@@ -338,7 +373,7 @@ class LLMBackend:
 
             packet = KVPacket(d["request_id"], list(d["prompt_ids"]), int(d["first_token"]), kv,
                               int(d["block_size"]), dict(d.get("sampling") or {}), d.get("ttft_ms"),
-                              ready=ready, on_imported=on_imported)
+                              ready=ready, on_imported=on_imported, first_logprobs=d.get("first_logprobs"))
             self.ipc_imports += 1
         else:
             packet = packet_for_import(d, self.engine.device)
@@ -353,9 +388,10 @@ class LLMBackend:
             if packet.on_imported is not None and not handed:
                 self._landing_zone().release(off)
             raise
-        return {"success": True, "outputs": await self._output(
-            seq.output_ids, prompt_len=seq.prompt_len, finish_reason=seq.finish_reason or "length",
-            ttft_ms=packet.ttft_ms, latency_ms=seq.latency_ms())}
+        out = await self._output(seq.output_ids, prompt_len=seq.prompt_len,
+                                 finish_reason=seq.finish_reason or "length", ttft_ms=packet.ttft_ms,
+                                 latency_ms=seq.latency_ms())
+        return {"success": True, "outputs": await self._add_logprobs(out, seq, sp, True)}
 
     async def predict_batch(self, inputs_list: List[Any]) -> List[Dict[str, Any]]:
         return list(await asyncio.gather(*(self.predict(x) for x in inputs_list)))

@@ -72,7 +72,9 @@ class KVBlockManager:
         (its logits are needed), so at most ``(len-1)//bs`` blocks are matched."""
         assert not seq.block_table
         matched: List[int] = []
-        if self.prefix_caching and not seq.imported_kv:
+        # prompt_logprobs needs the logits of every prompt position: nothing is matched (the blocks are still
+        # published afterwards)
+        if self.prefix_caching and not seq.imported_kv and getattr(seq.sampling, "prompt_logprobs", None) is None:
             hashes = self._prompt_hashes(seq)
             max_match = (seq.prompt_len - 1) // self.block_size
             matched = list(self.bm.match_prefix(hashes[:max_match]))

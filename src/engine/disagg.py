@@ -286,7 +286,8 @@ class RemoteDecodeLink:
 
 def sampling_to_dict(sp: SamplingParams) -> Dict[str, Any]:
     return {"max_tokens": sp.max_tokens, "temperature": sp.temperature, "top_k": sp.top_k, "top_p": sp.top_p,
-            "seed": sp.seed, "ignore_eos": sp.ignore_eos, "stop_token_ids": list(sp.stop_token_ids)}
+            "seed": sp.seed, "ignore_eos": sp.ignore_eos, "stop_token_ids": list(sp.stop_token_ids),
+            "logprobs": sp.logprobs, "prompt_logprobs": sp.prompt_logprobs}
 
 
 def packet_for_import(d: Dict[str, Any], device) -> KVPacket:

@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import collections
 import dataclasses
+import inspect
 import logging
 import time
 from typing import Callable, Dict, List, Optional
@@ -72,6 +73,27 @@ def choose_decode_weight_layout(model, cfg: EngineConfig, device: torch.device, 
             if cfg.num_kv_blocks > fits - extra // per_block:
                 return "single"
     return "tiled"
+
+
+def _takes_entry(cb) -> bool:
+    """Whether an on_token callback takes the token's logprob entry as a third argument."""
+    if cb is None:
+        return False
+    try:
+        params = list(inspect.signature(cb).parameters.values())
+    except (TypeError, ValueError):
+        return False
+    if any(p.kind == p.VAR_POSITIONAL for p in params):
+        return True
+    return len([p for p in params if p.kind in (p.POSITIONAL_ONLY, p.POSITIONAL_OR_KEYWORD)]) >= 3
+
+
+def logprob_entry(step: tuple, i: int, n: Optional[int]) -> Optional[dict]:
+    """Row i of one step's logprobs (ModelRunner._lp_read), trimmed to the n top tokens the request asked for."""
+    if n is None or step is None or step[0][i] is None:
+        return None
+    return {"logprob": step[0][i], "rank": step[1][i], "top_ids": list(step[3][i][:n]),
+            "top_logprobs": list(step[2][i][:n])}
 
 
 class LLMEngine:
@@ -171,8 +193,18 @@ class LLMEngine:
         if prompt_ids and (min(prompt_ids) < 0 or max(prompt_ids) >= self.arch.vocab_size):
             # an out-of-range id would be an out-of-bounds embedding read on the GPU
             raise ValueError(f"prompt token id outside [0, {self.arch.vocab_size})")
+        if sampling.prompt_logprobs is not None:
+            # every prompt row's logits are computed (keep_rows=None), which TP followers do not mirror and a
+            # prefill worker's one-token export does not carry
+            if getattr(self.model, "tp", None) is not None and self.model.tp.enabled:
+                raise ValueError("prompt_logprobs is not supported on a tensor-parallel engine")
+            if export_kv:
+                raise ValueError("prompt_logprobs is not supported on the disaggregated prefill path")
         seq = Sequence(request_id, list(prompt_ids), dataclasses.replace(sampling), on_finish=on_finish,
                        user_data=user_data, on_token=on_token)
+        if sampling.prompt_logprobs is not None:
+            seq.prompt_logprobs_out = [None] * len(prompt_ids)
+        seq._on_token_entry = _takes_entry(on_token)  # type: ignore[attr-defined]
         if export_kv:  # disaggregated prefill: stop after the first token and hand the prompt KV over
             seq.sampling.max_tokens = 1
             seq.export_kv = True  # type: ignore[attr-defined]
@@ -208,6 +240,13 @@ class LLMEngine:
         seq = Sequence(packet.request_id, list(packet.prompt_ids), dataclasses.replace(sampling),
                        on_finish=on_finish, imported_kv=True)
         seq.output_ids = [int(packet.first_token)]
+        if sampling.logprobs is not None:
+            # the prefill worker's entry for the first token (None over a channel that does not carry it)
+            fl = getattr(packet, "first_logprobs", None)
+            seq.output_logprobs = [None if fl is None else
+                                   {"logprob": fl["logprob"], "rank": fl["rank"],
+                                    "top_ids": list(fl["top_ids"][:sampling.logprobs]),
+                                    "top_logprobs": list(fl["top_logprobs"][:sampling.logprobs])}]
         seq.first_token_time = time.perf_counter()
         if packet.ttft_ms is not None:
             seq.arrival = seq.first_token_time - packet.ttft_ms / 1e3
@@ -257,7 +296,7 @@ class LLMEngine:
             toks_k = self.runner.decode_continue(self._continuation_window(seqs, pending))
             now = time.perf_counter()
             self.stats["decode_time"] += now - t0
-            self._apply_window(seqs, toks_k, finished)
+            self._apply_window(seqs, toks_k, finished, self._take_logprobs())
             if self.runner.inflight is not None:
                 self.stats["queued_windows"] = self.stats.get("queued_windows", 0) + 1
                 self.stats["steps"] += 1
@@ -290,17 +329,20 @@ class LLMEngine:
             now = time.perf_counter()
             self.stats["mixed_time" if out.decode else "prefill_time"] = \
                 self.stats.get("mixed_time" if out.decode else "prefill_time", 0.0) + now - t0
+            lps = self._take_logprobs()
+            lp0 = lps[0] if lps else None
+            self._record_prompt_logprobs(chunks)
             ntok = sum(c.length for c in chunks if not c.decode)
             if ntok and not out.decode:
                 per = (now - t0) / ntok
                 self._pf_tok_est = per if not self._pf_tok_est else 0.8 * self._pf_tok_est + 0.2 * per
-            for c, tok in zip(chunks, toks):
+            for i, (c, tok) in enumerate(zip(chunks, toks)):
                 seq = c.seq
                 if c.decode:
                     if seq.status == SeqStatus.FINISHED:
                         continue
                     seq.num_computed += 1
-                    self._append(seq, tok, finished)
+                    self._append(seq, tok, finished, logprob_entry(lp0, i, seq.sampling.logprobs))
                     continue
                 seq.num_computed = c.start + c.length
                 if tok is None:
@@ -309,7 +351,7 @@ class LLMEngine:
                 self.stats["prefix_hit_tokens"] += seq.num_prefix_hit
                 if seq.first_token_time is None:
                     seq.first_token_time = now
-                self._append(seq, tok, finished)
+                self._append(seq, tok, finished, logprob_entry(lp0, i, seq.sampling.logprobs))
         else:
             k = self._decode_window(out.decode)
             if k > 1:
@@ -321,7 +363,7 @@ class LLMEngine:
             now = time.perf_counter()
             self.stats["decode_time"] += now - t0
             self._step_est = 0.8 * self._step_est + 0.2 * (now - t0) / max(1, len(toks_k))
-            self._apply_window(out.decode, toks_k, finished)
+            self._apply_window(out.decode, toks_k, finished, self._take_logprobs())
         self.stats["steps"] += 1
         if self.cfg.kv_block_ttl_s:
             self.blocks.evict_expired()
@@ -426,13 +468,35 @@ class LLMEngine:
             seq.swap_buf = buf
             self.stats["swap_out_bytes"] = self.stats.get("swap_out_bytes", 0) + buf.numel() * buf.element_size()
 
-    def _apply_window(self, seqs: List[Sequence], toks_k: List[List[int]], finished: List[Sequence]) -> None:
-        for toks in toks_k:
-            for seq, tok in zip(seqs, toks):
+    def _take_logprobs(self):
+        take = getattr(self.runner, "take_logprobs", None)
+        return take() if take is not None else None
+
+    def _record_prompt_logprobs(self, chunks) -> None:
+        """File the step's prompt logprobs by absolute position. A recompute after a preemption scores positions
+        again: those keep their first value."""
+        res = getattr(self.runner, "last_prompt_logprobs", None)
+        if not res:
+            return
+        self.runner.last_prompt_logprobs = None
+        for i, (pos0, lp, rk, tl, ti) in res.items():
+            seq = chunks[i].seq
+            dst, n = seq.prompt_logprobs_out, seq.sampling.prompt_logprobs
+            if dst is None:
+                continue
+            for j in range(len(lp)):
+                if pos0 + j < len(dst) and dst[pos0 + j] is None:
+                    dst[pos0 + j] = {"logprob": lp[j], "rank": rk[j], "top_ids": ti[j][:n], "top_logprobs": tl[j][:n]}
+
+    def _apply_window(self, seqs: List[Sequence], toks_k: List[List[int]], finished: List[Sequence],
+                      lps_k: Optional[List[tuple]] = None) -> None:
+        for j, toks in enumerate(toks_k):
+            lp = lps_k[j] if lps_k else None
+            for i, (seq, tok) in enumerate(zip(seqs, toks)):
                 if seq.status == SeqStatus.FINISHED:  # stopped earlier in the window (or aborted): discard
-                    continue
+                    continue                          # (the token's logprob entry goes with it)
                 seq.num_computed += 1
-                self._append(seq, tok, finished)
+                self._append(seq, tok, finished, logprob_entry(lp, i, seq.sampling.logprobs) if lp else None)
         self.stats["decode_windows"] = self.stats.get("decode_windows", 0) + 1
 
     def _continuation_window(self, seqs: List[Sequence], pending: int) -> int:
@@ -501,11 +565,16 @@ class LLMEngine:
                 return 1
         return k
 
-    def _append(self, seq: Sequence, tok: int, finished: List[Sequence]) -> None:
+    def _append(self, seq: Sequence, tok: int, finished: List[Sequence], entry: Optional[dict] = None) -> None:
         seq.output_ids.append(int(tok))
+        if seq.sampling.logprobs is not None:
+            seq.output_logprobs.append(entry)  # one per output token, aligned with output_ids
         self.stats["generated_tokens"] += 1
         if seq.on_token is not None:
-            seq.on_token(seq, int(tok))
+            if getattr(seq, "_on_token_entry", False):
+                seq.on_token(seq, int(tok), entry)
+            else:
+                seq.on_token(seq, int(tok))
         sp = seq.sampling
         reason = None
         if not sp.ignore_eos and self.eos_token_id is not None and tok == self.eos_token_id:
@@ -552,6 +621,9 @@ class LLMEngine:
             seq.output_ids = prev + seq.output_ids
             seq.prompt_ids = seq.prompt_ids[: len(seq.prompt_ids) - len(prev)]
             seq._preempted_outputs = []  # type: ignore[attr-defined]
+            if seq.sampling.logprobs is not None:
+                seq.output_logprobs = getattr(seq, "_preempted_logprobs", []) + seq.output_logprobs
+                seq._preempted_logprobs = []  # type: ignore[attr-defined]
         if seq.on_finish is not None:
             seq.on_finish(seq)
 
@@ -573,4 +645,5 @@ class LLMEngine:
         s["kv_pool_gib"] = self.pool.nbytes / 2**30
         s["graphs"] = list(self.runner.graph_sizes)
         s["decode_weight_layout"] = self.decode_weight_layout
+        s["logprob_launches"] = getattr(self.runner, "logprob_launches", 0)  # ops.token_logprobs launches
         return s

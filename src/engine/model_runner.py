@@ -129,6 +129,19 @@ class ModelRunner:
                        torch.zeros(self.max_seqs, dtype=torch.int32, device=dev))
         self.d_tokens = torch.zeros(2 * self.k_max, self.max_seqs, dtype=i64, device=dev)
         self.d_ctl = torch.zeros(2, dtype=i32, device=dev)
+        # per-token log-probabilities (ops.token_logprobs: logprob, rank, top logprobs, top ids), shaped like
+        # d_tokens and written by a launch queued behind a step's graph replay — only for batches with a row
+        # that asked (SamplingParams.logprobs); the pinned twins come back with h_tokens, only then
+        top = ops.LOGPROBS_MAX_TOP
+        lp_shapes = (((2 * self.k_max, self.max_seqs), torch.float32), ((2 * self.k_max, self.max_seqs), i32),
+                     ((2 * self.k_max, self.max_seqs, top), torch.float32), ((2 * self.k_max, self.max_seqs, top), i32))
+        self.d_lp = tuple(torch.zeros(s, dtype=t, device=dev) for s, t in lp_shapes)
+        self.h_lp = tuple(torch.zeros(s, dtype=t, pin_memory=pin) for s, t in lp_shapes)
+        self.graph_logits: Dict[int, torch.Tensor] = {}   # each captured graph's logits [pad, vocab] (kept alive)
+        self._last_logits: Optional[torch.Tensor] = None  # of the latest _decode_forward
+        self.logprob_launches = 0
+        self.last_logprobs = None         # the latest call's logprobs (take_logprobs), None when no row asked
+        self.last_prompt_logprobs = None  # the latest prefill's prompt logprobs: {chunk index: (positions, ...)}
         self.d_adv_ticket = torch.zeros(1, dtype=i32, device=dev)  # sample_advance's row ticket (re-armed in-kernel)
         if self.is_cuda:
             maxp = ops.decode_partials(max_model_len)
@@ -212,6 +225,39 @@ class ModelRunner:
             return self.h_out[:n].tolist()
         return ids[:n].tolist()
 
+    # ----------------------------------------------------------- logprobs
+    @staticmethod
+    def _lp_top(seqs) -> int:
+        """-1 when no sequence asked for logprobs, else the largest number of top tokens any of them asked for."""
+        top = -1
+        for s in seqs:
+            v = s.sampling.logprobs
+            if v is not None and v > top:
+                top = v
+        return top
+
+    def _launch_logprobs(self, logits: torch.Tensor, targets: torch.Tensor, n: int, row: int, top: int) -> None:
+        """Queue ops.token_logprobs for the step's first n rows (targets: the ids just sampled) into row `row`
+        of the logprob buffers."""
+        ops.token_logprobs(logits[:n], targets[:n], top, out=tuple(d[row] for d in self.d_lp))
+        self.logprob_launches += 1
+
+    def _lp_to_host(self, lo: int, hi: int) -> None:
+        for d, h in zip(self.d_lp, self.h_lp):
+            h[lo:hi].copy_(d[lo:hi], non_blocking=self.is_cuda)
+
+    def _lp_read(self, lo: int, hi: int, n: int, top: int) -> List[tuple]:
+        """Per step: (logprobs [n], ranks [n], top logprobs [n][top], top ids [n][top]) from the host twins."""
+        lp, rk, tl, ti = self.h_lp
+        return [(lp[r, :n].tolist(), rk[r, :n].tolist(), tl[r, :n, :top].tolist(), ti[r, :n, :top].tolist())
+                for r in range(lo, hi)]
+
+    def take_logprobs(self):
+        """The logprobs of the latest prefill / decode / decode_multi / decode_continue call (None when no row
+        asked): one tuple per step as :meth:`_lp_read` gives them (prefill: one tuple over the sampled rows)."""
+        r, self.last_logprobs = self.last_logprobs, None
+        return r
+
     def _queue_fault_readback(self) -> None:
         """Queue device-side error words behind the step (read with the tokens, same sync). None on one GPU;
         the TP runner reads the one-shot collectives' sticky error word."""
@@ -256,34 +302,91 @@ class ModelRunner:
             nl = self.h_last.numpy()
             nl[:nd] = nl[done]
         greedy = self._fill_sampling([chunks[i].seq for i in done], nd) if nd else True
+        lp_top = self._lp_top(chunks[i].seq for i in done) if nd else -1
+        plan = self._prompt_logprob_plan(chunks)
+        self.last_logprobs = self.last_prompt_logprobs = None
         self._h2d(t, n, with_cu=True)
         max_q = max(c.length for c in chunks)
         self._sync_step(self.KIND_PREFILL, t, n, max_q, nd)
-        ids = self._exec_prefill(t, n, max_q, nd, greedy, kv_hook=kv_hook)
+        ids = self._exec_prefill(t, n, max_q, nd, greedy, kv_hook=kv_hook, lp_top=lp_top, plan=plan)
         res: List[Optional[int]] = [None] * n
         if nd:
+            if lp_top >= 0:
+                self._lp_to_host(0, 1)
             vals = self._to_host(ids, nd)
             for j, i in enumerate(done):
                 res[i] = vals[j]
+            if lp_top >= 0:  # row j of the launch belongs to chunk done[j]
+                lp, rk, tl, ti = self._lp_read(0, 1, nd, lp_top)[0]
+                full = ([None] * n, [None] * n, [None] * n, [None] * n)
+                for j, i in enumerate(done):
+                    full[0][i], full[1][i], full[2][i], full[3][i] = lp[j], rk[j], tl[j], ti[j]
+                self.last_logprobs = [full]
         elif self.is_cuda:
             self._queue_fault_readback()
             torch.cuda.current_stream(self.device).synchronize()
             self._raise_on_fault()
         return res
 
-    def _exec_prefill(self, t: int, n: int, max_q: int, nd: int, greedy: bool, kv_hook=None) -> Optional[torch.Tensor]:
-        # the last layer runs only for the sampled rows (CausalLM._last_layer_kept_rows; DIE_PRUNE_LAST=0: all)
-        keep = self.d_last[:nd] if self.prune_last else None
+    PROMPT_LOGPROB_SLAB = 1024  # rows of prompt logits at a time (<= 256 MiB of bf16 logits at a 128K vocabulary)
+
+    @staticmethod
+    def _prompt_logprob_plan(chunks: List[PrefillChunk]) -> List[tuple]:
+        """For every prompt chunk of a request with prompt_logprobs: (chunk index, first row in the step's flat
+        batch, first scored position, target ids, top-N). Row p (absolute position) scores prompt token p + 1 —
+        the last row of a chunk that does not complete the prompt scores the first token of the next chunk; the
+        row that completes the prompt samples instead. After a recompute preemption the prompt carries the earlier
+        outputs at its end: only the original prompt is scored."""
+        plan = []
+        row0 = 0
+        for i, c in enumerate(chunks):
+            s = c.seq
+            top = None if c.decode else s.sampling.prompt_logprobs
+            if top is not None:
+                orig = s.prompt_len - len(getattr(s, "_preempted_outputs", ()))
+                last = min(c.start + c.length, orig - 1)  # rows [start, last) have a next prompt token
+                if last > c.start:
+                    plan.append((i, row0, c.start + 1, s.prompt_ids[c.start + 1: last + 1], int(top)))
+            row0 += c.length
+        return plan
+
+    def _prompt_logprobs(self, hidden: torch.Tensor, plan: List[tuple]) -> dict:
+        """{chunk index: (first position, logprobs, ranks, top logprobs, top ids)} from the step's hidden rows,
+        PROMPT_LOGPROB_SLAB rows of logits at a time."""
+        res = {}
+        for i, row0, pos0, targets, top in plan:
+            tg = torch.tensor(targets, dtype=torch.int64).to(self.device)
+            parts = ([], [], [], [])
+            for a in range(0, len(targets), self.PROMPT_LOGPROB_SLAB):
+                b = min(len(targets), a + self.PROMPT_LOGPROB_SLAB)
+                logits = self.model.compute_logits(hidden[row0 + a: row0 + b])
+                out = ops.token_logprobs(logits, tg[a:b], top)
+                self.logprob_launches += 1
+                for acc, x in zip(parts, out):
+                    acc.extend(x.tolist())
+            res[i] = (pos0,) + parts
+        return res
+
+    def _exec_prefill(self, t: int, n: int, max_q: int, nd: int, greedy: bool, kv_hook=None, lp_top: int = -1,
+                      plan: Optional[List[tuple]] = None) -> Optional[torch.Tensor]:
+        # the last layer runs only for the sampled rows (CausalLM._last_layer_kept_rows; DIE_PRUNE_LAST=0: all);
+        # a step that scores prompt tokens (prompt_logprobs) needs every row
+        keep = self.d_last[:nd] if self.prune_last and not plan else None
         meta = AttnMetadata(is_prefill=True, slot_mapping=self.d_slots[:t], block_tables=self.d_bt[:n],
                             ctx_lens=self.d_ctx[:n], cu_q=self.d_cu[: n + 1], max_q_len=max_q, kv_hook=kv_hook,
                             keep_rows=keep)
         hidden = self.model.forward(self.d_ids[:t], self.d_pos[:t], meta, self.pool.tensor)
+        if plan:
+            self.last_prompt_logprobs = self._prompt_logprobs(hidden, plan)
         if not nd:
             return None
-        if hidden.shape[0] != nd:  # a path that computed every row (e.g. the slab path of small steps)
+        if hidden.shape[0] != nd or plan:  # a path that computed every row (e.g. the slab path of small steps)
             hidden = hidden.index_select(0, self.d_last[:nd])
         logits = self.model.compute_logits(hidden)
-        return self._sample(logits, nd, greedy, self.d_out)
+        ids = self._sample(logits, nd, greedy, self.d_out)
+        if lp_top >= 0:  # the first generated token's logprobs (the leader only: followers have nothing to report)
+            self._launch_logprobs(logits, ids, nd, 0, lp_top)
+        return ids
 
     # ------------------------------------------------------------- decode
     def _fused_tail(self, n: int) -> bool:
@@ -310,6 +413,7 @@ class ModelRunner:
                 and self.model.lm_head_argmax_parts() == self.d_lmpart.shape[1] else None)
         logits = self.model.compute_logits(hidden, argmax_parts=amax) if amax is not None else \
             self.model.compute_logits(hidden)
+        self._last_logits = logits  # ops.token_logprobs reads them behind the step (capture_graphs keeps each graph's)
         if not self.is_cuda:
             return ops.sample(logits, self.d_temp[:n], self.d_topk[:n], self.d_topp[:n], self.d_seed[:n],
                               self.d_step[:n])
@@ -347,6 +451,9 @@ class ModelRunner:
             with torch.cuda.graph(g, pool=self._graph_pool):
                 self._decode_forward(b)
             self.graphs[b] = g
+            # the graph's logits [b, vocab]: read by the logprob launch behind a replay; the reference also keeps
+            # the shared pool from handing this memory to a graph captured later
+            self.graph_logits[b] = self._last_logits
         torch.cuda.synchronize(self.device)
         self.graph_sizes = sizes
         logger.info("captured decode hipGraphs for batch sizes %s", sizes)
@@ -376,7 +483,15 @@ class ModelRunner:
             self.d_ctl.copy_(self.h_ctl, non_blocking=True)
         self._sync_step(self.KIND_DECODE, n, pad)
         ids = self._exec_decode(n, pad)
-        return self._to_host(ids, n)
+        top = self._lp_top(seqs)
+        self.last_logprobs = None
+        if top < 0:
+            return self._to_host(ids, n)
+        self._launch_logprobs(self.graph_logits[pad] if pad in self.graphs else self._last_logits, ids, n, 0, top)
+        self._lp_to_host(0, 1)
+        toks = self._to_host(ids, n)
+        self.last_logprobs = self._lp_read(0, 1, n, top)
+        return toks
 
     @torch.inference_mode()
     def decode_multi(self, seqs: List[Sequence], k: int, k_next: int = 0) -> List[List[int]]:
@@ -408,9 +523,8 @@ class ModelRunner:
         self.h_ctl[1] = n
         self.d_ctl.copy_(self.h_ctl, non_blocking=True)
         self._sync_window(n, pad, k)
-        for _ in range(k):
-            g.replay()
-        self.h_tokens[:k].copy_(self.d_tokens[:k], non_blocking=True)
+        top = self._lp_top(seqs)
+        self._replay_window(g, pad, n, k, 0, top)
         self._queue_fault_readback()
         if k_next > 1:
             ev = torch.cuda.Event()
@@ -420,7 +534,24 @@ class ModelRunner:
         else:
             torch.cuda.current_stream(self.device).synchronize()
         self._raise_on_fault()
+        self.last_logprobs = self._lp_read(0, k, n, top) if top >= 0 else None
         return self.h_tokens[:k, :n].tolist()
+
+    def _replay_window(self, g, pad: int, n: int, k: int, base: int, top: int) -> None:
+        """k replays queued back to back, their tokens into rows [base, base + k); top >= 0 (a row asked for
+        logprobs): one ops.token_logprobs launch behind each replay — it reads that step's logits and sampled ids
+        before the next replay overwrites them (stream order) — and the logprob rows come back with the tokens."""
+        if top < 0:
+            for _ in range(k):
+                g.replay()
+            self.h_tokens[base:base + k].copy_(self.d_tokens[base:base + k], non_blocking=True)
+            return
+        logits = self.graph_logits[pad]
+        for i in range(k):
+            g.replay()
+            self._launch_logprobs(logits, self.d_out, n, base + i, top)
+        self.h_tokens[base:base + k].copy_(self.d_tokens[base:base + k], non_blocking=True)
+        self._lp_to_host(base, base + k)
 
     def _queue_continuation(self, seqs: List[Sequence], pending: int, k: int, base: int) -> None:
         """Queue k more decode steps for `seqs` behind a window of `pending` steps whose tokens the
@@ -441,14 +572,12 @@ class ModelRunner:
         self.d_slots[:pad].copy_(hsl[:pad], non_blocking=True)
         self.d_ctl[0:1].fill_(base)  # token rows [base, base + k)
         self._sync_continuation(par, pad, k, base)
-        g = self.graphs[pad]
-        for _ in range(k):
-            g.replay()
-        self.h_tokens[base:base + k].copy_(self.d_tokens[base:base + k], non_blocking=True)
+        top = self._lp_top(seqs)
+        self._replay_window(self.graphs[pad], pad, n, k, base, top)
         self._queue_fault_readback()
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
-        self.inflight = {"seqs": list(seqs), "k": k, "base": base, "event": ev}
+        self.inflight = {"seqs": list(seqs), "k": k, "base": base, "event": ev, "lp_top": top}
 
     def inflight_batch(self):
         """(sequences, steps) of the queued window, or None."""
@@ -467,6 +596,7 @@ class ModelRunner:
         w["event"].synchronize()
         self._raise_on_fault()
         b, k, n = w["base"], w["k"], len(w["seqs"])
+        self.last_logprobs = self._lp_read(b, b + k, n, w["lp_top"]) if w["lp_top"] >= 0 else None
         return self.h_tokens[b:b + k, :n].tolist()
 
     def _exec_decode(self, n: int, pad: int) -> torch.Tensor:

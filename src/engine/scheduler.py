@@ -361,6 +361,9 @@ class Scheduler:
         seq.sampling.max_tokens -= len(seq.output_ids)
         seq._preempted_outputs = getattr(seq, "_preempted_outputs", []) + seq.output_ids  # type: ignore[attr-defined]
         seq.output_ids = []
+        # their logprob entries stay aligned with them (LLMEngine._complete puts both back)
+        seq._preempted_logprobs = getattr(seq, "_preempted_logprobs", []) + seq.output_logprobs  # type: ignore
+        seq.output_logprobs = []
         seq.block_hashes = None
         self.waiting.appendleft(seq)
 

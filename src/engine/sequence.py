@@ -43,6 +43,11 @@ class Sequence:
     # Disaggregation: a sequence whose prompt KV arrives from a prefill worker
     imported_kv: bool = False
     swap_buf: Any = None             # host copy of the KV blocks while SWAPPED
+    # SamplingParams.logprobs: one entry per output token, {"logprob", "rank", "top_ids", "top_logprobs"} (None
+    # where the producer could not report one, e.g. a first token imported over a channel that drops it)
+    output_logprobs: List[Optional[dict]] = field(default_factory=list)
+    # SamplingParams.prompt_logprobs: one entry per prompt position, None at position 0 (None: not requested)
+    prompt_logprobs_out: Optional[List[Optional[dict]]] = None
 
     def __len__(self) -> int:
         return len(self.prompt_ids) + len(self.output_ids)

@@ -6,13 +6,22 @@ coordinator's framed-RPC API. It holds no model state — every request becomes 
     python -m src.http_server --coordinator 127.0.0.1:9000 --port 8000
 
     POST /v1/completions   {"model", "prompt": str | [token ids], "max_tokens", "temperature",
-                            "top_p", "top_k", "seed", "stop_token_ids", "ignore_eos", "stream"}
+                            "top_p", "top_k", "seed", "stop_token_ids", "ignore_eos", "stream",
+                            "logprobs": 0..20, "echo"}
                            stream=true answers with server-sent events ("data: {...}" chunks,
-                           then "data: [DONE]"), text and token ids per chunk
+                           then "data: [DONE]"), text and token ids per chunk.
+                           logprobs=N: choice.logprobs = {"tokens", "token_logprobs", "top_logprobs":
+                           [{token: logprob}] (the N most likely), "text_offset", "top_token_ids"}, of the
+                           model's raw distribution (before temperature / top-k / top-p); with echo=true the
+                           prompt tokens are scored too (choice.prompt_logprobs, same layout, null first)
     POST /v1/chat/completions  {"model", "messages": [{"role", "content"}], same sampling keys}:
                            the messages rendered in the Llama-3 chat layout (header / end-of-turn
                            markers as text) plus an open assistant turn; answers "chat.completion"
-                           objects, or "chat.completion.chunk" deltas when streaming
+                           objects, or "chat.completion.chunk" deltas when streaming.
+                           logprobs=true (with top_logprobs 0..20): choice.logprobs = {"content": [{"token",
+                           "logprob", "bytes", "top_logprobs": [{"token", "logprob", "bytes"}]}]}
+    Stream chunks carry the same logprobs layouts for their delta; a request that does not ask gets
+    "logprobs": null; an out-of-range value is a 400. Non-finite logprobs arrive as -9999.0.
     GET  /v1/models        the coordinator's registered models
     GET  /health           200 when the coordinator answers its health RPC
     GET  /metrics          Prometheus text format (requests, errors, latency, tokens)
@@ -36,6 +45,53 @@ from src.utils import setup_logging
 
 _SAMPLING = ("max_tokens", "temperature", "top_p", "top_k", "seed", "stop_token_ids", "ignore_eos")
 _ROLES = ("system", "user", "assistant", "tool")
+MAX_LOGPROBS = 20
+
+
+def _logprob_count(v: Any, name: str) -> int:
+    if isinstance(v, bool) or not isinstance(v, int) or not 0 <= v <= MAX_LOGPROBS:
+        raise ValueError(f"{name} must be an integer in [0, {MAX_LOGPROBS}]")
+    return v
+
+
+def _token_strings(lp: Dict[str, Any]):
+    """(tokens, top tokens) of a backend logprobs block: its per-token strings, or the ids as text without them."""
+    n = len(lp.get("token_logprobs") or [])
+    toks = lp.get("tokens") or [""] * n
+    tops = lp.get("top_tokens") or [None if r is None else [str(t) for t in r] for r in lp.get("top_token_ids") or []]
+    return toks, tops
+
+
+def render_logprobs(lp: Optional[Dict[str, Any]], chat: bool, offset: int = 0) -> Optional[Dict[str, Any]]:
+    """A backend logprobs block ({"token_logprobs", "ranks", "top_token_ids", "top_logprobs", "tokens",
+    "top_tokens"}) in the OpenAI completions or chat layout; offset: the text position of its first token."""
+    if not isinstance(lp, dict):
+        return None
+    toks, tops = _token_strings(lp)
+    vals, top_vals = lp.get("token_logprobs") or [], lp.get("top_logprobs") or []
+    if chat:
+        def item(tok, v):
+            return {"token": tok, "logprob": v, "bytes": list(tok.encode("utf-8"))}
+        content = []
+        for i, v in enumerate(vals):
+            e = item(toks[i], v)
+            row = tops[i] if i < len(tops) and tops[i] is not None else []
+            e["top_logprobs"] = [item(t, top_vals[i][j]) for j, t in enumerate(row)]
+            content.append(e)
+        return {"content": content}
+    offsets, top_dicts = [], []
+    for i in range(len(vals)):
+        offsets.append(offset)
+        offset += len(toks[i])
+        if i >= len(tops) or tops[i] is None:
+            top_dicts.append(None)
+            continue
+        d: Dict[str, Any] = {}
+        for j, t in enumerate(tops[i]):  # two ids may render alike: the more likely one keeps the key
+            d.setdefault(t, top_vals[i][j])
+        top_dicts.append(d)
+    return {"tokens": list(toks), "token_logprobs": list(vals), "top_logprobs": top_dicts, "text_offset": offsets,
+            "top_token_ids": lp.get("top_token_ids")}
 
 
 def render_chat(messages: Any) -> str:
@@ -78,7 +134,7 @@ class Gateway:
         self.client.close()
 
     @staticmethod
-    def _inputs(body: Dict[str, Any]) -> Dict[str, Any]:
+    def _inputs(body: Dict[str, Any], chat: bool = False) -> Dict[str, Any]:
         prompt = body.get("prompt")
         if isinstance(prompt, list) and len(prompt) == 1 and isinstance(prompt[0], (str, list)):
             prompt = prompt[0]  # OpenAI allows a batch of one
@@ -90,12 +146,29 @@ class Gateway:
             raise ValueError("prompt must be a string or a list of token ids")
         inp.update({k: body[k] for k in _SAMPLING if k in body and body[k] is not None})
         inp.setdefault("max_tokens", 16)
+        if chat:  # logprobs: bool, top_logprobs: int
+            want = body.get("logprobs")
+            if want is not None and not isinstance(want, bool):
+                raise ValueError("logprobs must be a boolean")
+            if body.get("top_logprobs") is not None:
+                n = _logprob_count(body["top_logprobs"], "top_logprobs")
+                if not want:
+                    raise ValueError("top_logprobs needs logprobs: true")
+                inp["logprobs"] = n
+            elif want:
+                inp["logprobs"] = 0
+        elif body.get("logprobs") is not None:  # logprobs: int; with echo the prompt is scored too
+            inp["logprobs"] = _logprob_count(body["logprobs"], "logprobs")
+            if body.get("echo"):
+                inp["prompt_logprobs"] = inp["logprobs"]
         return inp
 
     @staticmethod
     def _choice(out: Dict[str, Any], chat: bool = False) -> Dict[str, Any]:
         c = {"index": 0, "token_ids": out.get("token_ids", []), "finish_reason": out.get("finish_reason"),
-             "logprobs": None}
+             "logprobs": render_logprobs(out.get("logprobs"), chat)}
+        if out.get("prompt_logprobs") is not None:
+            c["prompt_logprobs"] = render_logprobs(out["prompt_logprobs"], chat)
         if chat:
             c["message"] = {"role": "assistant", "content": out.get("text", "")}
         else:
@@ -115,7 +188,7 @@ class Gateway:
             model = body["model"]
             if chat:
                 body = dict(body, prompt=render_chat(body.get("messages")))
-            inputs = self._inputs(body)
+            inputs = self._inputs(body, chat)
         except (ValueError, KeyError, json.JSONDecodeError) as e:
             return web.json_response({"error": {"message": f"bad request: {e}", "type": "invalid_request"}},
                                      status=400)
@@ -130,21 +203,25 @@ class Gateway:
         await resp.prepare(req)
         final: Optional[Dict[str, Any]] = None
         first = True
+        offset = 0  # text position of the next chunk (completions logprobs' text_offset)
         try:
             async for frame in self.client.infer_stream(model, inputs):
                 if frame.get("done") is False:
+                    lps = render_logprobs(frame.get("delta_logprobs"), chat, offset)
+                    offset += len(frame.get("delta_text", ""))
                     if chat:
                         delta: Dict[str, Any] = {"content": frame.get("delta_text", "")}
                         if first:
                             delta["role"] = "assistant"
                         chunk = {"id": cid, "object": "chat.completion.chunk", "created": created, "model": model,
                                  "choices": [{"index": 0, "delta": delta,
-                                              "token_ids": frame.get("delta_token_ids", []), "finish_reason": None}]}
+                                              "token_ids": frame.get("delta_token_ids", []), "finish_reason": None,
+                                              "logprobs": lps}]}
                     else:
                         chunk = {"id": cid, "object": "text_completion", "created": created, "model": model,
                                  "choices": [{"index": 0, "text": frame.get("delta_text", ""),
                                               "token_ids": frame.get("delta_token_ids", []),
-                                              "finish_reason": None}]}
+                                              "finish_reason": None, "logprobs": lps}]}
                     first = False
                     await resp.write(b"data: " + json.dumps(chunk).encode() + b"\n\n")
                 else:

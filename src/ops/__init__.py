@@ -217,6 +217,38 @@ def sample(logits, temperature=None, top_k=None, top_p=None, seeds=None, steps=N
     return out
 
 
+LOGPROBS_MAX_TOP = 20  # the OpenAI chat API's cap (launchers.h)
+
+
+def token_logprobs(logits: torch.Tensor, targets: torch.Tensor, top_n: int, out=None):
+    """Log-probabilities of the model's RAW distribution (``log_softmax`` of the bf16 row in fp32, before
+    temperature and filters) -> ``(lp fp32 [R], rank int32 [R], top_lp fp32 [R, top_n], top_id int32 [R, top_n])``.
+    Tokens are ordered by larger logit, then lower id: ``rank`` counts the tokens strictly before ``targets[r]``
+    (the argmax has rank 0) and the top lists are the first ``top_n`` (0..20) tokens in that order. A target
+    outside ``[0, vocab)`` gives ``-inf`` and ``vocab``. ``out`` = the four tensors to write into (the top lists
+    may be wider than ``top_n``: the columns beyond it are left alone and the returned lists are views)."""
+    top_n = int(top_n)
+    if not logits.is_cuda:
+        res = ref.token_logprobs(logits, targets, top_n)
+        if out is None:
+            return res
+        r = logits.shape[0]
+        out[0][:r].copy_(res[0])
+        out[1][:r].copy_(res[1])
+        out[2][:r, :top_n].copy_(res[2])
+        out[3][:r, :top_n].copy_(res[3])
+        return out[0][:r], out[1][:r], out[2][:r, :top_n], out[3][:r, :top_n]
+    r = logits.shape[0]
+    if out is None:
+        dev = logits.device
+        w = max(top_n, 0)
+        out = (torch.empty(r, dtype=torch.float32, device=dev), torch.empty(r, dtype=torch.int32, device=dev),
+               torch.empty(r, w, dtype=torch.float32, device=dev), torch.empty(r, w, dtype=torch.int32, device=dev))
+    lp, rank, top_lp, top_id = out
+    _kern().token_logprobs(lp, rank, top_lp, top_id, logits, targets, top_n)
+    return lp[:r], rank[:r], top_lp[:r, :top_n], top_id[:r, :top_n]
+
+
 def sample_advance(logits, temperature, top_k, top_p, seeds, steps, out, lm_part, ids, pos, ctx, slots, bt, tokens,
                    cnt, n_real, block_size: int, ticket, embed=None) -> torch.Tensor:
     """:func:`sample` from the LM head's candidates (``lm_part``) fused with :func:`decode_advance`: every row's

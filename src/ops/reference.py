@@ -141,6 +141,30 @@ def sample(logits, temperature=None, top_k=None, top_p=None, seeds=None, steps=N
     return out
 
 
+def token_logprobs(logits: torch.Tensor, targets: torch.Tensor, top_n: int):
+    """Log-probabilities of the raw distribution: float64 ``log_softmax``; tokens ordered by larger logit, then
+    lower id (a stable descending sort). Returns (lp fp32 [R], rank int32 [R], top_lp fp32 [R, top_n], top_id
+    int32 [R, top_n]); a target outside [0, vocab) gives -inf and rank vocab."""
+    if not 0 <= top_n <= 20:
+        raise ValueError("top_n must be in [0, 20]")
+    rows, vocab = logits.shape
+    if top_n > vocab:
+        raise ValueError("top_n exceeds the vocabulary")
+    z = logits.double()
+    lsm = torch.log_softmax(z, dim=-1)
+    _, order = torch.sort(z, dim=-1, descending=True, stable=True)
+    targets = targets.to(device=logits.device, dtype=torch.long)[:rows]
+    ok = (targets >= 0) & (targets < vocab)
+    t = torch.where(ok, targets, torch.zeros_like(targets))
+    place = torch.empty_like(order)
+    place.scatter_(1, order, torch.arange(vocab, device=logits.device).expand(rows, vocab))
+    rank = torch.where(ok, place.gather(1, t[:, None])[:, 0], torch.full_like(t, vocab)).int()
+    lp = torch.where(ok, lsm.gather(1, t[:, None])[:, 0], torch.full((rows,), float("-inf"), dtype=torch.float64,
+                                                                     device=logits.device)).float()
+    top_id = order[:, :top_n]
+    return lp, rank, lsm.gather(1, top_id).float(), top_id.int()
+
+
 def topk_softmax(gating: torch.Tensor, k: int, renorm: bool = True):
     p = torch.softmax(gating.float(), dim=-1)
     w, ids = torch.topk(p, k, dim=-1)

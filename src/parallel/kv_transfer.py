@@ -21,6 +21,7 @@ no prompt recompute. For Llama-3-8B a 512-token prompt is 64 MiB of KV.
 from __future__ import annotations
 
 from dataclasses import dataclass, field
+import math
 import threading
 import time
 from typing import Any, Callable, Dict, List, Optional
@@ -45,6 +46,10 @@ class KVPacket:
     # called by the importing engine thread with an event recorded behind its scatter (the kv buffer
     # may be reused once that event completes): frees an IPC landing-zone slot without a host sync
     on_imported: Optional[Callable[[Any], None]] = None
+    # the first token's logprob entry ({"logprob", "rank", "top_ids", "top_logprobs"}) when the request asked for
+    # logprobs. Carried by packet_meta / packet_to_wire; the torch.distributed channel (RCCLChannel) does not
+    # carry it: the first entry of the request's logprobs is then None
+    first_logprobs: Optional[Dict[str, Any]] = None
 
     @property
     def nbytes(self) -> int:
@@ -459,10 +464,23 @@ class IPCSender:
         self.ptrs = []
 
 
+def _wire_logprobs(e: Optional[Dict[str, Any]]) -> Optional[Dict[str, Any]]:
+    """A logprob entry for the wire: plain lists, non-finite values floored (every transport stays valid JSON)."""
+    if e is None:
+        return None
+    from src.postproc import LOGPROB_FLOOR
+
+    def f(x):
+        return float(x) if math.isfinite(x) else LOGPROB_FLOOR
+    return {"logprob": f(e["logprob"]), "rank": int(e["rank"]), "top_ids": [int(t) for t in e["top_ids"]],
+            "top_logprobs": [f(v) for v in e["top_logprobs"]]}
+
+
 def packet_meta(p: KVPacket) -> Dict[str, Any]:
     """The packet without its KV payload (the IPC path writes the payload into the landing zone)."""
     return {"request_id": p.request_id, "prompt_ids": p.prompt_ids, "first_token": p.first_token,
-            "shape": list(p.kv.shape), "block_size": p.block_size, "sampling": p.sampling, "ttft_ms": p.ttft_ms}
+            "shape": list(p.kv.shape), "block_size": p.block_size, "sampling": p.sampling, "ttft_ms": p.ttft_ms,
+            "first_logprobs": _wire_logprobs(p.first_logprobs)}
 
 
 def packet_to_wire(p: KVPacket) -> Dict[str, Any]:
@@ -470,14 +488,14 @@ def packet_to_wire(p: KVPacket) -> Dict[str, Any]:
     raw = kv.view(torch.int16).numpy().tobytes()
     return {"request_id": p.request_id, "prompt_ids": p.prompt_ids, "first_token": p.first_token,
             "shape": list(kv.shape), "block_size": p.block_size, "sampling": p.sampling, "kv": raw,
-            "ttft_ms": p.ttft_ms}
+            "ttft_ms": p.ttft_ms, "first_logprobs": _wire_logprobs(p.first_logprobs)}
 
 
 def packet_from_wire(d: Dict[str, Any], device="cpu") -> KVPacket:
     arr = np.frombuffer(d["kv"], dtype=np.int16).reshape(d["shape"])
     kv = torch.from_numpy(arr.copy()).view(torch.bfloat16).to(device)
     return KVPacket(d["request_id"], list(d["prompt_ids"]), int(d["first_token"]), kv, int(d["block_size"]),
-                    dict(d.get("sampling") or {}), d.get("ttft_ms"))
+                    dict(d.get("sampling") or {}), d.get("ttft_ms"), first_logprobs=d.get("first_logprobs"))
 
 
 class RCCLChannel:

@@ -60,6 +60,9 @@ def load_tokenizer(path: Optional[str] = None, vocab_size: int = 128256):
     return ByteTokenizer(vocab_size)
 
 
+MAX_LOGPROBS = 20  # the OpenAI chat API's cap on top_logprobs
+
+
 @dataclass
 class SamplingParams:
     max_tokens: int = 16
@@ -69,6 +72,10 @@ class SamplingParams:
     seed: Optional[int] = None
     ignore_eos: bool = False
     stop_token_ids: List[int] = field(default_factory=list)
+    # log-probabilities of the model's raw distribution (before temperature / top-k / top-p): None = off,
+    # 0 = the chosen token's logprob and rank only, 1..20 = also that many most likely tokens
+    logprobs: Optional[int] = None
+    prompt_logprobs: Optional[int] = None  # the same, for the prompt tokens
 
     def __post_init__(self):
         if self.max_tokens < 1:
@@ -79,6 +86,12 @@ class SamplingParams:
             raise ValueError("top_p must be in (0, 1]")
         if self.top_k < 0:
             raise ValueError("top_k must be >= 0")
+        for name in ("logprobs", "prompt_logprobs"):
+            v = getattr(self, name)
+            if v is None:
+                continue
+            if isinstance(v, bool) or not isinstance(v, int) or not (0 <= v <= MAX_LOGPROBS):
+                raise ValueError(f"{name} must be None or an integer in [0, {MAX_LOGPROBS}]")
 
     @property
     def greedy(self) -> bool:
@@ -93,7 +106,8 @@ class GenerationInputs:
     return_text: bool = True
 
 
-_SAMPLING_KEYS = ("max_tokens", "temperature", "top_k", "top_p", "seed", "ignore_eos", "stop_token_ids")
+_SAMPLING_KEYS = ("max_tokens", "temperature", "top_k", "top_p", "seed", "ignore_eos", "stop_token_ids",
+                  "logprobs", "prompt_logprobs")
 
 
 def normalize_request(inputs: Any, tokenizer=None, max_model_len: Optional[int] = None) -> GenerationInputs:
