@@ -35,7 +35,7 @@ def main():
             if k % (256 * sk):
                 continue
             sl = torch.empty(sk, m, n, device=dev)
-            res[f"mode2_sk{sk}_us"] = round(timeit(lambda w, sl=sl, sk=sk: ops.gemm_decode(x, w, 2 | 32, 64, sk, out=sl, kc=256), ws), 2)
+            res[f"mode2_sk{sk}_us"] = round(timeit(lambda w, sl=sl, sk=sk: ops.gemm_decode(x, w, ops.MODE_SLAB | ops.TILED, 64, sk, out=sl, kc=256), ws), 2)
             res[f"mode3_sk{sk}_us"] = round(timeit(lambda w, sk=sk: ops.linear_slab_residual(x, w, resid, ssp, cnt, 64, sk, tiled=True, kc=256), ws), 2)
         print(json.dumps(res), flush=True)
         del ws, slab

@@ -41,7 +41,7 @@ def main():
                 cnt = torch.zeros(n // (wr // 2), dtype=torch.int32, device=dev)
 
                 def run():
-                    kern.gemm_decode(y, x, wt, mode | 32, wr, kc, sk, True, e, slab if mode == 6 else e,
+                    kern.gemm_decode(y, x, wt, mode | ops.TILED, wr, kc, sk, True, e, slab if mode == 6 else e,
                                      cnt if mode == 6 else e, ssp, 1e-5)
                 try:
                     run()

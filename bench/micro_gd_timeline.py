@@ -33,11 +33,11 @@ def main():
         ws = [torch.randn(rows, k, device=dev, dtype=torch.bfloat16) / 64 for _ in range(copies)]
         ref = ops.gemm_decode(x, ws[0], mode=mode, wr=wr, sk=sk)
         if tiled:  # pre-packed tile-order weights (ops.gd_pack_weights): same math, linear DMA pieces
-            ws = [ops.gd_pack_weights(w_, wr, silu=mode == 1) for w_ in ws]
-            mode |= 32
+            ws = [ops.gd_pack_weights(w_, wr, silu=mode == ops.MODE_SILU) for w_ in ws]
+            mode |= ops.TILED
             got = ops.gemm_decode(x, ws[0], mode=mode, wr=wr, sk=sk)
             assert torch.equal(got, ref), (name, (got.float() - ref.float()).abs().max())
-        cols = wr // 2 if (mode & 31) == 1 else wr
+        cols = wr // 2 if (mode & ops.MODE_MASK) == ops.MODE_SILU else wr
         nwg = (n // cols) * sk
         ts = torch.zeros(copies, 3 * nwg, dtype=torch.int64, device=dev)
         outs = []

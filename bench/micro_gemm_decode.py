@@ -13,6 +13,7 @@ import torch
 
 sys.path.insert(0, __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__))))
 from src import ops  # noqa: E402
+from src.ops.decode_tiles import DECODE_TILE_CFG, MODE_BF16, MODE_SILU, MODE_SLAB  # noqa: E402
 
 SHAPES = {  # name: (N_out, K, silu)
     "qkv_8b": (6144, 4096, False),
@@ -79,13 +80,13 @@ def main():
             kc = 128 if wr >= 96 else 256
             if silu:
                 if n % (wr // 2) == 0:
-                    res.append((f"gd_silu_wr{wr}", timeit(lambda w: ops.gemm_decode(x, w, 1, wr, 1), ws)))
+                    res.append((f"gd_silu_wr{wr}", timeit(lambda w: ops.gemm_decode(x, w, MODE_SILU, wr, 1), ws)))
                 continue
             if n % wr == 0:
-                res.append((f"gd_bf16_wr{wr}", timeit(lambda w: ops.gemm_decode(x, w, 0, wr, 1), ws)))
+                res.append((f"gd_bf16_wr{wr}", timeit(lambda w: ops.gemm_decode(x, w, MODE_BF16, wr, 1), ws)))
             for sk in (2, 4, 8):
                 if k % (kc * sk) == 0 and n % wr == 0 and (n // wr) * sk <= 1024:
-                    res.append((f"gd_slab_wr{wr}_sk{sk}", timeit(lambda w: ops.gemm_decode(x, w, 2, wr, sk), ws)))
+                    res.append((f"gd_slab_wr{wr}_sk{sk}", timeit(lambda w: ops.gemm_decode(x, w, MODE_SLAB, wr, sk), ws)))
         for v, us in res:
             print(json.dumps({"shape": name, "M": m, "N": n, "K": k, "variant": v, "us": round(us, 2),
                               "GBps": round(wbytes / us / 1e3, 1)}), flush=True)
@@ -99,15 +100,15 @@ def main_nt(m):
     for name, (n, k, silu) in SHAPES.items():
         if name.startswith("lm_head"):
             continue
-        mode = 1 if silu else (0 if (n, k, 0) in ops.DECODE_GEMM_CFG else 2)
-        wr, sk = ops._cfg_for(n, k, mode)
+        mode = MODE_SILU if silu else (MODE_BF16 if (n, k, MODE_BF16, 32) in DECODE_TILE_CFG else MODE_SLAB)
+        wr, kc, sk = ops.decode_tile(n, k, mode, 32)
         wrows = 2 * n if silu else n
         x = torch.randn(m, k, device=dev, dtype=torch.bfloat16)
         wbytes = wrows * k * 2
         copies = max(2, int(1.5 * 2**30 // wbytes) + 1)
         ws = [torch.randn(wrows, k, device=dev, dtype=torch.bfloat16) / 64 for _ in range(copies)]
         for nt in (False, True):
-            us = timeit(lambda w: ops.gemm_decode(x, w, mode, wr, sk, nt=nt), ws)
+            us = timeit(lambda w: ops.gemm_decode(x, w, mode, wr, sk, nt=nt, kc=kc), ws)
             print(json.dumps({"shape": name, "M": m, "mode": mode, "wr": wr, "sk": sk, "nt": nt, "us": round(us, 2),
                               "GBps": round(wbytes / us / 1e3, 1)}), flush=True)
         del ws
@@ -145,16 +146,16 @@ def main_warm(m):
     for name, (n, k, silu) in SHAPES.items():
         if name.startswith("lm_head") or "70b" in name:
             continue
-        mode = 1 if silu else 2
-        wr, sk = ops._cfg_for(n, k, mode)
+        mode = MODE_SILU if silu else MODE_SLAB
+        wr, kc, sk = ops.decode_tile(n, k, mode, 32)
         wrows = 2 * n if silu else n
         x = torch.randn(m, k, device=dev, dtype=torch.bfloat16)
         wbytes = wrows * k * 2
         copies = max(2, int(1.5 * 2**30 // wbytes) + 1)
         ws = [torch.randn(wrows, k, device=dev, dtype=torch.bfloat16) / 64 for _ in range(copies)]
         for nt in (True, False):
-            cold = timeit(lambda w: ops.gemm_decode(x, w, mode, wr, sk, nt=nt), ws)
-            warm = timeit(lambda w: ops.gemm_decode(x, w, mode, wr, sk, nt=nt), ws[:1], iters=max(8, copies))
+            cold = timeit(lambda w: ops.gemm_decode(x, w, mode, wr, sk, nt=nt, kc=kc), ws)
+            warm = timeit(lambda w: ops.gemm_decode(x, w, mode, wr, sk, nt=nt, kc=kc), ws[:1], iters=max(8, copies))
             print(json.dumps({"shape": name, "MB": round(wbytes / 2**20, 1), "nt": nt, "cold_us": round(cold, 2),
                               "warm_us": round(warm, 2)}), flush=True)
         del ws
@@ -162,14 +163,15 @@ def main_warm(m):
 
 
 def main_deep(m):
-    """Deep-ring variants (wr code rows+1: 128-wide K slots, 5-7 slots in flight) vs the tuned configs."""
+    """Deep-ring variants (128-wide K slots, 5-7 slots in flight) vs the tuned configs: (mode, wr, kc, sk)."""
     dev = torch.device("cuda:0")
     cand = {
-        "qkv_8b": [(2, 48, 2), (2, 49, 2), (2, 49, 4), (2, 65, 2), (2, 65, 4), (2, 33, 2)],
-        "o_8b": [(2, 64, 4), (2, 65, 4), (2, 65, 2), (2, 33, 2), (2, 49, 4)],
-        "gate_up_8b": [(1, 112, 1), (1, 65, 1), (1, 33, 1), (1, 64, 1)],
-        "down_8b": [(2, 64, 4), (2, 65, 4), (2, 65, 2), (2, 33, 2), (2, 49, 4)],
-        "lm_head_8b": [(0, 64, 1), (0, 65, 1)],
+        "qkv_8b": [(2, 48, 256, 2), (2, 48, 128, 2), (2, 48, 128, 4), (2, 64, 128, 2), (2, 64, 128, 4),
+                   (2, 32, 128, 2)],
+        "o_8b": [(2, 64, 256, 4), (2, 64, 128, 4), (2, 64, 128, 2), (2, 32, 128, 2), (2, 48, 128, 4)],
+        "gate_up_8b": [(1, 112, 128, 1), (1, 64, 128, 1), (1, 32, 128, 1), (1, 64, 256, 1)],
+        "down_8b": [(2, 64, 256, 4), (2, 64, 128, 4), (2, 64, 128, 2), (2, 32, 128, 2), (2, 48, 128, 4)],
+        "lm_head_8b": [(0, 64, 256, 1), (0, 64, 128, 1)],
     }
     for name, cfgs in cand.items():
         n, k, silu = SHAPES[name]
@@ -178,9 +180,9 @@ def main_deep(m):
         wbytes = wrows * k * 2
         copies = max(2, int(1.5 * 2**30 // wbytes) + 1)
         ws = [torch.randn(wrows, k, device=dev, dtype=torch.bfloat16) / 64 for _ in range(copies)]
-        for mode, wr, sk in cfgs:
-            us = timeit(lambda w: ops.gemm_decode(x, w, mode, wr, sk), ws)
-            print(json.dumps({"shape": name, "mode": mode, "wr": wr, "sk": sk, "us": round(us, 2),
+        for mode, wr, kc, sk in cfgs:
+            us = timeit(lambda w: ops.gemm_decode(x, w, mode, wr, sk, kc=kc), ws)
+            print(json.dumps({"shape": name, "mode": mode, "wr": wr, "kc": kc, "sk": sk, "us": round(us, 2),
                               "GBps": round(wbytes / us / 1e3, 1)}), flush=True)
         del ws
         torch.cuda.empty_cache()
@@ -194,14 +196,14 @@ def main_moe(m):
     xr16 = __import__("os").environ.get("DIE_GD_XR16", "1")
     for name in ("qkv_8b", "o_8b", "gate_up_8b", "down_8b"):
         n, k, silu = SHAPES[name]
-        mode = 1 if silu else (0 if (n, k, 0) in ops.DECODE_GEMM_CFG else 2)
-        wr, sk = ops._cfg_for(n, k, mode)
+        mode = MODE_SILU if silu else (MODE_BF16 if (n, k, MODE_BF16, 32) in DECODE_TILE_CFG else MODE_SLAB)
+        wr, kc, sk = ops.decode_tile(n, k, mode, 32)
         wrows = 2 * n if silu else n
         x = torch.randn(m, k, device=dev, dtype=torch.bfloat16)
         wbytes = wrows * k * 2
         copies = max(2, int(1.5 * 2**30 // wbytes) + 1)
         ws = [torch.randn(wrows, k, device=dev, dtype=torch.bfloat16) / 64 for _ in range(copies)]
-        us = timeit(lambda w: ops.gemm_decode(x, w, mode, wr, sk), ws)
+        us = timeit(lambda w: ops.gemm_decode(x, w, mode, wr, sk, kc=kc), ws)
         print(json.dumps({"shape": name, "M": m, "xr16": xr16, "us": round(us, 2),
                           "GBps": round(wbytes / us / 1e3, 1)}), flush=True)
         del ws
@@ -215,11 +217,10 @@ def main_moe(m):
     w2s = [torch.randn(e, h, inter, device=dev, dtype=torch.bfloat16) / 64 for _ in range(2)]
     kern = ops._kern()
     none = torch.empty(0, dtype=torch.int32, device=dev)
-    wr1 = ops._cfg_for(inter, h, 1)[0]
-    wr2 = ops._moe_down_wr(h, inter)
-    for nm, ws, fn in (("moe_w13", w13s, lambda w: kern.gemm_decode_grouped(a, xs, w, offsets, 1, *ops.gd_tile(wr1),
+    t1, t2 = ops.moe_decode_tiles(h, inter, m)
+    for nm, ws, fn in (("moe_w13", w13s, lambda w: kern.gemm_decode_grouped(a, xs, w, offsets, MODE_SILU, *t1,
                                                                             none, 1, m, 1)),
-                       ("moe_w2", w2s, lambda w: kern.gemm_decode_grouped(ys, a, w, offsets, 0, *ops.gd_tile(wr2),
+                       ("moe_w2", w2s, lambda w: kern.gemm_decode_grouped(ys, a, w, offsets, MODE_BF16, *t2,
                                                                           none, 1, m, 1))):
         us = timeit(fn, ws)
         wbytes = ws[0].numel() * 2
@@ -234,7 +235,7 @@ def main_chain(m):
     dev = torch.device("cuda:0")
     kern = ops._kern()
     h, inter = 4096, 14336
-    wr = ops._cfg_for(inter, h, 1)[0]
+    wr, kc, _ = ops.decode_tile(inter, h, MODE_SILU, 32)
     x = torch.randn(m, h, device=dev, dtype=torch.bfloat16)
     none = torch.empty(0, dtype=torch.int32, device=dev)
     for n in (1, 2, 4, 8):
@@ -242,8 +243,8 @@ def main_chain(m):
         xs = x.repeat(n, 1).contiguous()
         a = torch.empty(n * m, inter, device=dev, dtype=torch.bfloat16)
         offsets = torch.arange(0, (n + 1) * m, m, dtype=torch.int32, device=dev)
-        one = timeit(lambda w: kern.gemm_decode_grouped(a, xs, w, offsets, 1, *ops.gd_tile(wr), none, 1, m, 1), ws)
-        sep = timeit(lambda w: [ops.gemm_decode(x, w[i], 1, wr, 1) for i in range(n)], ws)
+        one = timeit(lambda w: kern.gemm_decode_grouped(a, xs, w, offsets, MODE_SILU, wr, kc, none, 1, m, 1), ws)
+        sep = timeit(lambda w: [ops.gemm_decode(x, w[i], MODE_SILU, wr, 1, kc=kc) for i in range(n)], ws)
         wbytes = n * 2 * inter * h * 2
         print(json.dumps({"bench": "chain", "M": m, "n_weight_sets": n, "one_launch_us": round(one, 2),
                           "separate_launches_us": round(sep, 2), "one_launch_TBps": round(wbytes / one / 1e6, 2),

@@ -68,7 +68,7 @@ def main():
                     wts = (wts * ((copies + 1) // 2))[:copies]
                     try:
                         if mode == 2:
-                            fn = lambda w: ops.gemm_decode(x, w, 2 | 32, wr, sk, kc=kc)  # noqa: E731
+                            fn = lambda w: ops.gemm_decode(x, w, ops.MODE_SLAB | ops.TILED, wr, sk, kc=kc)  # noqa: E731
                         elif mode == 3:
                             ssp = torch.zeros(n // wr, ops.SSP_LD, device=dev)
                             cnt = torch.zeros(n // wr, dtype=torch.int32, device=dev)

@@ -2,8 +2,8 @@
 written before every call; median of 10 event-timed calls). For each projection of a TP rank's decode layer —
 qkv (mode 2: fp32 split-K slabs), o / down (mode 3: split-K + last-arriver residual update, the local form of the
 fused row-parallel exchange) and gate/up (mode 4 full-K / mode 6 split-K, norm row scale + SiLU) — every valid
-(wr, kc, sk) tile is timed. One JSON line per (shape, tile); the fastest per shape goes into ops.DECODE_TILE_CFG /
-DECODE_SILU_SPLITK_CFG.
+(wr, kc, sk) tile is timed. One JSON line per (shape, tile); the fastest per shape goes into DECODE_TILE_CFG
+(src/ops/decode_tiles.py; the split-K gate/up under its mode-6 key).
 
 python bench/micro_tp_tiles.py [--shapes 70b_tp8,8b_tp2]
 """
@@ -86,18 +86,18 @@ def main():
                         except AssertionError:
                             continue
                         cnt = torch.zeros(max(1, ntiles), dtype=torch.int32, device=dev)
-                        tb = 32 if tiled else 0
+                        tb = ops.TILED if tiled else 0
                         if mode == 0:
                             y = torch.empty(m, n, dtype=torch.bfloat16, device=dev)
-                            args = (y, x, wt, tb, wr, kc, 1, True, e, e, e, e, 0.0)
+                            args = (y, x, wt, ops.MODE_BF16 | tb, wr, kc, 1, True, e, e, e, e, 0.0)
                         elif mode == 2:
                             y = torch.empty(sk, m, n, dtype=torch.float32, device=dev)
-                            args = (y, x, wt, 2 | tb, wr, kc, sk, True, e, e, e, e, 0.0)
+                            args = (y, x, wt, ops.MODE_SLAB | tb, wr, kc, sk, True, e, e, e, e, 0.0)
                         elif mode == 3:
                             y = torch.empty(sk, m, n, dtype=torch.float32, device=dev)
                             resid = torch.zeros(m, n, dtype=torch.bfloat16, device=dev)
                             sspo = torch.zeros(ntiles, 128, device=dev)
-                            args = (y, x, wt, 3 | tb, wr, kc, sk, True, resid, sspo, cnt, e, 0.0)
+                            args = (y, x, wt, ops.MODE_RESID | tb, wr, kc, sk, True, resid, sspo, cnt, e, 0.0)
                         else:
                             y = torch.empty(m, n, dtype=torch.bfloat16, device=dev)
                             slab = torch.empty(sk * m * 2 * n, dtype=torch.float32, device=dev) if mode == 6 else e

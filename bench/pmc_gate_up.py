@@ -11,6 +11,6 @@ dev = torch.device("cuda:0")
 x = torch.randn(32, 4096, device=dev, dtype=torch.bfloat16)
 ws = [torch.randn(28672, 4096, device=dev, dtype=torch.bfloat16) / 64 for _ in range(8)]
 for i in range(40):
-    ops.gemm_decode(x, ws[i % 8], 1, 112, 1)
+    ops.gemm_decode(x, ws[i % 8], ops.MODE_SILU, 112, 1)
 torch.cuda.synchronize()
 print("done")

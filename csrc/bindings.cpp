@@ -7,6 +7,7 @@
 #include <torch/extension.h>
 #include <c10/hip/HIPStream.h>
 
+#include "kernels/gd_tiles.h"
 #include "kernels/launchers.h"
 
 using torch::Tensor;
@@ -571,14 +572,13 @@ void moe_combine_residual(Tensor ssp, Tensor resid, Tensor ys, Tensor pos, Tenso
 // Diagnostics: when set (non-empty int64 tensor [>= 3 * workgroups]), every decode-GEMM launch writes
 // per-workgroup [start, end, xcc] s_memrealtime stamps (100 MHz) there (bench/micro_gd_timeline.py).
 static long long* g_gd_ts = nullptr;
-// decode-GEMM tiles that are instantiated (gemm_decode.hip launch_gemm_decode)
+// decode-GEMM tiles that are instantiated (gd_tiles.h; gemm_decode.hip launch_gemm_decode dispatches on the same list)
 static bool gd_tile_ok(int64_t wr, int64_t kc) {
-  switch (kc) {
-    case 256: return wr == 32 || wr == 48 || wr == 64;
-    case 128: return wr == 32 || wr == 48 || wr == 64 || wr == 96 || wr == 112 || wr == 128;
-    case 64: case 32: return wr == 64 || wr == 128;
-    default: return false;
-  }
+#define GD_TILE(WR, KC) \
+  if (wr == WR && kc == KC) return true;
+  GD_TILES(GD_TILE)
+#undef GD_TILE
+  return false;
 }
 void gd_set_timestamps(Tensor t) {
   g_gd_ts = t.numel() ? reinterpret_cast<long long*>(t.data_ptr<int64_t>()) : nullptr;

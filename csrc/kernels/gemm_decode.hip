@@ -32,6 +32,7 @@
 //    next RMSNorm's row statistics.
 #include "car_common.h"
 #include "common.h"
+#include "gd_tiles.h"
 #include "launchers.h"
 
 #include <algorithm>
@@ -42,7 +43,6 @@ namespace gd {
 
 constexpr int NTH = 256;              // threads per workgroup
 constexpr int SSP_LD = 128;           // row stride of the norm-statistics arrays ([tiles][SSP_LD])
-constexpr int RING_BYTES = 147456;    // LDS for the ring (144 KiB; the epilogue scratch reuses it)
 
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void global_cvoid;
@@ -66,16 +66,6 @@ __device__ __forceinline__ int swz(int r) {
   if constexpr (ROWB >= 256) return r & 15;
   else if constexpr (ROWB == 128) return (r >> 1) & 7;
   else return (r ^ (r >> 1)) & 3;  // 64-byte rows
-}
-
-// LDS ring depth for a (WR, XR, KC) tile: the deepest that fits RING_BYTES and the 6-bit vmcnt
-constexpr int ring_slots(int wr, int xr, int kc) {
-  const int slot = (wr + xr) * kc * 2;
-  const int per_wave = (wr + xr) / (64 / (kc / 8)) / 4;
-  int s = RING_BYTES / slot;
-  if (s > 8) s = 8;
-  while (s > 2 && (s - 1) * per_wave > 63) --s;
-  return s;
 }
 
 }  // namespace gd
@@ -648,33 +638,7 @@ __global__ void __launch_bounds__(NTH) gemm_decode_kernel(void* __restrict__ Yv,
   }
 }
 
-// LDS bytes of one launch: the ring, and after the loop the partials red[NRED][RR][WR] fp32 + scratch
-constexpr size_t gd_lds(int wr, int xr, int kc, int s) {
-  const size_t ring = (size_t)s * (wr + xr) * kc * 2;
-  const size_t red = (size_t)(xr < 64 && kc >= 128 ? 4 : 1) * (xr < 32 ? 32 : xr) * wr * 4 + 2048;
-  return ring > red ? ring : red;
-}
-
-// a (WR, XR, KC) tile exists: a ring of >= 2 slots fits, the DMA pieces split evenly over the 4 waves and
-// the wave split has work for every wave
-constexpr bool gd_valid(int wr, int xr, int kc) {
-  const int rpp = 64 / (kc / 8);
-  const int s = ring_slots(wr, xr, kc);
-  return s >= 2 && (wr + xr) % (4 * rpp) == 0 && xr % rpp == 0 && wr % rpp == 0 &&
-         !(xr < 64 && kc < 128 && wr % 64 != 0) && gd_lds(wr, xr, kc, s) <= 160 * 1024;
-}
-
-// ring depth of the half-LDS form (mode 3, fz.half_ring): at most HALF_RING_BYTES so that two workgroups fit on a
-// CU (160 KiB of LDS). The TP row-parallel projections use it where the grid is about one workgroup per CU: with
-// two resident per CU the whole grid of every GPU is co-resident with room to spare, which the exchange's
-// waiting last arrivers need (CustomAllReduce.fused_ok); 0 = no such form
-constexpr int HALF_RING_BYTES = 76 * 1024;
-constexpr int half_ring_slots(int wr, int xr, int kc) {
-  const int s = ring_slots(wr, xr, kc);
-  const int h = HALF_RING_BYTES / ((wr + xr) * kc * 2);
-  const int r = h < s ? h : s;
-  return r >= 2 ? r : 0;
-}
+// tile geometry (ring_slots, gd_lds, gd_valid, half_ring_slots): gd_tiles.h
 
 // launch (or, with fz.occupancy set, only report the resident workgroups per CU of) one instantiation
 template <int WR, int EPI, int S, int KC, int XR, int SKC>
@@ -769,7 +733,7 @@ static hipError_t launch_modes(void* Y, int64_t ldy, const bf16_t* X, int64_t ld
 // mode 6: mode 4 split over sk K slices: fp32 partials in fz.slab6 [sk][M][2 N], the tile's last arriver
 //         finishes (fz.counters [N / (wr / 2)] tickets, zero, re-armed).
 // fz.amax (mode 0, 16-byte aligned Y rows): per-tile greedy candidates [M][N / wr][2].
-// (wr, kc): weight rows per workgroup and K elements per ring slot (gemm_decode_tile_ok), so that
+// (wr, kc): weight rows per workgroup and K elements per ring slot (one of gd_tiles.h's GD_TILES), so that
 // (N / columns) * sk can be made a multiple of the CU count for the model's shapes (e.g. 8B gate/up:
 // 14336 / 56 = 256 workgroups at wr = 112). Small K slots (64 / 32) are for M > 32: they keep the
 // activation image from crowding the weights out of the ring.
@@ -802,19 +766,7 @@ hipError_t launch_gemm_decode(void* Y, int64_t ldy, const bf16_t* X, int64_t ldx
   }
 #define GD_TILE(WR, KC) \
   if (wr == WR && kc == KC) return launch_modes<WR, KC>(Y, ldy, X, ldx, W, M, N, K, mode, sk, nt, fz, s);
-  GD_TILE(32, 256)
-  GD_TILE(48, 256)
-  GD_TILE(64, 256)
-  GD_TILE(32, 128)
-  GD_TILE(48, 128)
-  GD_TILE(64, 128)
-  GD_TILE(96, 128)
-  GD_TILE(112, 128)
-  GD_TILE(128, 128)
-  GD_TILE(64, 64)
-  GD_TILE(128, 64)
-  GD_TILE(64, 32)
-  GD_TILE(128, 32)
+  GD_TILES(GD_TILE)
 #undef GD_TILE
   return hipErrorInvalidValue;
 }

@@ -29,6 +29,7 @@ import torch.nn.functional as F
 
 from src import ops
 from src.models.presets import ArchConfig
+from src.ops.decode_tiles import LM_HEAD_TILES
 from src.ops.reference import rope_cos_sin
 from src.parallel.tp import TPContext
 
@@ -226,10 +227,6 @@ class CausalLM:
                 lw.ln2.fill_(1)
         self.norms_folded = True
 
-    # LM head tiles tried in order (bench/micro_tp_tiles.py --shapes lm_head, cold, 32 rows: tile-order
-    # (128, 128) 171.8 us vs the row-major (64, 256) 187.0 us for Llama-3's 128,256 x 4,096)
-    LM_HEAD_TILES = ((128, 128), (64, 256), (64, 128))
-
     def pack_lm_head(self) -> bool:
         """Re-lay the LM head IN PLACE in the decode GEMM's tile order (one copy: its only consumer is the
         decode GEMM — logits are computed for the sampled rows, in <= 128-row chunks). Returns whether packed."""
@@ -240,7 +237,7 @@ class CausalLM:
         if not (self.device.type == "cuda" and ops.native_available()):
             return False
         rows, k = self.lm_head.shape
-        for wr, kc in self.LM_HEAD_TILES:
+        for wr, kc in LM_HEAD_TILES:
             if rows % wr == 0 and k % kc == 0 and ops.gd_tile_valid(wr, kc, 32):
                 self.lm_head.copy_(ops.gd_pack_weights(self.lm_head, wr, kc=kc))
                 self.lm_head_tile = (wr, kc)
@@ -576,10 +573,7 @@ class CausalLM:
         return ops.fused_add_rms_norm_slab(slab, residual, self.norm, eps)
 
     # ----------------------------------------- fused decode path (norms folded, M <= 128)
-    @staticmethod
-    def decode_bucket(m: int) -> int:
-        """Row bucket of a decode step: the activation image of its GEMMs (32, 64 or 128 rows)."""
-        return 32 if m <= 32 else (64 if m <= 64 else 128)
+    decode_bucket = staticmethod(ops.decode_bucket)
 
     def decode_plan(self, m: int = 32) -> dict:
         """Decode-GEMM tiles of the fused path for steps of ``m`` rows: (wr, kc, sk) of the qkv slab
@@ -591,12 +585,13 @@ class CausalLM:
         # area (V3_MERGE_BYTES): at most 50 rows
         g = max(1, self.hq // self.hkv)
         rm = not getattr(self, "tiled_decode_weights", True)  # decode streams the row-major weights by choice (KV capacity)
-        qkv = ops.decode_tile(self.layers[0].qkv.shape[0], h, 2, b, max_sk=max(1, 50 // (g + 2)), row_major=rm)
+        qkv = ops.decode_tile(self.layers[0].qkv.shape[0], h, ops.MODE_SLAB, b, max_sk=max(1, 50 // (g + 2)),
+                              row_major=rm)
         # residual-updating split-K (mode 3); under TP the same tiles carry the one-shot exchange of each column
         # tile in their last arrivers' epilogue (one launch per row-parallel projection) where the group allows
         # it (TPContext.fused_row_parallel), else bf16 partial sums (mode 0) for a separate all-reduce launch
-        o = ops.decode_tile(h, self.hq * d, 3, b, row_major=rm)
-        down = ops.decode_tile(h, self.inter, 3, b, row_major=rm) if not self.arch.is_moe else None
+        o = ops.decode_tile(h, self.hq * d, ops.MODE_RESID, b, row_major=rm)
+        down = ops.decode_tile(h, self.inter, ops.MODE_RESID, b, row_major=rm) if not self.arch.is_moe else None
         tp_fused = o_half = down_half = False
         if self.tp.enabled:
             fo = self._tp_fused_tile(h, self.hq * d, b, o) if not self.arch.is_moe else None
@@ -605,8 +600,8 @@ class CausalLM:
             if tp_fused:
                 (o, o_half), (down, down_half) = fo, fd
             else:
-                o = ops.decode_tile(h, self.hq * d, 0, b)
-                down = ops.decode_tile(h, self.inter, 0, b) if not self.arch.is_moe else None
+                o = ops.decode_tile(h, self.hq * d, ops.MODE_BF16, b)
+                down = ops.decode_tile(h, self.inter, ops.MODE_BF16, b) if not self.arch.is_moe else None
         gu = ops.decode_tile_silu(self.inter, h, b, row_major=rm) if not self.arch.is_moe else None
         return {"qkv": qkv, "o": o, "down": down, "gate_up": gu[:2] if gu else None,
                 "gate_up_sk": gu[2] if gu else 1, "tp_fused": tp_fused, "o_half": o_half, "down_half": down_half}
@@ -646,7 +641,7 @@ class CausalLM:
 
             # both forms on tile-order weights, as served (the separate form's partial GEMM on its own mode-0 tile)
             wt = ops.gd_pack_weights(w, wr, kc=kc)
-            wr0, kc0 = ops.decode_tile(h, k, 0, 32)[:2]
+            wr0, kc0 = ops.decode_tile(h, k, ops.MODE_BF16, 32)[:2]
             wt0 = ops.gd_pack_weights(w, wr0, kc=kc0)
 
             def fused():
@@ -692,7 +687,7 @@ class CausalLM:
             if n % wr or k % (kc * sk) or n // wr > lim or not ops.gd_tile_valid(wr, kc, bucket):
                 continue
             for half in ((False, True) if bucket <= 32 else (False,)):
-                occ = ops.gd_occupancy(3, wr, kc, sk, bucket, half)
+                occ = ops.gd_occupancy(ops.MODE_RESID, wr, kc, sk, bucket, half)
                 if half and occ <= 0:
                     continue
                 if self.tp.fused_row_parallel(n // wr, n // wr * sk, occ):

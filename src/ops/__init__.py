@@ -8,12 +8,16 @@ which lets the engine's control flow run in CPU-only tests.
 
 from __future__ import annotations
 
-import os
 from typing import Optional
 
 import torch
 
 from . import reference as ref
+# the decode GEMM's mode word, tiles, measured table and lookup: one module, re-exported for the callers of ops
+from .decode_tiles import (DECODE_GEMM_MAX_M, DECODE_TILE_CFG, HALF_RING, MODE_BF16, MODE_MASK, MODE_RESID, MODE_SILU,
+                           MODE_SILU_NORM, MODE_SILU_NORM_SK, MODE_SLAB, SSP_LD, SSP_MAX_TILES, SSP_MAX_TILES_WIDE,
+                           TILED, _tile_overrides, decode_bucket, decode_tile, decode_tile_silu, gd_tile,
+                           gd_tile_valid, moe_decode_tiles)
 
 _C = None
 _C_ERR: Optional[BaseException] = None
@@ -301,13 +305,9 @@ def scatter_blocks(pool: torch.Tensor, ids: torch.Tensor, buf: torch.Tensor) -> 
     _kern().move_blocks(pool, buf, ids, False)
 
 
-DECODE_GEMM_MAX_M = 128   # weight-streaming decode GEMM / fused decode path (gemm_decode.hip)
 # expert-streaming grouped decode GEMM up to this many tokens (<= 128 rows per expert: 16/32/64/128-row
 # images; above it: <= 128-row segments). 32 (round 1's limit) measured 14.9 vs 18.1 req/s at batch 64
 MOE_DECODE_MAX_T = 128
-SSP_LD = 128              # row stride of the norm-statistics arrays [tiles, SSP_LD]
-SSP_MAX_TILES = 256       # statistics tiles a consumer takes at <= 32 decode rows (launchers.h)
-SSP_MAX_TILES_WIDE = 128  # ... above 32 rows
 
 
 def _decode_gemm_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
@@ -317,25 +317,19 @@ def _decode_gemm_ok(x: torch.Tensor, w: torch.Tensor) -> bool:
 
 DECODE_GEMM_NT = True
 
-def gd_tile(wr: int, kc: Optional[int] = None):
-    """(weight rows, K slot) of a decode-GEMM tile. ``kc`` defaults from the legacy wr codes: 256 for
-    32 / 48 / 64 rows, 128 for >= 96 rows, and odd codes 33 / 49 / 65 = the 128-wide deep-ring variants."""
-    if kc is None:
-        kc = 128 if (wr >= 96 or wr & 1) else 256
-    return wr & ~1, kc
-
 
 def gemm_decode(x: torch.Tensor, w: torch.Tensor, mode: int = 0, wr: int = 64, sk: int = 1,
                 out: Optional[torch.Tensor] = None, nt: Optional[bool] = None, kc: Optional[int] = None) -> torch.Tensor:
     """Raw access to the decode GEMM kernel (see csrc/kernels/gemm_decode.hip).
-    mode 0: bf16 x@w^T; mode 1: bf16 silu(gate)*up (w = [gate; up]);
-    mode 2: fp32 split-K slabs [sk, M, N]. ``(wr, kc)``: the workgroup tile (:func:`gd_tile`)."""
+    ``mode``: a decode_tiles.MODE_* epilogue (MODE_BF16: bf16 x@w^T; MODE_SILU: bf16 silu(gate)*up, w = [gate; up];
+    MODE_SLAB: fp32 split-K slabs [sk, M, N]), | TILED for a w packed by gd_pack_weights. ``(wr, kc)``: the
+    workgroup tile (:func:`gd_tile`)."""
     m = x.shape[0]
     wr, kc = gd_tile(wr, kc)
-    base = mode & 31  # | 32: w pre-packed by gd_pack_weights
-    n = w.shape[0] // 2 if base == 1 else w.shape[0]
+    base = mode & MODE_MASK
+    n = w.shape[0] // 2 if base == MODE_SILU else w.shape[0]
     if out is None:
-        if base == 2:
+        if base == MODE_SLAB:
             out = torch.empty(sk, m, n, dtype=torch.float32, device=x.device)
         else:
             out = torch.empty(m, n, dtype=x.dtype, device=x.device)
@@ -359,7 +353,7 @@ def gd_pack_weights(w: torch.Tensor, wr: int, silu: bool = False, kc: Optional[i
     K-chunk c, the tile's (wr x KC) block is contiguous and already in the kernel's LDS-image order
     (rows of the tile, 16-byte chunks XOR-swizzled by row), so every 1-KiB LDS-DMA piece is one
     linear read. silu: w = [gate; up] and a tile holds wr/2 gate rows then the matching wr/2 up
-    rows. The result has w's shape (pass mode | 32 to gemm_decode)."""
+    rows. The result has w's shape (pass mode | TILED to gemm_decode)."""
     rows, k = w.shape
     wrr, kc = gd_tile(wr, kc)
     cpr = kc // 8
@@ -413,8 +407,8 @@ def linear_slab_residual(x: torch.Tensor, w: torch.Tensor, resid: torch.Tensor, 
     wr, kc = gd_tile(wr, kc)
     slab = torch.empty(sk, m, n, dtype=torch.float32, device=x.device)
     e = _empty(x.device)
-    _kern().gemm_decode(slab, x, w, 3 | (32 if tiled else 0) | (64 if half_ring else 0), wr, kc, sk, DECODE_GEMM_NT,
-                        resid, ssp_out, counters, e, 0.0)
+    _kern().gemm_decode(slab, x, w, MODE_RESID | (TILED if tiled else 0) | (HALF_RING if half_ring else 0), wr, kc, sk,
+                        DECODE_GEMM_NT, resid, ssp_out, counters, e, 0.0)
     return slab
 
 
@@ -429,7 +423,7 @@ def gd_occupancy(mode: int, wr: int, kc: int, sk: int, rows: int, half_ring: boo
     key = (mode, wr, kc, sk, rows, half_ring)
     v = _OCC.get(key)
     if v is None:
-        v = max(0, int(_kern().gd_occupancy(mode | (64 if half_ring else 0), wr, kc, sk, rows, DECODE_GEMM_NT)))
+        v = max(0, int(_kern().gd_occupancy(mode | (HALF_RING if half_ring else 0), wr, kc, sk, rows, DECODE_GEMM_NT)))
         _OCC[key] = v
     return v
 
@@ -439,49 +433,24 @@ def linear_silu_mul_rownorm(x: torch.Tensor, w_gate_up: torch.Tensor, ssp_in: to
                             slab: Optional[torch.Tensor] = None,
                             counters: Optional[torch.Tensor] = None) -> torch.Tensor:
     """silu(r * x @ gate^T) * (r * x @ up^T) with r = rsqrt(sum_t ssp_in[t] / K + eps) per row:
-    RMSNorm (weight folded into w_gate_up) + gate/up + SiLU*mul in one weight stream. sk > 1 (mode 6): K
+    RMSNorm (weight folded into w_gate_up) + gate/up + SiLU*mul in one weight stream. sk > 1 (MODE_SILU_NORM_SK): K
     split over sk workgroups per tile with fp32 partials in ``slab`` (>= sk * rows * 2N floats) and the tile's
     last arriver finishing (``counters``: >= N / (wr / 2) int32, zero; re-armed by the kernel)."""
     n = w_gate_up.shape[0] // 2
     if wr is None:
-        wr, kc, _ = decode_tile(n, x.shape[1], 4, _bucket(x.shape[0]))
+        wr, kc, _ = decode_tile(n, x.shape[1], MODE_SILU_NORM, decode_bucket(x.shape[0]))
     wr, kc = gd_tile(wr, kc)
     out = torch.empty(x.shape[0], n, dtype=x.dtype, device=x.device)
     e = _empty(x.device)
     if sk > 1:
         if slab is None or counters is None:
             raise ValueError("split-K gate/up (sk > 1) needs its slab and counters")
-        _kern().gemm_decode(out, x, w_gate_up, 6 | (32 if tiled else 0), wr, kc, sk, DECODE_GEMM_NT, e, slab, counters,
-                            ssp_in, float(eps))
+        _kern().gemm_decode(out, x, w_gate_up, MODE_SILU_NORM_SK | (TILED if tiled else 0), wr, kc, sk,
+                            DECODE_GEMM_NT, e, slab, counters, ssp_in, float(eps))
         return out
-    _kern().gemm_decode(out, x, w_gate_up, 4 | (32 if tiled else 0), wr, kc, 1, DECODE_GEMM_NT, e, e, e, ssp_in,
-                        float(eps))
+    _kern().gemm_decode(out, x, w_gate_up, MODE_SILU_NORM | (TILED if tiled else 0), wr, kc, 1, DECODE_GEMM_NT, e, e, e,
+                        ssp_in, float(eps))
     return out
-
-
-# (N_out, K, row bucket) -> (wr, kc, sk) of the split-K gate/up (mode 6), where the full-K form's grid forces
-# narrow tiles (bench/micro_gd_splitk_silu.py, profiles/micro_gd_splitk_silu_r3.jsonl): Llama-3-70B's TP=8
-# shard 27.1 us vs 30.0 for the best full-K tile (32, 256). Dense 8B shapes lose with split-K (not listed).
-DECODE_SILU_SPLITK_CFG = {
-    (3584, 8192, 32): (64, 128, 2),   # round 4 sweep (micro_tp_tiles_r4): 26.84 us vs 30.36 for (64, 256, 2) cold
-    # 64 / 128 rows (micro_tp_tiles --rows 64 / 128, profiles/micro_tp_tiles_r4_rows64_128.jsonl, cold us)
-    (3584, 8192, 64): (112, 128, 4),  # 34.76 vs 41.28 for the full-K (32, 128)
-    (3584, 8192, 128): (64, 128, 2),  # 46.36 vs 52.12
-}
-
-
-def decode_tile_silu(n: int, k: int, bucket: int = 32, row_major: bool = False):
-    """(wr, kc, sk) of the norm-scaled SiLU gate/up decode GEMM: a split-K tile where one was measured faster,
-    else the full-K tile (sk = 1). ``row_major``: on weights kept row-major (DECODE_TILE_CFG_RM)."""
-    if row_major:
-        c = DECODE_TILE_CFG_RM.get((n, k, 6, bucket)) or DECODE_TILE_CFG_RM.get((n, k, 4, bucket))
-        if c is not None:
-            return c
-    # DIE_TILE_OVERRIDE entries with mode 6 name the split-K SiLU gate/up tile (N_out, K, 6, bucket) (in-graph A/Bs)
-    c = DECODE_TILE_CFG.get((n, k, 6, bucket)) or DECODE_SILU_SPLITK_CFG.get((n, k, bucket))
-    if c is not None:
-        return c
-    return (*decode_tile(n, k, 4, bucket)[:2], 1)
 
 
 def residual_add_sumsq(resid: torch.Tensor, x: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
@@ -520,190 +489,15 @@ def row_sumsq(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tens
     return out
 
 
-# (N, K, mode) -> (wr, sk), measured with bench/micro_gemm_decode.py on MI355X (cold
-# weights, M = 32, nt weight loads; profiles/micro_gemm_decode_m32_r1b.jsonl). Fastest
-# configs put (N/cols)*sk at (a multiple of) ~256 workgroups, one per CU.
-DECODE_GEMM_CFG = {
-    (6144, 4096, 2): (48, 2),      # Llama-3-8B / Mixtral qkv  (11.6 us vs hipBLASLt 15.3)
-    (4096, 4096, 2): (64, 4),      # 8B o_proj                  (9.3 vs 13.3)
-    (14336, 4096, 1): (112, 1),    # 8B gate/up + SiLU          (46.4 vs 53.4)
-    (4096, 14336, 2): (64, 4),     # 8B down_proj               (22.2 vs 33.9)
-    (128256, 4096, 0): (64, 1),    # Llama-3 LM head            (177 vs 190, 5.9 TB/s)
-    (1280, 8192, 2): (64, 8),      # 70B TP=8 qkv               (7.8 vs 15.3)
-    (8192, 1024, 0): (32, 1),      # 70B TP=8 o_proj            (6.3 vs 11.4)
-    (3584, 8192, 1): (32, 1),      # 70B TP=8 gate/up + SiLU    (26.6 vs 29.7)
-    (8192, 3584, 0): (32, 1),      # 70B TP=8 down_proj         (13.3 vs 15.6)
-}
 DECODE_GEMM_MAX_N = 262144
-# mode 3 (split-K + last-arriver residual update), (N, K) -> (wr, sk). In isolation
-# (micro_gemm_decode.py resid) wr32/sk2 wins by ~1 us, but inside the decode graph wr64/sk4
-# is faster (bench decode 4.07 -> 3.93 ms/step): keep what the real step measures.
-DECODE_GEMM_RESID_CFG = {
-    (4096, 4096): (64, 4),     # 8B o_proj
-    (4096, 14336): (64, 4),    # 8B down
-}
-
-
-def _cfg_for(n: int, k: int, mode: int, max_sk: int = 8):
-    c = DECODE_GEMM_CFG.get((n, k, mode))
-    if c is not None and c[1] <= max_sk:
-        return c
-    import math
-
-    best, score = (64, 1), 1e9
-    for wr in (64, 32):
-        cols = wr // 2 if mode == 1 else wr
-        if n % cols:
-            continue
-        for sk in ((1, 2, 4, 8) if mode == 2 else (1,)):
-            if sk > max_sk:
-                continue
-            if k % (256 * sk):
-                continue
-            s = abs(math.log2((n // cols) * sk / 256.0))
-            if s < score - 1e-9:
-                best, score = (wr, sk), s
-    return best
-
-
-def gd_tile_valid(wr: int, kc: int, xr: int) -> bool:
-    """A (wr, kc) tile has an xr-row activation image (mirror of gemm_decode.hip gd_valid)."""
-    rpp = 64 // (kc // 8)
-    slot = (wr + xr) * kc * 2
-    s = min(8, 147456 // slot)
-    per_wave = (wr + xr) // rpp // 4
-    while s > 2 and (s - 1) * per_wave > 63:
-        s -= 1
-    red = (4 if xr < 64 and kc >= 128 else 1) * max(xr, 32) * wr * 4 + 2048
-    return (s >= 2 and (wr + xr) % (4 * rpp) == 0 and xr % rpp == 0 and wr % rpp == 0
-            and not (xr < 64 and kc < 128 and wr % 64) and max(s * slot, red) <= 160 * 1024)
-
-
-# (N, K, mode, row bucket) -> (wr, kc, sk) for the fused decode layer's projections (mode 2 qkv slabs,
-# 3 o / down residual update, 4 gate/up row-norm + SiLU), Llama-3-8B shapes, measured on MI355X with
-# bench/micro_gemm_decode_large.py (cold weights, tile-order packed; profiles/micro_gemm_decode_large_r2.jsonl).
-# The 32-row bucket keeps round 1's in-graph choices (DECODE_GEMM_CFG / DECODE_GEMM_RESID_CFG).
-DECODE_TILE_CFG = {
-    (6144, 4096, 2, 64): (96, 128, 4),     # qkv   15.0 us vs hipBLASLt 17.9
-    (6144, 4096, 2, 128): (48, 128, 2),    #       20.2 vs 25.3
-    (4096, 4096, 3, 64): (64, 128, 4),     # o     13.4 vs 15.3
-    (4096, 4096, 3, 128): (32, 128, 2),    #       16.5 vs 24.6
-    (14336, 4096, 4, 64): (112, 128, 1),   # gate/up + SiLU  45.6 vs 50.5
-    (14336, 4096, 4, 128): (128, 64, 1),   #                 57.2 vs 54.7
-    (4096, 14336, 3, 64): (64, 128, 4),    # down  28.3 vs 40.0
-    (4096, 14336, 3, 128): (128, 64, 8),   #       38.3 vs 75.3
-    # the bench's 32-row bucket, round-4 sweep (bench/micro_tp_tiles.py --shapes 8b, profiles/micro_8b_tiles_r4.jsonl,
-    # cold us) confirmed in the real graph: bench 50.49 -> 51.45 req/s with all three, same box
-    # (profiles/bench_r4_tile_ab.jsonl; gate/up alone 50.94, o alone 50.44)
-    (4096, 4096, 3, 32): (32, 256, 2),     # o      13.96 vs 15.44 for (64, 256, 4)
-    (14336, 4096, 4, 32): (128, 128, 1),   # gate/up + SiLU 42.08 vs 43.96 for (112, 128, 1)
-    (4096, 14336, 3, 32): (64, 128, 4),    # down   29.6 vs 30.2 for (64, 256, 4)
-    # tensor-parallel shards, 32 rows (bench/micro_tp_tiles.py, profiles/micro_tp_tiles_r4.jsonl, cold, us)
-    # round 5: consumers take 256 statistics tiles at <= 32 rows, so the 70B shard's wr = 32 tiles (one workgroup
-    # per CU, no split-K) are usable (bench/micro_tp_tiles.py --proj o,down, profiles/r5_tp8_tiles_wr32.jsonl):
-    # o 10.00 vs 11.28 us for (64, 256, 1), down 17.20 vs 17.96 for (64, 128, 2); probe 5.74 -> 5.58 ms/step
-    (8192, 1024, 3, 32): (32, 128, 1),     # 70B TP=8 o
-    (8192, 3584, 3, 32): (32, 256, 1),     # 70B TP=8 down
-    (4096, 2048, 3, 32): (32, 128, 2),     # 8B TP=2 o      11.48 vs 12.68
-    (4096, 7168, 3, 32): (64, 128, 4),     # 8B TP=2 down   18.40 vs 18.88
-    (3072, 4096, 2, 32): (48, 128, 4),     # 8B TP=2 qkv    11.08 vs 11.80
-    (7168, 4096, 4, 32): (64, 128, 1),     # 8B TP=2 gate/up 24.84 vs 25.68
-    (1280, 8192, 2, 64): (32, 256, 4),     # 70B TP=8 qkv at 64 rows  13.80 vs 14.40 for (32, 128, 4)
-    (8192, 1024, 3, 128): (64, 64, 2),     # 70B TP=8 o at 128 rows   17.52 vs 18.20 for (64, 128, 2)
-    # Llama-3-70B on ONE GPU (TP=1): decode streams the row-major weights (their tile-order copies do not fit beside
-    # 141 GB); round-6 sweep (bench/micro_tp_tiles.py --shapes 70b --row-major, profiles/r6_70b_tp1_tiles.jsonl, cold us)
-    (10240, 8192, 2, 32): (64, 256, 1),    # qkv            38.76 vs 43.68 for the generic (64, 256, 2)
-    (28672, 8192, 4, 32): (112, 128, 1),   # gate/up + SiLU 165.76 vs 189.88 for (64, 256, 1)
-    (8192, 28672, 3, 32): (128, 128, 4),   # down           80.68 vs 88.48 for (64, 256, 2)
-}
-
-
-def _tile_overrides(spec: str) -> dict:
-    """DIE_TILE_OVERRIDE="N,K,mode,bucket=wr,kc,sk;...": decode-GEMM tiles to try in the real graph (A/B runs of
-    a micro-bench winner) without editing DECODE_TILE_CFG."""
-    out = {}
-    for item in filter(None, (s.strip() for s in spec.split(";"))):
-        key, val = item.split("=")
-        out[tuple(int(v) for v in key.split(","))] = tuple(int(v) for v in val.split(","))
-    return out
-
-
-DECODE_TILE_CFG.update(_tile_overrides(os.environ.get("DIE_TILE_OVERRIDE", "")))
-_GENERIC_TILES = ((64, 128),(128, 64), (32, 128), (64, 64), (128, 32), (64, 32), (112, 128), (96, 128), (48, 128),
-                  (128, 128))
-
-
-# (N, K, mode, row bucket) -> (wr, kc, sk) where the decode GEMM streams the ROW-MAJOR weights by choice
-# (EngineConfig.decode_weight_layout = single: the KV pool is the constraint, no tile-order copies), measured with
-# bench/micro_tp_tiles.py --row-major; shapes not listed fall back to the tile-order table's choice
-# Round 6, Llama-3-8B at 32 rows: the cold sweep's row-major winners (o (64, 256, 4) 14.44 vs 15.28 us, gate/up
-# (64, 256, 1) 48.28 vs 53.68, profiles/r6_8b_rm_tiles.jsonl) LOST in the graph — decode 3.96 vs 3.76 ms/step,
-# profiles/r6_decode_layout_rm_tiles_negative.jsonl — so the 8B shapes keep the tile-order table's tiles.
-DECODE_TILE_CFG_RM: dict = {}
-
-
-def decode_tile(n: int, k: int, mode: int, bucket: int = 32, max_sk: int = 8, row_major: bool = False):
-    """(wr, kc, sk) of the decode GEMM for an [N, K] projection in ``mode`` (0 bf16, 1 / 4 SiLU, 2 slabs,
-    3 residual update) at steps of up to ``bucket`` rows (32, 64, 128); ``row_major``: on weights kept row-major."""
-    import math
-
-    if row_major:
-        c = DECODE_TILE_CFG_RM.get((n, k, mode, bucket))
-        if c is not None and c[2] <= max_sk:
-            return c
-
-    c = DECODE_TILE_CFG.get((n, k, mode, bucket))
-    # mode 3 writes one statistics tile per wr columns; its consumers take at most 128 of them
-    if c is not None and c[2] <= max_sk and (mode != 3 or n // c[0] <= (SSP_MAX_TILES if bucket <= 32
-                                                                         else SSP_MAX_TILES_WIDE)):
-        return c
-    if bucket <= 32:
-        if mode == 3:
-            c = DECODE_GEMM_RESID_CFG.get((n, k))
-            if c is None:
-                wr, sk = _cfg_for(n, k, 2, max_sk)
-                if wr not in (32, 64, 128) or n % wr:
-                    wr = 64 if n % 64 == 0 else 32
-                while sk > 1 and k % (256 * sk):
-                    sk //= 2
-                c = (wr, sk)
-            return (*gd_tile(c[0]), c[1])
-        wr, sk = _cfg_for(n, k, {4: 1}.get(mode, mode), max_sk)
-        return (*gd_tile(wr), sk)
-    return _generic_tile(n, k, mode, bucket, max_sk)
-
-
-def _generic_tile(n: int, k: int, mode: int, bucket: int, max_sk: int = 8):
-    """The (wr, kc, sk) tile that exists for `bucket` activation rows and brings the grid closest to 256
-    workgroups (one per CU)."""
-    import math
-
-    best, score = None, 1e9
-    for wr, kc in _GENERIC_TILES:
-        cols = wr // 2 if mode in (1, 4) else wr
-        if n % cols or (mode == 3 and wr not in (32, 64, 128)) or not gd_tile_valid(wr, kc, bucket):
-            continue
-        for sk in ((1, 2, 4, 8) if mode in (2, 3) else (1,)):
-            if sk > max_sk or k % (kc * sk):
-                continue
-            sc = abs(math.log2((n // cols) * sk / 256.0))
-            if sc < score - 1e-9:
-                best, score = (wr, kc, sk), sc
-    if best is None:
-        raise ValueError(f"no decode-GEMM tile for N={n} K={k} mode={mode} at {bucket} rows")
-    return best
-
-
-def _bucket(m: int) -> int:
-    return 32 if m <= 32 else (64 if m <= 64 else 128)
 
 
 def linear(x: torch.Tensor, w: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """y = x @ w^T. Decode-sized M (<= 128 rows) runs on the weight-streaming
     gfx950 kernel (gemm_decode.hip); larger M goes to hipBLASLt."""
     if _decode_gemm_ok(x, w) and w.shape[0] % 32 == 0 and w.shape[0] <= DECODE_GEMM_MAX_N:
-        wr, kc, _ = decode_tile(w.shape[0], x.shape[1], 0, _bucket(x.shape[0]))
-        return gemm_decode(x, w, 0, wr, 1, out, kc=kc)
+        wr, kc, _ = decode_tile(w.shape[0], x.shape[1], MODE_BF16, decode_bucket(x.shape[0]))
+        return gemm_decode(x, w, MODE_BF16, wr, 1, out, kc=kc)
     return torch.nn.functional.linear(x, w, out=out) if out is not None else torch.nn.functional.linear(x, w)
 
 
@@ -718,7 +512,7 @@ def linear_residual(resid: torch.Tensor, x: torch.Tensor, w: torch.Tensor) -> to
 
 def linear_tiled(x: torch.Tensor, w: torch.Tensor, wr: int, kc: int) -> torch.Tensor:
     """y = x @ w^T (bf16, decode sizes) with w packed by gd_pack_weights for the (wr, kc) tile."""
-    return gemm_decode(x, w, 0 | 32, wr, 1, kc=kc)
+    return gemm_decode(x, w, MODE_BF16 | TILED, wr, 1, kc=kc)
 
 
 def linear_tiled_argmax(x: torch.Tensor, w: torch.Tensor, wr: int, kc: int, amax: torch.Tensor) -> torch.Tensor:
@@ -736,17 +530,17 @@ def linear_slab(x: torch.Tensor, w: torch.Tensor, sk: Optional[int] = None, wr: 
     tiled: w was packed by gd_pack_weights for this (wr, kc)."""
     if sk is None or wr is None:
         assert not tiled, "a tiled weight needs its packing wr"
-        wr0, kc0, sk0 = decode_tile(w.shape[0], x.shape[1], 2, _bucket(x.shape[0]))
+        wr0, kc0, sk0 = decode_tile(w.shape[0], x.shape[1], MODE_SLAB, decode_bucket(x.shape[0]))
         wr, sk, kc = wr or wr0, sk or sk0, kc or kc0
-    return gemm_decode(x, w, 2 | (32 if tiled else 0), wr, sk, kc=kc)
+    return gemm_decode(x, w, MODE_SLAB | (TILED if tiled else 0), wr, sk, kc=kc)
 
 
 def linear_silu_mul(x: torch.Tensor, w_gate_up: torch.Tensor) -> torch.Tensor:
     """silu(x @ gate^T) * (x @ up^T) with w_gate_up = [gate; up] (fused epilogue
     in the decode kernel; GEMM + silu_and_mul kernel otherwise)."""
     if _decode_gemm_ok(x, w_gate_up) and (w_gate_up.shape[0] // 2) % 32 == 0:
-        wr, kc, _ = decode_tile(w_gate_up.shape[0] // 2, x.shape[1], 1, _bucket(x.shape[0]))
-        return gemm_decode(x, w_gate_up, 1, wr, 1, kc=kc)
+        wr, kc, _ = decode_tile(w_gate_up.shape[0] // 2, x.shape[1], MODE_SILU, decode_bucket(x.shape[0]))
+        return gemm_decode(x, w_gate_up, MODE_SILU, wr, 1, kc=kc)
     return silu_and_mul(torch.nn.functional.linear(x, w_gate_up))
 
 
@@ -865,7 +659,7 @@ def moe_apply(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, w: torch.Ten
     # rows of the extra groups are never computed: zero them so that weight 0 x row stays 0
     ys = (torch.zeros if groups > e else torch.empty)(t * k, hdim, dtype=x.dtype, device=x.device)
     x = x.contiguous()
-    tiles = _moe_decode_tiles(hdim, inter, t)
+    tiles = moe_decode_tiles(hdim, inter, t)
     if tiles is not None and t <= MOE_DECODE_MAX_T:
         # decode: every expert's weights streamed once by the weight-streaming kernel, its routed
         # tokens (<= t, so the activation image of the step's row bucket holds any expert's group)
@@ -873,15 +667,15 @@ def moe_apply(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, w: torch.Ten
         # fused; idle experts read nothing
         (wr1, kc1), (wr2, kc2) = tiles
         a = torch.empty(t * k, inter, dtype=x.dtype, device=x.device)
-        kern.gemm_decode_grouped(a, x, w13, offsets, 1, wr1, kc1, sorted_idx, k, t, 1)
-        kern.gemm_decode_grouped(ys, a, w2, offsets, 0, wr2, kc2, _NO_ROWS(x.device), 1, t, 1)
+        kern.gemm_decode_grouped(a, x, w13, offsets, MODE_SILU, wr1, kc1, sorted_idx, k, t, 1)
+        kern.gemm_decode_grouped(ys, a, w2, offsets, MODE_BF16, wr2, kc2, _NO_ROWS(x.device), 1, t, 1)
         if residual is not None:  # combine + residual add + next-norm statistics in one launch
             kern.moe_combine_residual(ssp, residual, ys, pos, w)
             return residual
         out = torch.empty_like(x)
         kern.moe_combine(out, ys, pos, w)
         return out
-    seg_tiles = _moe_decode_tiles(hdim, inter, MOE_DECODE_MAX_T)
+    seg_tiles = moe_decode_tiles(hdim, inter, MOE_DECODE_MAX_T)
     capturing = torch.cuda.is_current_stream_capturing()
     if (t >= MOE_LIBRARY_MIN_TOKENS or seg_tiles is None) and not capturing:
         # prefill: the per-expert groups are thousands of rows — hipBLASLt GEMMs per expert at
@@ -907,8 +701,8 @@ def moe_apply(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, w: torch.Ten
         off_v = torch.minimum(offsets[:-1, None] + j[None, :], offsets[1:, None]).reshape(-1)
         off_v = torch.cat([off_v, offsets[-1:]]).to(torch.int32).contiguous()
         a = torch.empty(t * k, inter, dtype=x.dtype, device=x.device)
-        kern.gemm_decode_grouped(a, x, w13, off_v, 1, wr1, kc1, sorted_idx, k, MOE_DECODE_MAX_T, segs)
-        kern.gemm_decode_grouped(ys, a, w2, off_v, 0, wr2, kc2, _NO_ROWS(x.device), 1, MOE_DECODE_MAX_T, segs)
+        kern.gemm_decode_grouped(a, x, w13, off_v, MODE_SILU, wr1, kc1, sorted_idx, k, MOE_DECODE_MAX_T, segs)
+        kern.gemm_decode_grouped(ys, a, w2, off_v, MODE_BF16, wr2, kc2, _NO_ROWS(x.device), 1, MOE_DECODE_MAX_T, segs)
     out = torch.empty_like(x)
     kern.moe_combine(out, ys, pos, w)
     if residual is not None:
@@ -926,26 +720,3 @@ def _NO_ROWS(device) -> torch.Tensor:
     if t is None:
         t = _NO_ROWS_CACHE[device] = torch.empty(0, dtype=torch.int32, device=device)
     return t
-
-
-def _moe_decode_tiles(hdim: int, inter: int, t: int):
-    """((wr, kc) of the gate/up grouped GEMM, (wr, kc) of the down one) for a decode step of t tokens, or
-    None when the shapes do not tile. Up to 32 rows: round 1's measured choice (gate/up as the dense
-    gate/up shape, down wr 64 / 32 at a 256-wide K slot); above, the row bucket's generic tile."""
-    if hdim % 32 or inter % 32:
-        return None
-    if t <= 32:
-        wr1 = _cfg_for(inter, hdim, 1)[0]
-        if not (hdim % 256 or inter % 256 or inter % (wr1 // 2) or hdim % 64):
-            return gd_tile(wr1), gd_tile(64)
-    try:  # the row bucket's generic tiles (also for small shards, e.g. experts split under TP)
-        b = _bucket(t)
-        wr1, kc1, _ = _generic_tile(inter, hdim, 1, b, max_sk=1)
-        wr2, kc2, _ = _generic_tile(hdim, inter, 0, b, max_sk=1)
-    except ValueError:
-        return None
-    return (wr1, kc1), (wr2, kc2)
-
-
-def _moe_down_wr(hdim: int, inter: int) -> int:
-    return 64 if hdim % 64 == 0 else 32

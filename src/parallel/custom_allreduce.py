@@ -165,8 +165,8 @@ class CustomAllReduce:
 
         m, n = x.shape[0], w.shape[0]
         slab = torch.empty(sk, m, n, dtype=torch.float32, device=x.device)
-        _kern().gemm_decode_car(slab, x, w, 3 | (32 if tiled else 0) | (64 if half_ring else 0), wr, kc, sk,
-                                ops.DECODE_GEMM_NT, resid, ssp,
+        mode = ops.MODE_RESID | (ops.TILED if tiled else 0) | (ops.HALF_RING if half_ring else 0)
+        _kern().gemm_decode_car(slab, x, w, mode, wr, kc, sk, ops.DECODE_GEMM_NT, resid, ssp,
                                 counters, self.rank, self.bufs, self.sigs, self.ctl, self.cap)
 
     def read_ctl(self) -> List[int]:

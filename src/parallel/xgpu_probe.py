@@ -128,10 +128,10 @@ def _fused_row_parallel(rank: int, world: int, dev, car, group=None, rccl_group=
         if k % 256:
             res[name] = {"skipped": f"K = {k}"}
             continue
-        wr, kc, sk = ops.decode_tile(n, k, 3, 32)
+        wr, kc, sk = ops.decode_tile(n, k, ops.MODE_RESID, 32)
         half = None
         for h in (False, True):  # the model's choice (CausalLM._tp_fused_tile): full LDS ring, else the half ring
-            if car.fused_ok(n // wr, (n // wr) * sk, ops.gd_occupancy(3, wr, kc, sk, 32, h)):
+            if car.fused_ok(n // wr, (n // wr) * sk, ops.gd_occupancy(ops.MODE_RESID, wr, kc, sk, 32, h)):
                 half = h
                 break
         if half is None:

@@ -624,8 +624,8 @@ def test_gemm_decode_uneven_split_slabs(dev, n, k, wr, kc, sk, m):
     x = torch.randn(m, k, device=dev, dtype=torch.bfloat16)
     w = torch.randn(n, k, device=dev, dtype=torch.bfloat16) / math.sqrt(k)
     ref32 = x.float() @ w.float().t()
-    a = ops.gemm_decode(x, w, mode=2, wr=wr, sk=sk, kc=kc)
-    b = ops.gemm_decode(x, ops.gd_pack_weights(w, wr, kc=kc), mode=2 | 32, wr=wr, sk=sk, kc=kc)
+    a = ops.gemm_decode(x, w, mode=ops.MODE_SLAB, wr=wr, sk=sk, kc=kc)
+    b = ops.gemm_decode(x, ops.gd_pack_weights(w, wr, kc=kc), mode=ops.MODE_SLAB | ops.TILED, wr=wr, sk=sk, kc=kc)
     assert a.shape == (sk, m, n) and torch.equal(a, b)
     close(a.sum(0), ref32, atol=2e-3, rtol=2e-3)
 
@@ -689,7 +689,7 @@ def test_gemm_decode_tiled_weights(dev, mode, n, k, wr, sk):
         b = ops.linear_silu_mul_rownorm(x, wt, ssp_in, 1e-5, wr, tiled=True)
     else:
         a = ops.gemm_decode(x, w, mode=mode, wr=wr, sk=sk)
-        b = ops.gemm_decode(x, wt, mode=mode | 32, wr=wr, sk=sk)
+        b = ops.gemm_decode(x, wt, mode=mode | ops.TILED, wr=wr, sk=sk)
     assert torch.equal(a, b)
     if mode == 0:
         close(a, x.float() @ w.float().t(), atol=2e-2, rtol=1e-2)
@@ -775,13 +775,13 @@ def test_gemm_decode_large_m(dev, m, wr, kc):
     x = torch.randn(m, k, device=dev, dtype=torch.bfloat16)
     w = torch.randn(2 * n, k, device=dev, dtype=torch.bfloat16) / math.sqrt(k)
     try:
-        y = ops.gemm_decode(x, w[:n], 0, wr, 1, kc=kc)
+        y = ops.gemm_decode(x, w[:n], ops.MODE_BF16, wr, 1, kc=kc)
     except RuntimeError as e:  # (wr, kc) has no image for this many rows: a clean launch error
         assert "invalid" in str(e).lower() or "unsupported" in str(e).lower(), e
         return
     close(y, x.float() @ w[:n].float().t(), atol=2e-2, rtol=2e-2)
     if wr in (64, 128) or (wr == 112 and n % 56 == 0):
-        ys = ops.gemm_decode(x, w, 1, wr, 1, kc=kc)
+        ys = ops.gemm_decode(x, w, ops.MODE_SILU, wr, 1, kc=kc)
         h = x.float() @ w.float().t()
         close(ys, torch.nn.functional.silu(h[:, :n]) * h[:, n:], atol=3e-2, rtol=3e-2)
 
@@ -792,10 +792,10 @@ def test_gemm_decode_large_m_slabs_and_tiled(dev, m, wr, kc, sk):
     k, n = 4096, 2048
     x = torch.randn(m, k, device=dev, dtype=torch.bfloat16)
     w = torch.randn(n, k, device=dev, dtype=torch.bfloat16) / math.sqrt(k)
-    a = ops.gemm_decode(x, w, 2, wr, sk, kc=kc)
+    a = ops.gemm_decode(x, w, ops.MODE_SLAB, wr, sk, kc=kc)
     close(a.sum(0), x.float() @ w.float().t(), atol=2e-2, rtol=2e-2)
     wt = ops.gd_pack_weights(w, wr, kc=kc)
-    b = ops.gemm_decode(x, wt, 2 | 32, wr, sk, kc=kc)
+    b = ops.gemm_decode(x, wt, ops.MODE_SLAB | ops.TILED, wr, sk, kc=kc)
     assert torch.equal(a, b)
 
 
@@ -817,7 +817,7 @@ def test_embed_sumsq_matches_gather_and_fp32_sumsq(dev, rows):
 
 @pytest.mark.parametrize("n,k,wr,kc,sk,m", [(3584, 8192, 64, 256, 2, 32), (3584, 8192, 64, 256, 2, 7),
                                            (2048, 1024, 64, 128, 4, 32), (2048, 1024, 128, 64, 2, 1),
-                                           # the 70B TP=8 shard's 64- / 128-row tiles (DECODE_SILU_SPLITK_CFG)
+                                           # the 70B TP=8 shard's 64- / 128-row tiles (DECODE_TILE_CFG's mode-6 keys)
                                            (3584, 8192, 112, 128, 4, 64), (3584, 8192, 112, 128, 4, 50),
                                            (3584, 8192, 64, 128, 2, 128), (3584, 8192, 64, 128, 2, 100)])
 def test_gate_up_split_k_silu_matches_full_k(dev, n, k, wr, kc, sk, m):
@@ -969,8 +969,8 @@ def test_half_ring_residual_gemm_matches_full_ring(dev, n, k, wr, kc, sk, rows):
     """The half-LDS ring of the residual-updating decode GEMM (mode 3, two workgroups per CU: the TP exchange's
     residency form at the 70B TP=8 shard's o / down shapes) gives bit-identical residual and statistics to the full
     ring, and its occupancy is what the residency rule assumes (2 per CU vs 1)."""
-    assert ops.gd_occupancy(3, wr, kc, sk, 32, False) == 1
-    assert ops.gd_occupancy(3, wr, kc, sk, 32, True) >= 2
+    assert ops.gd_occupancy(ops.MODE_RESID, wr, kc, sk, 32, False) == 1
+    assert ops.gd_occupancy(ops.MODE_RESID, wr, kc, sk, 32, True) >= 2
     g = torch.Generator(device=dev).manual_seed(n + k + rows)
     x = (torch.randn(rows, k, device=dev, generator=g) * 0.5).to(torch.bfloat16)
     w = (torch.randn(n, k, device=dev, generator=g) * 0.03).to(torch.bfloat16)
@@ -1009,6 +1009,7 @@ def test_tp8_shard_plan_takes_the_half_ring_on_real_occupancy():
     m.tp = NodeTP(rank=0, world_size=8)
     m.hq, m.hkv, m.head_dim, m.inter = 8, 1, 128, 28672 // 8
     m.layers = [type("L", (), {"qkv": torch.empty(1280, 8192, device="meta")})()]
-    assert ops.gd_occupancy(3, 32, 128, 1, 32, False) == 1 and ops.gd_occupancy(3, 32, 256, 1, 32, False) == 1
+    assert ops.gd_occupancy(ops.MODE_RESID, 32, 128, 1, 32, False) == 1
+    assert ops.gd_occupancy(ops.MODE_RESID, 32, 256, 1, 32, False) == 1
     p = m.decode_plan(32)
     assert p["tp_fused"] and p["o"][0] == 32 and p["down"][0] == 32 and p["o_half"] and p["down_half"], p
