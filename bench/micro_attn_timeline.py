@@ -3,8 +3,11 @@ FUSED prologue) — by default the headline shape, 32 sequences x 8 kv heads (Ll
 contexts 512..640; ``--shape 70b_tp8`` is a Llama-3-70B TP=8 rank (1 kv head, 8 q heads), ``--ctx N`` gives
 every sequence the same context (as in a bench wave), ``--max-ctx`` the static bound that sizes the parts
 (C = chunks per task). KV blocks allocated contiguously per sequence as the engine's block manager does, cold
-KV (a new pool slice per call). Stamps (s_memrealtime, 100 MHz): entry, first chunk landed, prologue done,
-stream done, end. Prints the median phase durations, the kernel span and the event-timed us per call."""
+KV: the launches rotate over ``--kv-pools N`` distinct KV pools whose read bytes total more than the 256 MB
+Infinity Cache, so every timed launch reads its K/V from HBM as a step of the engine does (one replayed pool
+would sit in the Infinity Cache and rank the cache policies the wrong way round). ``--kv-policy`` picks the
+K/V stream's cache policy (once = nt, default). Stamps (s_memrealtime, 100 MHz): entry, first chunk landed,
+prologue done, stream done, end. Prints the median phase durations, the kernel span and the event-timed us per call."""
 
 import json
 import os
@@ -27,6 +30,8 @@ def main():
     ap.add_argument("--max-ctx", type=int, default=2048)
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--static-parts", action="store_true", help="A/B: the static split also for few pairs")
+    ap.add_argument("--kv-pools", type=int, default=0, help="distinct KV pools to rotate over (0: 12, 40 for shards)")
+    ap.add_argument("--kv-policy", default="once", choices=["once", "default"], help="cache policy of the K/V stream")
     ap.add_argument("--sk", type=int, default=0, help="qkv split-K slabs the prologue sums (0: the engine's tile)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -36,7 +41,10 @@ def main():
     ctxs = [a.ctx] * n if a.ctx else [512 + 4 * i for i in range(n)]
     max_ctx = a.max_ctx
     per_seq = max_ctx // bs
-    copies = 12 if a.shape == "8b" else 40         # >> the 256 MB Infinity Cache
+    copies = a.kv_pools or (12 if a.shape == "8b" else 40)
+    kv_bytes = sum(ctxs) * hkv * d * 2 * 2
+    # the first two pools are warm-up; the rest must push each other out of the 256 MB Infinity Cache
+    assert copies >= 3 and copies * kv_bytes > 256e6, f"--kv-pools {copies} x {kv_bytes >> 20} MB stays cached"
     nb = copies * n * per_seq
     kc = torch.randn(nb, hkv, bs, d, device=dev, dtype=torch.bfloat16)
     vc = torch.randn(nb, hkv, bs, d, device=dev, dtype=torch.bfloat16)
@@ -56,12 +64,11 @@ def main():
     cnt = torch.zeros(n * hkv, dtype=torch.int32, device=dev)
     ncu = torch.cuda.get_device_properties(dev).multi_processor_count
     ts = torch.zeros(copies, 2 * ncu * 6, dtype=torch.int64, device=dev)  # grids of up to 2 workgroups per CU
-    kv_bytes = sum(ctxs) * hkv * d * 2 * 2
 
     def call(c):
         slots = (bts[c][torch.arange(n, device=dev), (ctx - 1).long() // bs].long() * bs + (ctx - 1).long() % bs)
         ops.attn_decode_fused(slab, ssp, pos, cs, slots, kc, vc, bts[c], ctx, max_ctx, hq, hkv, d ** -0.5, 1e-5, hid,
-                              po, pm, cnt)
+                              po, pm, cnt, kv_once=a.kv_policy == "once")
 
     for c in range(copies):
         call(c)
@@ -101,7 +108,8 @@ def main():
     out["us_per_call"] = round(us_call, 2)
     out["kv_TBps_call"] = round(kv_bytes / us_call / 1e6, 2)
     print(json.dumps({"bench": "attn_decode_timeline", "shape": a.shape, "batch": n, "ctx": [ctxs[0], ctxs[-1]],
-                      "max_ctx": max_ctx, "qkv_sk": sk, "workgroups_with_a_task": int((t[-1][:, 3] > 0).sum()),
+                      "max_ctx": max_ctx, "kv_pools": copies, "kv_policy": a.kv_policy, "qkv_sk": sk,
+                      "workgroups_with_a_task": int((t[-1][:, 3] > 0).sum()),
                       **out}), flush=True)
 
 

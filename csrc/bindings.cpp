@@ -197,7 +197,8 @@ void attn_prefill(Tensor out, Tensor q, Tensor k_cache, Tensor v_cache, Tensor b
 // counters: int32 [>= num_seqs * hkv], zero before first use (the kernel re-arms them); an empty tensor
 // selects the two-kernel path (partials + merge launch).
 void attn_decode(Tensor out, Tensor part_o, Tensor part_ml, Tensor counters, Tensor q, Tensor k_cache, Tensor v_cache,
-                 Tensor block_tables, Tensor ctx_lens, int64_t max_ctx, int64_t hq, int64_t hkv, double scale) {
+                 Tensor block_tables, Tensor ctx_lens, int64_t max_ctx, int64_t hq, int64_t hkv, double scale,
+                 bool kv_once) {
   CHK_CUDA(q);
   CHK_BF16(q);
   CHK_BF16(out);
@@ -229,7 +230,7 @@ void attn_decode(Tensor out, Tensor part_o, Tensor part_ml, Tensor counters, Ten
   HIP_OK(die::launch_attn_decode(bf(out), part_o.data_ptr<float>(), part_ml.data_ptr<float>(), cnt, bf(q), q.stride(0),
                                   bf(k_cache), bf(v_cache), block_tables.data_ptr<int>(), (int)block_tables.size(1),
                                   ctx_lens.data_ptr<int>(), (int)nseq, (int)max_ctx, (int)hq, (int)hkv, (int)D,
-                                  (int)k_cache.size(2), (float)scale, nullptr, cur_stream()));
+                                  (int)k_cache.size(2), (float)scale, nullptr, kv_once, cur_stream()));
 }
 
 // Decode attention with the fused prologue: q / new K,V built from the qkv projection's
@@ -238,7 +239,7 @@ void attn_decode(Tensor out, Tensor part_o, Tensor part_ml, Tensor counters, Ten
 void attn_decode_fused(Tensor out, Tensor part_o, Tensor part_ml, Tensor counters, Tensor slab, Tensor ssp,
                        Tensor positions, Tensor cos_sin, Tensor slot_mapping, Tensor k_cache, Tensor v_cache,
                        Tensor block_tables, Tensor ctx_lens, int64_t max_ctx, int64_t hq, int64_t hkv, double scale,
-                       double eps, int64_t hidden) {
+                       double eps, int64_t hidden, bool kv_once) {
   CHK_CUDA(slab);
   CHK_DTYPE(slab, at::kFloat);
   CHK_CONTIG(slab);
@@ -293,7 +294,7 @@ void attn_decode_fused(Tensor out, Tensor part_o, Tensor part_ml, Tensor counter
                                   counters.data_ptr<int>(), nullptr, 0, bf(k_cache), bf(v_cache),
                                   block_tables.data_ptr<int>(), (int)block_tables.size(1), ctx_lens.data_ptr<int>(),
                                   (int)nseq, (int)max_ctx, (int)hq, (int)hkv, (int)D, 16, (float)scale, &fz,
-                                  cur_stream()));
+                                  kv_once, cur_stream()));
 }
 
 int64_t decode_partials(int64_t max_ctx) { return die::attn_decode_max_partials((int)max_ctx); }

@@ -388,7 +388,7 @@ static_assert(V3_LDS <= 160 * 1024, "one v3 workgroup per CU");
 // row straight into this step's LDS image. The separate RoPE/KV-write and RMSNorm kernels of
 // the decode layer disappear. Everything the prologue needs arrives by LDS-DMA, staged in the
 // merge area (idle at a task start), so no ordinary load stalls the chunk stream.
-template <int G, bool FUSED>
+template <int G, bool FUSED, int KV_AUX>
 __global__ void __launch_bounds__(256, 1) attn_decode_v3_kernel(
     bf16_t* __restrict__ out, float* __restrict__ part_o, float* __restrict__ part_ml, int* __restrict__ counters,
     const bf16_t* __restrict__ q, int64_t q_stride, bf16_t* __restrict__ k_cache, bf16_t* __restrict__ v_cache,
@@ -445,8 +445,10 @@ __global__ void __launch_bounds__(256, 1) attn_decode_v3_kernel(
         const int64_t blk = j <= last_blk ? (i < 4 ? e0 : e1) : el; // past the context: last block
         const int key = min(c * DEC_KEYS + r, ctx - 1);            // clamp: never read past the context
         const int64_t roff = ((blk * hkv + kvh) * 16 + (key & 15)) * D;
-        glds16(k_cache + roff + (pch ^ (r & 15)) * 8, base + (wave * 8 + i) * 1024);
-        glds16(v_cache + roff + (pch ^ ((r & 3) << 2)) * 8, base + DEC_KEYS * DEC_ROW + (wave * 8 + i) * 1024);
+        // KV_AUX: a step reads every K / V byte once, from one CU (attn_common.h, glds16)
+        glds16<KV_AUX>(k_cache + roff + (pch ^ (r & 15)) * 8, base + (wave * 8 + i) * 1024);
+        glds16<KV_AUX>(v_cache + roff + (pch ^ ((r & 3) << 2)) * 8,
+                       base + DEC_KEYS * DEC_ROW + (wave * 8 + i) * 1024);
       }
     };
 
@@ -795,7 +797,8 @@ void attn_set_few_pair_parts(bool on) { g_few_pair_parts = on; }
 hipError_t launch_attn_decode(bf16_t* out, float* part_o, float* part_ml, int* counters, const bf16_t* q,
                               int64_t q_stride, bf16_t* k_cache, bf16_t* v_cache, const int* block_tables,
                               int bt_stride, const int* ctx_lens, int num_seqs, int max_ctx, int hq, int hkv,
-                              int head_dim, int block_size, float scale, const AttnDecodeFuse* fz, hipStream_t s) {
+                              int head_dim, int block_size, float scale, const AttnDecodeFuse* fz, bool kv_once,
+                              hipStream_t s) {
   if (num_seqs == 0) return hipSuccess;
   if (head_dim != D || hq % hkv) return hipErrorInvalidValue;
   const int G = hq / hkv;
@@ -835,16 +838,23 @@ hipError_t launch_attn_decode(bf16_t* out, float* part_o, float* part_ml, int* c
       fzc.ts = g_attn_ts;
       fz = &fzc;
     }
-#define D3_CASE(GG)                                                                                              \
-  case GG:                                                                                                      \
-    if (fz)                                                                                                     \
-      hipLaunchKernelGGL((attn_decode_v3_kernel<GG, true>), grid, block, V3_LDS, s, out, part_o, part_ml,       \
-                         counters, q, q_stride, k_cache, v_cache, block_tables, bt_stride, ctx_lens, num_seqs, hq, \
-                         hkv, sl2, maxp3, cpp, *fz, fz->slot_mapping);                                     \
-    else                                                                                                        \
-      hipLaunchKernelGGL((attn_decode_v3_kernel<GG, false>), grid, block, V3_LDS, s, out, part_o, part_ml,      \
-                         counters, q, q_stride, k_cache, v_cache, block_tables, bt_stride, ctx_lens, num_seqs, hq, \
-                         hkv, sl2, maxp3, cpp, none, nullptr);                                             \
+    // kv_once: the K / V chunk stream is loaded as once-read data (nt). A launch argument, not a process-wide
+    // switch: the engine leaves it on also for batches whose sequences share prefix blocks (read by several
+    // workgroups in one step: bench/kv_eviction_bench.py measured no loss, docs/performance.md); false is the A/B side
+#define D3_LAUNCH(GG, FU, AUX, FZ, SM)                                                                           \
+  hipLaunchKernelGGL((attn_decode_v3_kernel<GG, FU, AUX>), grid, block, V3_LDS, s, out, part_o, part_ml, counters, \
+                     q, q_stride, k_cache, v_cache, block_tables, bt_stride, ctx_lens, num_seqs, hq, hkv, sl2,   \
+                     maxp3, cpp, FZ, SM)
+#define D3_CASE(GG)                                                                \
+  case GG:                                                                        \
+    if (fz && kv_once)                                                            \
+      D3_LAUNCH(GG, true, KV_AUX_ONCE, *fz, fz->slot_mapping);                    \
+    else if (fz)                                                                  \
+      D3_LAUNCH(GG, true, KV_AUX_DEFAULT, *fz, fz->slot_mapping);                 \
+    else if (kv_once)                                                             \
+      D3_LAUNCH(GG, false, KV_AUX_ONCE, none, nullptr);                           \
+    else                                                                          \
+      D3_LAUNCH(GG, false, KV_AUX_DEFAULT, none, nullptr);                        \
     break;
     switch (G) {
       D3_CASE(1)
@@ -853,6 +863,7 @@ hipError_t launch_attn_decode(bf16_t* out, float* part_o, float* part_ml, int* c
       D3_CASE(8)
     }
 #undef D3_CASE
+#undef D3_LAUNCH
     return hipGetLastError();
   }
   if (G > 32 || G * D * 4 * 4 + 4 * 32 * 2 * 4 > DEC_LDS) return hipErrorInvalidValue;

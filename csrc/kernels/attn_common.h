@@ -224,8 +224,13 @@ constexpr int DEC_LDS = 2 * DEC_KEYS * DEC_ROW;    // 64 KiB
 typedef __attribute__((address_space(3))) void lds_void;
 typedef __attribute__((address_space(1))) const void global_cvoid;
 
+// AUX: the load's cache policy, as gd::glds16 (gemm_decode.hip): 0 = default, 2 = nt for bytes that are
+// read once per step by one CU (the decode KV stream); everything re-read or just written stays at 0.
+constexpr int KV_AUX_DEFAULT = 0;
+constexpr int KV_AUX_ONCE = 2;
+template <int AUX = 0>
 __device__ __forceinline__ void glds16(const void* src, char* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((global_cvoid*)src, (lds_void*)lds_wave_base, 16, 0, 0);
+  __builtin_amdgcn_global_load_lds((global_cvoid*)src, (lds_void*)lds_wave_base, 16, 0, AUX);
 }
 
 // S^T tile from a swizzled K image (row r, logical chunk c at physical c ^ (r & 15)).

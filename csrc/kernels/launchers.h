@@ -60,10 +60,13 @@ struct AttnDecodeFuse {
 };
 void attn_set_timestamps(long long* ts);  // diagnostics: stamps for every following decode launch
 void attn_set_few_pair_parts(bool on);  // decode launch policy for few (sequence, kv head) pairs (default on)
+// kv_once: load the K / V chunk stream with the once-read (nt) cache policy (v3 kernel only; false: the default
+// policy, for A/B). The result is the same bit for bit either way.
 hipError_t launch_attn_decode(bf16_t* out, float* part_o, float* part_ml, int* counters, const bf16_t* q,
                               int64_t q_stride, bf16_t* k_cache, bf16_t* v_cache, const int* block_tables,
                               int bt_stride, const int* ctx_lens, int num_seqs, int max_ctx, int hq, int hkv,
-                              int head_dim, int block_size, float scale, const AttnDecodeFuse* fz, hipStream_t s);
+                              int head_dim, int block_size, float scale, const AttnDecodeFuse* fz, bool kv_once,
+                              hipStream_t s);
 int attn_decode_max_partials(int max_ctx);
 
 // splits > 1: greedy rows are argmax'ed by `splits` workgroups each (part [rows][splits][2] u32 scratch, cnt [rows]

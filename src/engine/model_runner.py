@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import bisect
 import logging
+import os
 from typing import Dict, List, Optional, Sequence as Seq
 
 import torch
@@ -143,6 +144,8 @@ class ModelRunner:
         self.last_logprobs = None         # the latest call's logprobs (take_logprobs), None when no row asked
         self.last_prompt_logprobs = None  # the latest prefill's prompt logprobs: {chunk index: (positions, ...)}
         self.d_adv_ticket = torch.zeros(1, dtype=i32, device=dev)  # sample_advance's row ticket (re-armed in-kernel)
+        # decode attention streams K/V as once-read data (DIE_ATTN_KV_ONCE=0: the default cache policy, for A/B)
+        self.kv_once = os.environ.get("DIE_ATTN_KV_ONCE", "1") != "0"
         if self.is_cuda:
             maxp = ops.decode_partials(max_model_len)
             hq = model.hq
@@ -406,8 +409,8 @@ class ModelRunner:
         tail = self._fused_tail(n)
         meta = AttnMetadata(is_prefill=False, slot_mapping=self.d_slots[:n], block_tables=self.d_bt[:n],
                             ctx_lens=self.d_ctx[:n], max_ctx=self.max_model_len, part_o=self.part_o,
-                            part_ml=self.part_ml, attn_cnt=self.attn_cnt, scratch=self.dec_scratch,
-                            pre_embedded=tail)
+                            part_ml=self.part_ml, attn_cnt=self.attn_cnt, kv_once=self.kv_once,
+                            scratch=self.dec_scratch, pre_embedded=tail)
         hidden = self.model.forward(self.d_ids[:n], self.d_pos[:n], meta, self.pool.tensor)
         amax = (self.d_lmpart if self.d_lmpart is not None and n <= ops.DECODE_GEMM_MAX_M
                 and self.model.lm_head_argmax_parts() == self.d_lmpart.shape[1] else None)

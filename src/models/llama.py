@@ -48,6 +48,7 @@ class AttnMetadata:
     part_o: Optional[torch.Tensor] = None
     part_ml: Optional[torch.Tensor] = None
     attn_cnt: Optional[torch.Tensor] = None  # decode attention merge tickets (int32, zeroed once)
+    kv_once: bool = True            # decode: the K/V stream is once-read data (ops.attn_decode)
     scratch: Optional[dict] = None  # fused decode path buffers (CausalLM.alloc_decode_scratch)
     kv_hook: Optional[Callable[[int], None]] = None  # prefill: called once layer i's KV writes are queued
     # prefill: the only rows whose final hidden state is used (each sampled chunk's last token, [n] int64): the
@@ -504,7 +505,8 @@ class CausalLM:
                                     meta.max_q_len, hq, hkv, self.scale, cos_sin=self.cos_sin if fuse_q else None,
                                     q_scale=rs)
         return ops.attn_decode(q, k_cache, v_cache, meta.block_tables, meta.ctx_lens, meta.max_ctx, hq, hkv,
-                               self.scale, part_o=meta.part_o, part_ml=meta.part_ml, counters=meta.attn_cnt)
+                               self.scale, part_o=meta.part_o, part_ml=meta.part_ml, counters=meta.attn_cnt,
+                               kv_once=meta.kv_once)
 
     def _mlp(self, lw: LayerWeights, x: torch.Tensor) -> torch.Tensor:
         """This rank's partial FFN / MoE output (summed over the TP group by the caller)."""
@@ -567,7 +569,7 @@ class CausalLM:
             else:
                 attn = ops.attn_decode(q, k_cache, v_cache, meta.block_tables, meta.ctx_lens, meta.max_ctx, hq,
                                        hkv, self.scale, part_o=meta.part_o, part_ml=meta.part_ml,
-                                       counters=meta.attn_cnt)
+                                       counters=meta.attn_cnt, kv_once=meta.kv_once)
             x = ops.fused_add_rms_norm_slab(ops.linear_slab(attn, lw.o), residual, lw.ln2, eps)
             slab = ops.linear_slab(ops.linear_silu_mul(x, lw.gate_up), lw.down)
         return ops.fused_add_rms_norm_slab(slab, residual, self.norm, eps)
@@ -825,7 +827,8 @@ class CausalLM:
             slab = ops.linear_slab(h, wqkv, sk=sq, wr=wq, tiled=tq, kc=kq)
             attn = ops.attn_decode_fused(slab, ssp_prev, positions, self.cos_sin, meta.slot_mapping,
                                          k_cache, v_cache, meta.block_tables, meta.ctx_lens, meta.max_ctx, hq, hkv,
-                                         self.scale, eps, hid, meta.part_o, meta.part_ml, meta.attn_cnt)
+                                         self.scale, eps, hid, meta.part_o, meta.part_ml, meta.attn_cnt,
+                                         kv_once=meta.kv_once)
             if a.is_moe:  # ln2 stays explicit (it also feeds the router); MoE output added back + statistics
                 if self.tp.enabled:
                     self.tp.all_reduce_residual(ops.linear(attn, lw.o), h, ssp_a)

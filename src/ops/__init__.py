@@ -161,10 +161,12 @@ def decode_partials(max_ctx: int) -> int:
 def attn_decode(q, k_cache, v_cache, block_tables, ctx_lens, max_ctx: int, hq: int, hkv: int, scale: float,
                 part_o: Optional[torch.Tensor] = None, part_ml: Optional[torch.Tensor] = None,
                 out: Optional[torch.Tensor] = None, counters: Optional[torch.Tensor] = None,
-                merge_kernel: bool = False) -> torch.Tensor:
+                merge_kernel: bool = False, kv_once: bool = True) -> torch.Tensor:
     """Paged decode attention. `counters` (int32, >= num_seqs * hkv, zeroed once) are the
     per-(sequence, kv head) tickets of the self-merging kernel; they are re-armed by the kernel,
-    so a runner allocates them once. merge_kernel=True forces the two-launch path."""
+    so a runner allocates them once. merge_kernel=True forces the two-launch path. kv_once: the
+    self-merging kernel streams K/V with the once-read (nt) cache policy (False: the default policy,
+    for A/B; the result is the same bit for bit either way)."""
     if not q.is_cuda:
         n = ctx_lens.numel()
         cu = torch.arange(n + 1, dtype=torch.int32)
@@ -181,7 +183,7 @@ def attn_decode(q, k_cache, v_cache, block_tables, ctx_lens, max_ctx: int, hq: i
     elif counters is None:
         counters = torch.zeros(n * hkv, dtype=torch.int32, device=q.device)
     _kern().attn_decode(out, part_o, part_ml, counters, q, k_cache, v_cache, block_tables, ctx_lens, max_ctx, hq,
-                        hkv, scale)
+                        hkv, scale, kv_once)
     return out
 
 
@@ -189,15 +191,18 @@ def attn_decode_fused(qkv_slab: torch.Tensor, ssp: torch.Tensor, positions: torc
                       slot_mapping: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                       block_tables: torch.Tensor, ctx_lens: torch.Tensor, max_ctx: int, hq: int, hkv: int,
                       scale: float, eps: float, hidden: int, part_o: torch.Tensor, part_ml: torch.Tensor,
-                      counters: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                      counters: torch.Tensor, out: Optional[torch.Tensor] = None,
+                      kv_once: bool = True) -> torch.Tensor:
     """Decode attention whose prologue does the input RMSNorm row scale (statistics ssp [T, 32],
     weight folded into Wqkv), the split-K reduction of the qkv slabs [sk, M, width], RoPE at
-    position ctx-1 and the paged KV write of the new token (attention.hip, FUSED)."""
+    position ctx-1 and the paged KV write of the new token (attention.hip, FUSED). kv_once as in
+    attn_decode."""
     n = ctx_lens.numel()
     if out is None:
         out = torch.empty(n, hq * 128, dtype=torch.bfloat16, device=qkv_slab.device)
     _kern().attn_decode_fused(out, part_o, part_ml, counters, qkv_slab, ssp, positions, cos_sin, slot_mapping,
-                              k_cache, v_cache, block_tables, ctx_lens, max_ctx, hq, hkv, scale, eps, hidden)
+                              k_cache, v_cache, block_tables, ctx_lens, max_ctx, hq, hkv, scale, eps, hidden,
+                              kv_once)
     return out
 
 
