@@ -12,6 +12,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rng_hash.h"  // hash_uniform: the counter-based RNG -> uniform strictly inside (0, 1)
+
 namespace die {
 
 typedef uint16_t bf16_t;  // storage type for bfloat16
@@ -109,15 +111,6 @@ __device__ __forceinline__ float block_sum(float v, float* red) {
   for (int i = 0; i < NT / 64; ++i) t += red[i];
   __syncthreads();
   return t;
-}
-
-// Counter-based RNG (splitmix64 finaliser) -> uniform in (0,1).
-__device__ __forceinline__ float hash_uniform(uint64_t seed, uint64_t a, uint64_t b) {
-  uint64_t z = seed ^ (a * 0x9E3779B97F4A7C15ull) ^ (b * 0xD1B54A32D192ED03ull);
-  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-  z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return ((float)(z >> 40) + 0.5f) * (1.0f / 16777216.0f);
 }
 
 // Compute units of the current device (256 on MI355X), cached per device: persistent and

@@ -7,7 +7,16 @@
 //  * the draw is Gumbel-max, argmax(z_i + G_i) over the kept set with
 //    G_i = -log(-log(u_i)), u from a counter-based hash of
 //    (request seed, generation step, token id): reproducible per request and
-//    independent of batch composition, and needs no prefix sum.
+//    independent of batch composition, and needs no prefix sum. u is one of the
+//    2^23 values (h + 0.5) * 2^-23 (rng_hash.h), never 0 and never 1, so G_i is
+//    finite (-2.82 .. 16.64) and no token wins on noise alone.
+// Contract of the filters (tests/sampling_reference.py is its float64 oracle,
+// tests/test_sampling_kernel_gpu.py compares draw by draw): zz = z * (1 / t) in
+// fp32; top-k keeps every zz >= the k-th largest (ties kept; k <= 0 or >= vocab
+// keeps all); top-p keeps the value levels, from the top, whose mass WITHIN the
+// top-k set first reaches p (whole levels, at least the top one); the floor is
+// the higher of the two. Drawn tokens depend on the uniform's mapping: they are
+// reproducible per build of this file, not across changes to rng_hash.h.
 // Rows stream from L2 (a 128256-entry bf16 row is 250 KiB), 16 B per lane.
 #include "common.h"
 #include "launchers.h"
