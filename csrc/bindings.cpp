@@ -374,6 +374,53 @@ void token_logprobs(Tensor lp, Tensor rank, Tensor top_lp, Tensor top_id, Tensor
                                      (int)std::min<int64_t>(std::max<int64_t>(top_n, -1), 1 << 20), cur_stream()));
 }
 
+// Penalties and logit_bias on logits [rows, vocab] in place (logit_process.hip). slot int32 [>= rows]; state int16
+// [slots, vocab] (the kernel reads it as uint16); params fp32 [slots, 4]; bias_cnt int32 [slots]; bias_ids int32 /
+// bias_vals fp32 [slots, cap]; count_ids int64 [>= rows] and lm_part int32 [>= rows, parts, 2] optional. The
+// launcher itself refuses vocab % 8 != 0, cap > 300 and an empty state table.
+void logit_process(Tensor logits, Tensor slot, Tensor state, Tensor params, Tensor bias_cnt, Tensor bias_ids,
+                   Tensor bias_vals, c10::optional<Tensor> count_ids, c10::optional<Tensor> lm_part) {
+  CHK_CUDA(logits);
+  CHK_BF16(logits);
+  check_rows(logits, "logits");
+  const int64_t rows = logits.size(0), vocab = logits.size(1);
+  TORCH_CHECK(slot.is_cuda() && slot.scalar_type() == at::kInt && slot.is_contiguous() && slot.numel() >= rows,
+              "logit_process: slot int32 [rows]");
+  TORCH_CHECK(state.is_cuda() && state.scalar_type() == at::kShort && state.is_contiguous() &&
+                  (state.numel() == 0 || (state.dim() == 2 && state.size(1) == vocab)),
+              "logit_process: state int16 [slots, vocab]");
+  const int64_t slots = state.numel() ? state.size(0) : 0;
+  TORCH_CHECK(params.is_cuda() && params.scalar_type() == at::kFloat && params.is_contiguous() &&
+                  params.numel() >= 4 * slots && reinterpret_cast<uintptr_t>(params.data_ptr()) % 16 == 0,
+              "logit_process: params fp32 [slots, 4]");
+  TORCH_CHECK(bias_cnt.is_cuda() && bias_cnt.scalar_type() == at::kInt && bias_cnt.is_contiguous() &&
+                  bias_cnt.numel() >= slots, "logit_process: bias_cnt int32 [slots]");
+  TORCH_CHECK(bias_ids.is_cuda() && bias_ids.scalar_type() == at::kInt && bias_ids.is_contiguous() &&
+                  bias_ids.dim() == 2 && bias_ids.size(0) >= slots && bias_vals.is_cuda() &&
+                  bias_vals.scalar_type() == at::kFloat && bias_vals.is_contiguous() && bias_vals.dim() == 2 &&
+                  bias_vals.size(0) >= slots && bias_vals.size(1) == bias_ids.size(1),
+              "logit_process: bias_ids int32 / bias_vals fp32 [slots, cap]");
+  const int64_t* cp = nullptr;
+  if (count_ids.has_value()) {
+    TORCH_CHECK(count_ids->is_cuda() && count_ids->scalar_type() == at::kLong && count_ids->is_contiguous() &&
+                    count_ids->numel() >= rows, "logit_process: count_ids int64 [rows]");
+    cp = count_ids->data_ptr<int64_t>();
+  }
+  uint32_t* lp = nullptr;
+  int lparts = 0;
+  if (lm_part.has_value()) {
+    TORCH_CHECK(lm_part->is_cuda() && lm_part->scalar_type() == at::kInt && lm_part->dim() == 3 &&
+                    lm_part->size(0) >= rows && lm_part->size(2) == 2 && lm_part->is_contiguous(),
+                "logit_process: lm_part [rows, parts, 2] int32");
+    lp = reinterpret_cast<uint32_t*>(lm_part->data_ptr<int>());
+    lparts = (int)lm_part->size(1);
+  }
+  HIP_OK(die::launch_logit_process(bf(logits), logits.stride(0), (int)rows, (int)vocab, slot.data_ptr<int>(),
+                                    (int)slots, slots ? reinterpret_cast<uint16_t*>(state.data_ptr<int16_t>()) : nullptr,
+                                    params.data_ptr<float>(), bias_cnt.data_ptr<int>(), bias_ids.data_ptr<int>(),
+                                    bias_vals.data_ptr<float>(), (int)bias_ids.size(1), cp, lp, lparts, cur_stream()));
+}
+
 // A decode step's sampling from the LM head's candidates (sample(..., lm_part)) that also advances the step's
 // inputs as decode_advance does (ids / pos / ctx / slots / step, the window's token row, the step counter cnt[0]),
 // one workgroup per row; ticket: int32 [1], zero, re-armed by the kernel.
@@ -1063,6 +1110,7 @@ PYBIND11_MODULE(_C, m) {
         py::arg("lm_part") = py::none());
   m.def("copy_blocks", &copy_blocks);
   m.def("token_logprobs", &token_logprobs);
+  m.def("logit_process", &logit_process);
   m.def("sample_advance", &sample_advance);
   m.def("move_blocks", &move_blocks);
   m.def("gather_blocks_rows", &gather_blocks_rows);

@@ -109,6 +109,18 @@ hipError_t launch_token_logprobs(float* lp, int* rank, float* top_lp, int* top_i
                                  const bf16_t* logits, int64_t stride, int rows, int vocab, const int64_t* targets,
                                  int top_n, hipStream_t s);
 
+// repetition / frequency / presence penalties and logit_bias on rows [rows, stride] in place (logit_process.hip):
+// row r -> slot[r] (< 0 or >= num_slots: untouched); state [num_slots, vocab] u16 (bit 15 prompt, bits 0-14 output
+// count); params [num_slots, 4] = (rp, 1/rp, freq, pres); bias_cnt [num_slots], bias_ids / bias_vals [num_slots,
+// bias_cap]; count_ids (optional) [rows]: this step's input ids, counted first; lm_part (optional) [rows, lm_parts,
+// 2]: the row's greedy candidates, rewritten to the processed argmax. hipErrorInvalidValue for vocab % 8 != 0,
+// bias_cap > LOGIT_BIAS_MAX or a null state table.
+constexpr int LOGIT_BIAS_MAX = 300;
+hipError_t launch_logit_process(bf16_t* logits, int64_t stride, int rows, int vocab, const int* slot, int num_slots,
+                                uint16_t* state, const float* params, const int* bias_cnt, const int* bias_ids,
+                                const float* bias_vals, int bias_cap, const int64_t* count_ids, uint32_t* lm_part,
+                                int lm_parts, hipStream_t s);
+
 hipError_t launch_topk_softmax(float* w, int* ids, const bf16_t* gating, int T, int E, int K, bool renorm,
                                hipStream_t s);
 hipError_t launch_moe_route(float* w, int* ids, const bf16_t* x, int64_t ldx, const bf16_t* wg, int T, int H, int E,

@@ -6,6 +6,7 @@
     python examples/example_client.py --model llama --prompt "Hi" -n 64 --concurrency 32   # mini load test
     python examples/example_client.py --model llama --prompt "Hello" --max-tokens 64 --stream  # token stream
     python examples/example_client.py --model llama --prompt "Hello" --logprobs 5   # per-token logprobs + top 5
+    python examples/example_client.py --model llama --prompt "Hello" --repetition-penalty 1.2 --logit-bias '{"50256": -100}'
 """
 
 import argparse
@@ -31,6 +32,8 @@ async def main():
     ap.add_argument("--temperature", type=float, default=0.0)
     ap.add_argument("--logprobs", type=int, default=None, metavar="N",
                     help="per-token logprobs of the raw distribution: 0 = the chosen token's, 1..20 = also the top N")
+    ap.add_argument("--repetition-penalty", type=float, default=None, help="> 0; 1.0 = off")
+    ap.add_argument("--logit-bias", default=None, metavar="JSON", help='{"token id": bias in [-100, 100]}, <= 300 entries')
     ap.add_argument("--request-key", default=None, help="session key for shard affinity")
     ap.add_argument("-n", type=int, default=1)
     ap.add_argument("--concurrency", type=int, default=1)
@@ -41,6 +44,10 @@ async def main():
         inputs = {"prompt": a.prompt, "max_tokens": a.max_tokens, "temperature": a.temperature}
         if a.logprobs is not None:
             inputs["logprobs"] = a.logprobs
+        if a.repetition_penalty is not None:
+            inputs["repetition_penalty"] = a.repetition_penalty
+        if a.logit_bias is not None:
+            inputs["logit_bias"] = json.loads(a.logit_bias)
     else:
         inputs = json.loads(a.inputs) if a.inputs else {"text": "hello"}
     c = InferenceClient(a.address)

@@ -287,7 +287,11 @@ class RemoteDecodeLink:
 def sampling_to_dict(sp: SamplingParams) -> Dict[str, Any]:
     return {"max_tokens": sp.max_tokens, "temperature": sp.temperature, "top_k": sp.top_k, "top_p": sp.top_p,
             "seed": sp.seed, "ignore_eos": sp.ignore_eos, "stop_token_ids": list(sp.stop_token_ids),
-            "logprobs": sp.logprobs, "prompt_logprobs": sp.prompt_logprobs}
+            "logprobs": sp.logprobs, "prompt_logprobs": sp.prompt_logprobs,
+            "presence_penalty": sp.presence_penalty, "frequency_penalty": sp.frequency_penalty,
+            "repetition_penalty": sp.repetition_penalty,
+            # string keys: the packet travels as JSON / msgpack maps, SamplingParams converts them back
+            "logit_bias": None if not sp.logit_bias else {str(k): v for k, v in sp.logit_bias.items()}}
 
 
 def packet_for_import(d: Dict[str, Any], device) -> KVPacket:

@@ -193,6 +193,7 @@ class LLMEngine:
         if prompt_ids and (min(prompt_ids) < 0 or max(prompt_ids) >= self.arch.vocab_size):
             # an out-of-range id would be an out-of-bounds embedding read on the GPU
             raise ValueError(f"prompt token id outside [0, {self.arch.vocab_size})")
+        self._check_logit_processing(sampling)
         if sampling.prompt_logprobs is not None:
             # every prompt row's logits are computed (keep_rows=None), which TP followers do not mirror and a
             # prefill worker's one-token export does not carry
@@ -215,6 +216,22 @@ class LLMEngine:
         self.stats["prompt_tokens"] += len(prompt_ids)
         return seq
 
+    def _check_logit_processing(self, sampling: SamplingParams) -> None:
+        """Penalties / logit_bias need per-sequence state on the runner's device (ops.logit_process): a runner whose
+        steps other ranks mirror does not keep it, and a bias id beyond the vocabulary names no logit."""
+        if not getattr(sampling, "processes_logits", False):
+            return
+        if not getattr(self.runner, "supports_logit_processing", False):
+            raise ValueError("presence_penalty / frequency_penalty / repetition_penalty / logit_bias are not "
+                             "supported on a tensor-parallel engine")
+        if sampling.logit_bias and max(sampling.logit_bias) >= self.arch.vocab_size:
+            raise ValueError(f"logit_bias token id outside [0, {self.arch.vocab_size})")
+
+    def _release_logit_state(self, seq: Sequence) -> None:
+        rel = getattr(self.runner, "release_logit_state", None)
+        if rel is not None:
+            rel(seq)
+
     def add_imported(self, packet, sampling: SamplingParams,
                      on_finish: Optional[Callable[[Sequence], None]] = None) -> Sequence:
         """Resume a sequence whose prompt KV was computed by a prefill worker:
@@ -236,6 +253,7 @@ class LLMEngine:
 
         if packet.block_size != self.cfg.block_size:
             raise ValueError("block size mismatch between prefill and decode workers")
+        self._check_logit_processing(sampling)
         self._last_import = time.perf_counter()
         seq = Sequence(packet.request_id, list(packet.prompt_ids), dataclasses.replace(sampling),
                        on_finish=on_finish, imported_kv=True)
@@ -302,7 +320,8 @@ class LLMEngine:
                 self.stats["steps"] += 1
                 return finished
         out: SchedulerOutput = self.scheduler.schedule()
-        for s in out.preempted:
+        for s in out.preempted:  # recomputed or swapped out: its logit-processing slot is rebuilt when it returns
+            self._release_logit_state(s)
             if s.status == SeqStatus.FINISHED:  # rejected at admission
                 s.finish_time = time.perf_counter()
                 finished.append(s)
@@ -615,6 +634,7 @@ class LLMEngine:
 
     def _complete(self, seq: Sequence) -> None:
         self.seqs.pop(seq.request_id, None)
+        self._release_logit_state(seq)
         self.stats["finished"] += 1
         prev = getattr(seq, "_preempted_outputs", None)
         if prev:
@@ -646,4 +666,5 @@ class LLMEngine:
         s["graphs"] = list(self.runner.graph_sizes)
         s["decode_weight_layout"] = self.decode_weight_layout
         s["logprob_launches"] = getattr(self.runner, "logprob_launches", 0)  # ops.token_logprobs launches
+        s["logit_process_launches"] = getattr(self.runner, "logit_process_launches", 0)  # ops.logit_process
         return s

@@ -21,6 +21,7 @@ import logging
 import os
 from typing import Dict, List, Optional, Sequence as Seq
 
+import numpy as np
 import torch
 
 from src import ops
@@ -62,6 +63,9 @@ class KVPool:
 
 class ModelRunner:
     mirrors_windows = False  # see supports_multistep
+    # penalties / logit_bias (SamplingParams.processes_logits): per-sequence state on this runner's device; a
+    # runner whose steps other ranks mirror would need mirrored state (TPModelRunner: False, the engine refuses)
+    supports_logit_processing = True
 
     def __init__(self, model: CausalLM, pool: KVPool, cfg: EngineConfig, max_model_len: int):
         self.model = model
@@ -144,6 +148,18 @@ class ModelRunner:
         self.last_logprobs = None         # the latest call's logprobs (take_logprobs), None when no row asked
         self.last_prompt_logprobs = None  # the latest prefill's prompt logprobs: {chunk index: (positions, ...)}
         self.d_adv_ticket = torch.zeros(1, dtype=i32, device=dev)  # sample_advance's row ticket (re-armed in-kernel)
+        # logit processing (ops.logit_process): row r of a step -> d_pen_slot[r] -> that sequence's state (-1: the
+        # row did not ask, or is padding). The tables themselves are allocated by _pen_alloc when first needed.
+        self.h_pen_slot = torch.full((self.max_seqs,), -1, dtype=i32, pin_memory=pin)
+        self.d_pen_slot = torch.full((self.max_seqs,), -1, dtype=i32, device=dev)
+        self.d_pen = None                       # (state, params, bias_cnt, bias_ids, bias_vals)
+        self._pen_slots: Dict[int, int] = {}    # seq_id -> slot
+        self._pen_free: List[int] = []
+        self._pen_ev = None                     # the latest upload from the pinned staging buffers
+        self.graphs_proc: Dict[int, torch.cuda.CUDAGraph] = {}  # the decode graphs with the ops.logit_process launch
+        self.graph_logits_proc: Dict[int, torch.Tensor] = {}
+        self.logit_process_launches = 0  # eager launches and processed graph replays
+        self._proc = False                      # the step being assembled has a row that asks (_fill_sampling)
         # decode attention streams K/V as once-read data (DIE_ATTN_KV_ONCE=0: the default cache policy, for A/B)
         self.kv_once = os.environ.get("DIE_ATTN_KV_ONCE", "1") != "0"
         if self.is_cuda:
@@ -182,10 +198,97 @@ class ModelRunner:
             self.d_cu[: n_seq + 1].copy_(self.h_cu[: n_seq + 1], non_blocking=nb)
             self.d_last[:n_seq].copy_(self.h_last[:n_seq], non_blocking=nb)
 
-    def _fill_sampling(self, seqs: Seq[Sequence], n_pad: int) -> bool:
+    # --------------------------------------------------- logit processing
+    def _pen_alloc(self) -> None:
+        """The per-sequence tables of ops.logit_process (max_seqs x vocab uint16 counts, parameters, bias lists)
+        and their pinned staging twins: at the first request that needs them — or at capture_graphs, whose
+        processed graphs bake the tables' addresses in."""
+        if self.d_pen is not None:
+            return
+        dev, pin, m = self.device, self.is_cuda, self.max_seqs
+        v, nb = self.model.arch.vocab_size, ops.LOGIT_BIAS_MAX
+        shapes = (((v,), torch.int16), ((4,), torch.float32), ((), torch.int32), ((nb,), torch.int32),
+                  ((nb,), torch.float32))
+        self.d_pen = tuple(torch.zeros((m,) + s, dtype=t, device=dev) for s, t in shapes)
+        self.h_pen = tuple(torch.zeros(s, dtype=t, pin_memory=pin) for s, t in shapes)
+        self._pen_free = list(range(m - 1, -1, -1))
+
+    @staticmethod
+    def _asks(seqs) -> bool:
+        """THE predicate of the processed decode path: one of the rows set a penalty or a bias."""
+        return any(s.sampling.processes_logits for s in seqs)
+
+    def _pen_build(self, seq: Sequence, all_outputs: bool) -> int:
+        """The sequence's slot. A sequence without one gets one and its state is built here from its token
+        lists, whatever brought it (a fresh prompt, a recompute, a swap-in, a disaggregated import): prompt bits
+        from the original prompt, counts from every output except the next decode step's input (the step counts
+        that one itself) — all_outputs (a prefill step's sampled rows, where no such input exists): every output,
+        and an existing slot is rebuilt (a decode row of a mixed step). The upload rides the compute stream, so
+        a slot reused after a queued window is rewritten behind that window."""
+        slot = self._pen_slots.get(seq.seq_id)
+        if slot is not None and not all_outputs:
+            return slot
+        self._pen_alloc()
+        if slot is None:
+            slot = self._pen_free.pop()
+            self._pen_slots[seq.seq_id] = slot
+        if self._pen_ev is not None:  # the staging buffers' previous upload
+            self._pen_ev.synchronize()
+        sp = seq.sampling
+        pre = list(getattr(seq, "_preempted_outputs", None) or ())
+        prompt = seq.prompt_ids[: len(seq.prompt_ids) - len(pre)]
+        outs = pre + (seq.output_ids if all_outputs else seq.output_ids[:-1])
+        h_row, h_par, h_cnt, h_bid, h_bval = self.h_pen
+        row = h_row.numpy().view(np.uint16)
+        row.fill(0)
+        if prompt:
+            row[np.asarray(prompt, dtype=np.int64)] = 0x8000
+        if outs:
+            ids, cnt = np.unique(np.asarray(outs, dtype=np.int64), return_counts=True)
+            row[ids] |= np.minimum(cnt, ops.LOGIT_COUNT_MAX).astype(np.uint16)
+        rp = np.float32(sp.repetition_penalty)
+        h_par.numpy()[:] = (rp, np.float32(1.0) / rp, sp.frequency_penalty, sp.presence_penalty)
+        bias = sp.logit_bias or {}
+        h_cnt.fill_(len(bias))
+        if bias:
+            h_bid.numpy()[:len(bias)] = list(bias.keys())
+            h_bval.numpy()[:len(bias)] = list(bias.values())
+        for h, d in zip(self.h_pen, self.d_pen):
+            d[slot].copy_(h, non_blocking=self.is_cuda)
+        if self.is_cuda:
+            self._pen_ev = torch.cuda.Event()
+            self._pen_ev.record(torch.cuda.current_stream(self.device))
+        return slot
+
+    def release_logit_state(self, seq: Sequence) -> None:
+        """Give the sequence's slot back (finish, abort, preemption, swap-out). A window still queued may go on
+        counting into it; whoever takes it next rewrites it behind that window (stream order)."""
+        slot = self._pen_slots.pop(seq.seq_id, None)
+        if slot is not None:
+            self._pen_free.append(slot)
+
+    def _fill_pen(self, seqs: Seq[Sequence], n_pad: int, all_outputs: bool) -> bool:
+        """d_pen_slot[:n_pad] for the step (-1: padding, and rows that did not ask); False and nothing written
+        when no row asks — the raw graphs never read it."""
+        if not self._asks(seqs):
+            return False
+        n = len(seqs)
+        ns = self.h_pen_slot.numpy()
+        ns[:n] = [self._pen_build(s, all_outputs) if s.sampling.processes_logits else -1 for s in seqs]
+        ns[n:n_pad] = -1
+        self.d_pen_slot[:n_pad].copy_(self.h_pen_slot[:n_pad], non_blocking=self.is_cuda)
+        return True
+
+    def _launch_logit_process(self, logits: torch.Tensor, n: int, count_ids=None, lm_part=None) -> None:
+        ops.logit_process(logits, self.d_pen_slot[:n], *self.d_pen, count_ids=count_ids, lm_part=lm_part)
+        self.logit_process_launches += 1
+
+    def _fill_sampling(self, seqs: Seq[Sequence], n_pad: int, prefill: bool = False) -> bool:
         """Write per-row sampling params; returns True when every row is greedy.
         Skips the H2D copies when the rows are all greedy (the kernel's greedy
-        path ignores them) — the common decode case costs nothing here."""
+        path ignores them) — the common decode case costs nothing here.
+        Also maps the rows that ask for logit processing to their slots (self._proc: one of them does)."""
+        self._proc = self._fill_pen(seqs, n_pad, all_outputs=prefill)
         greedy = all(s.sampling.greedy for s in seqs)
         if greedy:
             key = ("greedy", n_pad)
@@ -304,14 +407,15 @@ class ModelRunner:
         if nd and nd != n:
             nl = self.h_last.numpy()
             nl[:nd] = nl[done]
-        greedy = self._fill_sampling([chunks[i].seq for i in done], nd) if nd else True
+        greedy = self._fill_sampling([chunks[i].seq for i in done], nd, prefill=True) if nd else True
+        proc = bool(nd) and self._proc
         lp_top = self._lp_top(chunks[i].seq for i in done) if nd else -1
         plan = self._prompt_logprob_plan(chunks)
         self.last_logprobs = self.last_prompt_logprobs = None
         self._h2d(t, n, with_cu=True)
         max_q = max(c.length for c in chunks)
         self._sync_step(self.KIND_PREFILL, t, n, max_q, nd)
-        ids = self._exec_prefill(t, n, max_q, nd, greedy, kv_hook=kv_hook, lp_top=lp_top, plan=plan)
+        ids = self._exec_prefill(t, n, max_q, nd, greedy, kv_hook=kv_hook, lp_top=lp_top, plan=plan, process=proc)
         res: List[Optional[int]] = [None] * n
         if nd:
             if lp_top >= 0:
@@ -371,7 +475,7 @@ class ModelRunner:
         return res
 
     def _exec_prefill(self, t: int, n: int, max_q: int, nd: int, greedy: bool, kv_hook=None, lp_top: int = -1,
-                      plan: Optional[List[tuple]] = None) -> Optional[torch.Tensor]:
+                      plan: Optional[List[tuple]] = None, process: bool = False) -> Optional[torch.Tensor]:
         # the last layer runs only for the sampled rows (CausalLM._last_layer_kept_rows; DIE_PRUNE_LAST=0: all);
         # a step that scores prompt tokens (prompt_logprobs) needs every row
         keep = self.d_last[:nd] if self.prune_last and not plan else None
@@ -386,6 +490,8 @@ class ModelRunner:
         if hidden.shape[0] != nd or plan:  # a path that computed every row (e.g. the slab path of small steps)
             hidden = hidden.index_select(0, self.d_last[:nd])
         logits = self.model.compute_logits(hidden)
+        if process:  # penalties / bias of the rows that ask (their counts hold every output: nothing to count here)
+            self._launch_logit_process(logits, nd)
         ids = self._sample(logits, nd, greedy, self.d_out)
         if lp_top >= 0:  # the first generated token's logprobs (the leader only: followers have nothing to report)
             self._launch_logprobs(logits, ids, nd, 0, lp_top)
@@ -405,7 +511,7 @@ class ModelRunner:
             sc = self.dec_scratch
             ops.embed_sumsq(self.d_ids[:pad], self.model.embed, sc["ssp0"], out=sc["h_in"][:pad])
 
-    def _decode_forward(self, n: int) -> torch.Tensor:
+    def _decode_forward(self, n: int, process: bool = False) -> torch.Tensor:
         tail = self._fused_tail(n)
         meta = AttnMetadata(is_prefill=False, slot_mapping=self.d_slots[:n], block_tables=self.d_bt[:n],
                             ctx_lens=self.d_ctx[:n], max_ctx=self.max_model_len, part_o=self.part_o,
@@ -417,6 +523,10 @@ class ModelRunner:
         logits = self.model.compute_logits(hidden, argmax_parts=amax) if amax is not None else \
             self.model.compute_logits(hidden)
         self._last_logits = logits  # ops.token_logprobs reads them behind the step (capture_graphs keeps each graph's)
+        if process:
+            # between the LM head and the sampling tail: counts this step's input ids (the previous samples), rewrites
+            # the rows that ask in place and makes their greedy candidates agree with the rewritten rows
+            self._launch_logit_process(logits, n, count_ids=self.d_ids[:n], lm_part=amax[:n] if amax is not None else None)
         if not self.is_cuda:
             return ops.sample(logits, self.d_temp[:n], self.d_topk[:n], self.d_topp[:n], self.d_seed[:n],
                               self.d_step[:n])
@@ -458,6 +568,22 @@ class ModelRunner:
             # the shared pool from handing this memory to a graph captured later
             self.graph_logits[b] = self._last_logits
         torch.cuda.synchronize(self.device)
+        if self.supports_logit_processing:
+            # a second set with the ops.logit_process launch, for batches with a row that asks (_asks): the raw
+            # set above is captured first and stays what it was
+            self._pen_alloc()
+            self.d_pen_slot.fill_(-1)
+            for b in sizes:
+                self._decode_forward(b, process=True)
+            torch.cuda.synchronize(self.device)
+            for b in reversed(sizes):
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, pool=self._graph_pool):
+                    self._decode_forward(b, process=True)
+                self.graphs_proc[b] = g
+                self.graph_logits_proc[b] = self._last_logits
+            torch.cuda.synchronize(self.device)
+            self.logit_process_launches = 0  # warm-up and capture served no request
         self.graph_sizes = sizes
         logger.info("captured decode hipGraphs for batch sizes %s", sizes)
 
@@ -485,12 +611,14 @@ class ModelRunner:
             self.h_ctl[1] = n
             self.d_ctl.copy_(self.h_ctl, non_blocking=True)
         self._sync_step(self.KIND_DECODE, n, pad)
-        ids = self._exec_decode(n, pad)
+        proc = self._proc
+        ids = self._exec_decode(n, pad, proc)
         top = self._lp_top(seqs)
         self.last_logprobs = None
         if top < 0:
             return self._to_host(ids, n)
-        self._launch_logprobs(self.graph_logits[pad] if pad in self.graphs else self._last_logits, ids, n, 0, top)
+        glog = self.graph_logits_proc if proc else self.graph_logits
+        self._launch_logprobs(glog[pad] if pad in self.graphs else self._last_logits, ids, n, 0, top)
         self._lp_to_host(0, 1)
         toks = self._to_host(ids, n)
         self.last_logprobs = self._lp_read(0, 1, n, top)
@@ -527,7 +655,7 @@ class ModelRunner:
         self.d_ctl.copy_(self.h_ctl, non_blocking=True)
         self._sync_window(n, pad, k)
         top = self._lp_top(seqs)
-        self._replay_window(g, pad, n, k, 0, top)
+        self._replay_window(pad, n, k, 0, top, self._proc)
         self._queue_fault_readback()
         if k_next > 1:
             ev = torch.cuda.Event()
@@ -540,16 +668,21 @@ class ModelRunner:
         self.last_logprobs = self._lp_read(0, k, n, top) if top >= 0 else None
         return self.h_tokens[:k, :n].tolist()
 
-    def _replay_window(self, g, pad: int, n: int, k: int, base: int, top: int) -> None:
+    def _replay_window(self, pad: int, n: int, k: int, base: int, top: int, proc: bool) -> None:
         """k replays queued back to back, their tokens into rows [base, base + k); top >= 0 (a row asked for
         logprobs): one ops.token_logprobs launch behind each replay — it reads that step's logits and sampled ids
-        before the next replay overwrites them (stream order) — and the logprob rows come back with the tokens."""
+        before the next replay overwrites them (stream order) — and the logprob rows come back with the tokens.
+        proc (a row asks for logit processing, _asks): the graphs with the ops.logit_process launch and their
+        logits; otherwise the raw graphs, launch for launch as without the feature."""
+        g = (self.graphs_proc if proc else self.graphs)[pad]
+        if proc:
+            self.logit_process_launches += k
         if top < 0:
             for _ in range(k):
                 g.replay()
             self.h_tokens[base:base + k].copy_(self.d_tokens[base:base + k], non_blocking=True)
             return
-        logits = self.graph_logits[pad]
+        logits = (self.graph_logits_proc if proc else self.graph_logits)[pad]
         for i in range(k):
             g.replay()
             self._launch_logprobs(logits, self.d_out, n, base + i, top)
@@ -576,7 +709,7 @@ class ModelRunner:
         self.d_ctl[0:1].fill_(base)  # token rows [base, base + k)
         self._sync_continuation(par, pad, k, base)
         top = self._lp_top(seqs)
-        self._replay_window(self.graphs[pad], pad, n, k, base, top)
+        self._replay_window(pad, n, k, base, top, self._asks(seqs))
         self._queue_fault_readback()
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
@@ -602,9 +735,12 @@ class ModelRunner:
         self.last_logprobs = self._lp_read(b, b + k, n, w["lp_top"]) if w["lp_top"] >= 0 else None
         return self.h_tokens[b:b + k, :n].tolist()
 
-    def _exec_decode(self, n: int, pad: int) -> torch.Tensor:
+    def _exec_decode(self, n: int, pad: int, process: bool = False) -> torch.Tensor:
         g = self.graphs.get(pad)
         if g is not None:
+            if process:
+                g = self.graphs_proc[pad]
+                self.logit_process_launches += 1
             g.replay()
             return self.d_out
-        return self._decode_forward(n)
+        return self._decode_forward(n, process)

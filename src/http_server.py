@@ -7,7 +7,8 @@ coordinator's framed-RPC API. It holds no model state — every request becomes 
 
     POST /v1/completions   {"model", "prompt": str | [token ids], "max_tokens", "temperature",
                             "top_p", "top_k", "seed", "stop_token_ids", "ignore_eos", "stream",
-                            "logprobs": 0..20, "echo"}
+                            "logprobs": 0..20, "echo", "presence_penalty", "frequency_penalty" (-2..2),
+                            "repetition_penalty" (> 0), "logit_bias": {token id: -100..100}, <= 300 entries}
                            stream=true answers with server-sent events ("data: {...}" chunks,
                            then "data: [DONE]"), text and token ids per chunk.
                            logprobs=N: choice.logprobs = {"tokens", "token_logprobs", "top_logprobs":
@@ -22,6 +23,9 @@ coordinator's framed-RPC API. It holds no model state — every request becomes 
                            "logprob", "bytes", "top_logprobs": [{"token", "logprob", "bytes"}]}]}
     Stream chunks carry the same logprobs layouts for their delta; a request that does not ask gets
     "logprobs": null; an out-of-range value is a 400. Non-finite logprobs arrive as -9999.0.
+    Penalties and logit_bias (both endpoints) rewrite the logits on the GPU before sampling; a bad value is a
+    400, and so is a request that sets them on a model served tensor-parallel. With them, logprobs are those
+    of the processed distribution (before temperature / top-k / top-p); without them nothing changes.
     GET  /v1/models        the coordinator's registered models
     GET  /health           200 when the coordinator answers its health RPC
     GET  /metrics          Prometheus text format (requests, errors, latency, tokens)
@@ -41,9 +45,11 @@ from prometheus_client import CollectorRegistry, Counter, Histogram, generate_la
 from prometheus_client.exposition import CONTENT_TYPE_LATEST
 
 from src.client import InferenceClient
+from src.preproc import SamplingParams
 from src.utils import setup_logging
 
-_SAMPLING = ("max_tokens", "temperature", "top_p", "top_k", "seed", "stop_token_ids", "ignore_eos")
+_LOGIT_PROCESSING = ("presence_penalty", "frequency_penalty", "repetition_penalty", "logit_bias")
+_SAMPLING = ("max_tokens", "temperature", "top_p", "top_k", "seed", "stop_token_ids", "ignore_eos") + _LOGIT_PROCESSING
 _ROLES = ("system", "user", "assistant", "tool")
 MAX_LOGPROBS = 20
 
@@ -146,6 +152,8 @@ class Gateway:
             raise ValueError("prompt must be a string or a list of token ids")
         inp.update({k: body[k] for k in _SAMPLING if k in body and body[k] is not None})
         inp.setdefault("max_tokens", 16)
+        # ranges and types of the penalties / bias: refused here with a 400, not by a worker after routing
+        SamplingParams(**{k: inp[k] for k in _LOGIT_PROCESSING if k in inp})
         if chat:  # logprobs: bool, top_logprobs: int
             want = body.get("logprobs")
             if want is not None and not isinstance(want, bool):
@@ -259,7 +267,9 @@ class Gateway:
                 chat: bool = False) -> web.Response:
         if not rep.get("success"):
             self.m_err.labels(model).inc()
-            status = 404 if "not registered" in str(rep.get("error", "")) else 502
+            msg = str(rep.get("error", ""))
+            # a request the engine refused (e.g. penalties on a tensor-parallel engine) is the client's error
+            status = 404 if "not registered" in msg else 400 if "not supported on a" in msg else 502
             return web.json_response({"error": {"message": rep.get("error"), "type": "server_error"}}, status=status)
         out = rep["outputs"]
         if not isinstance(out, dict) or "token_ids" not in out:  # a mock model: pass its outputs through

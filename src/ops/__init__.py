@@ -258,6 +258,28 @@ def token_logprobs(logits: torch.Tensor, targets: torch.Tensor, top_n: int, out=
     return lp[:r], rank[:r], top_lp[:r, :top_n], top_id[:r, :top_n]
 
 
+LOGIT_BIAS_MAX = 300  # logit_bias entries per request (launchers.h; the OpenAI API's cap)
+LOGIT_COUNT_MAX = ref.LOGIT_COUNT_MAX
+
+
+def logit_process(logits: torch.Tensor, slot: torch.Tensor, state: torch.Tensor, params: torch.Tensor,
+                  bias_cnt: torch.Tensor, bias_ids: torch.Tensor, bias_vals: torch.Tensor,
+                  count_ids: Optional[torch.Tensor] = None, lm_part: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Repetition / frequency / presence penalties and logit_bias on ``logits`` [rows, vocab] bf16 IN PLACE, before
+    the sampler reads them (:func:`reference.logit_process` is the per-entry contract). Row r uses the state of
+    ``slot[r]`` (int32; < 0: the row is left untouched): ``state`` int16 [slots, vocab] (as uint16: bit 15 = the
+    token occurs in the prompt, bits 0-14 = how often it was generated, saturating at 32767), ``params`` fp32
+    [slots, 4] = (rp, fp32(1 / rp), freq, pres), ``bias_cnt`` int32 [slots] and ``bias_ids`` int32 / ``bias_vals``
+    fp32 [slots, <= 300] with unique ids. ``count_ids`` int64 [rows]: the step's input tokens (the previous
+    samples), added to the counts first. ``lm_part`` [rows, parts, 2] int32: the LM head's greedy candidates of
+    these rows, overwritten with the processed row's (max, lowest index) so that :func:`sample` /
+    :func:`sample_advance` with ``lm_part`` return the processed argmax."""
+    if not logits.is_cuda:
+        return ref.logit_process_rows(logits, slot, state, params, bias_cnt, bias_ids, bias_vals, count_ids, lm_part)
+    _kern().logit_process(logits, slot, state, params, bias_cnt, bias_ids, bias_vals, count_ids, lm_part)
+    return logits
+
+
 def sample_advance(logits, temperature, top_k, top_p, seeds, steps, out, lm_part, ids, pos, ctx, slots, bt, tokens,
                    cnt, n_real, block_size: int, ticket, embed=None) -> torch.Tensor:
     """:func:`sample` from the LM head's candidates (``lm_part``) fused with :func:`decode_advance`: every row's

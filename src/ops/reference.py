@@ -165,6 +165,65 @@ def token_logprobs(logits: torch.Tensor, targets: torch.Tensor, top_n: int):
     return lp, rank, lsm.gather(1, top_id).float(), top_id.int()
 
 
+LOGIT_COUNT_MAX = 32767  # the output count's 15 bits (bit 15 of a state entry: "in the prompt")
+
+
+def logit_process(logits: torch.Tensor, in_prompt: torch.Tensor, counts: torch.Tensor, rp: float, inv_rp: float,
+                  freq: float, pres: float, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Penalties and logit_bias on bf16 logits [..., V] (the contract of csrc/kernels/logit_process.hip): per
+    entry, one individually rounded fp32 operation per step —
+    x = float(z) + bias; if in the prompt or count > 0: x = x * inv_rp if x > 0 else x * rp;
+    x = x - freq * float(count); if count > 0: x = x - pres; one rounding to bf16.
+    in_prompt bool [..., V], counts integer [..., V], bias fp32 [..., V] or None; inv_rp = fp32(1 / rp)."""
+    f32 = torch.float32
+    x = logits.to(f32)
+    b = torch.zeros_like(x) if bias is None else bias.to(f32)
+    x = x + b
+    c = counts.to(torch.int64).clamp(max=LOGIT_COUNT_MAX)
+    seen = in_prompt.to(torch.bool) | (c > 0)
+    t_rp, t_inv = torch.tensor(rp, dtype=f32), torch.tensor(inv_rp, dtype=f32)
+    x = torch.where(seen, torch.where(x > 0, x * t_inv, x * t_rp), x)
+    x = x - torch.tensor(freq, dtype=f32) * c.to(f32)
+    x = torch.where(c > 0, x - torch.tensor(pres, dtype=f32), x)
+    return x.to(torch.bfloat16)
+
+
+def logit_process_rows(logits, slot, state, params, bias_cnt, bias_ids, bias_vals, count_ids=None, lm_part=None):
+    """ops.logit_process on host tensors: the kernel's arguments (state int16 [slots, V] with bit 15 = in the
+    prompt and bits 0-14 = output count, params [slots, 4] = rp, 1/rp, freq, pres, the per-slot bias lists),
+    rows rewritten in place, count_ids counted first (saturating), lm_part candidates overwritten."""
+    vocab = logits.shape[1]
+    for r in range(logits.shape[0]):
+        s = int(slot[r])
+        if s < 0 or s >= state.shape[0]:
+            continue
+        st = state[s].to(torch.int32) & 0xffff
+        if count_ids is not None:
+            t = int(count_ids[r])
+            if 0 <= t < vocab:
+                c = int(st[t]) & 0x7fff
+                v = (int(st[t]) & 0x8000) | min(c + 1, LOGIT_COUNT_MAX)
+                st[t] = v
+                state[s, t] = v - 65536 if v >= 32768 else v
+        bias = None
+        nb = min(int(bias_cnt[s]), bias_ids.shape[1])
+        if nb > 0:
+            bias = torch.zeros(vocab, dtype=torch.float32)
+            ids = bias_ids[s, :nb].long()
+            ok = (ids >= 0) & (ids < vocab)
+            bias[ids[ok]] = bias_vals[s, :nb][ok].float()
+        rp, inv_rp, freq, pres = (float(v) for v in params[s])
+        # z is a bf16 logit by contract (an fp32 host model's row is rounded to it first)
+        logits[r] = logit_process(logits[r].to(torch.bfloat16), (st & 0x8000) != 0, st & 0x7fff, rp, inv_rp, freq, pres, bias)
+        if lm_part is not None:
+            v, i = torch.max(logits[r].float(), 0)  # first maximal index
+            lm_part[r, :, 0] = torch.tensor(float("-inf")).view(torch.int32)
+            lm_part[r, :, 1] = 0x7fffffff
+            lm_part[r, 0, 0] = v.view(torch.int32)
+            lm_part[r, 0, 1] = int(i)
+    return logits
+
+
 def topk_softmax(gating: torch.Tensor, k: int, renorm: bool = True):
     p = torch.softmax(gating.float(), dim=-1)
     w, ids = torch.topk(p, k, dim=-1)

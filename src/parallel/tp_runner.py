@@ -70,6 +70,8 @@ class TPModelRunner(ModelRunner):
     # replays its captured graph k times and advances its own inputs on the device from the all-gathered
     # logits' samples (identical on every rank), so a window costs one host round trip on the leader only
     mirrors_windows = True
+    # followers sample too: penalties / logit_bias would need every rank to mirror the per-sequence state
+    supports_logit_processing = False
     HDR = 8
 
     def __init__(self, model: CausalLM, pool: KVPool, cfg: EngineConfig, max_model_len: int):

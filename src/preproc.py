@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import asyncio
 import concurrent.futures as cf
+import math
 import os
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional, Sequence, Tuple
@@ -61,6 +62,13 @@ def load_tokenizer(path: Optional[str] = None, vocab_size: int = 128256):
 
 
 MAX_LOGPROBS = 20  # the OpenAI chat API's cap on top_logprobs
+MAX_LOGIT_BIAS = 300  # the OpenAI API's cap on logit_bias entries (launchers.h LOGIT_BIAS_MAX)
+
+
+def _finite_number(v: Any, name: str) -> float:
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+        raise ValueError(f"{name} must be a finite number")
+    return float(v)
 
 
 @dataclass
@@ -76,6 +84,15 @@ class SamplingParams:
     # 0 = the chosen token's logprob and rank only, 1..20 = also that many most likely tokens
     logprobs: Optional[int] = None
     prompt_logprobs: Optional[int] = None  # the same, for the prompt tokens
+    # logit processing (ops.logit_process, applied to the bf16 logits row before anything else reads it):
+    # OpenAI's presence / frequency penalties over the generated tokens, the multiplicative repetition penalty
+    # over prompt and generated tokens (1.0 = off) and logit_bias {token id: value added to its logit}.
+    # For a request that sets any of them, logprobs are computed from the PROCESSED row (still before
+    # temperature / top-k / top-p); a request that sets none keeps exactly the raw-distribution meaning above.
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    repetition_penalty: float = 1.0
+    logit_bias: Optional[Dict[int, float]] = None
 
     def __post_init__(self):
         if self.max_tokens < 1:
@@ -92,10 +109,45 @@ class SamplingParams:
                 continue
             if isinstance(v, bool) or not isinstance(v, int) or not (0 <= v <= MAX_LOGPROBS):
                 raise ValueError(f"{name} must be None or an integer in [0, {MAX_LOGPROBS}]")
+        for name in ("presence_penalty", "frequency_penalty"):
+            v = _finite_number(getattr(self, name), name)
+            if not (-2.0 <= v <= 2.0):
+                raise ValueError(f"{name} must be in [-2, 2]")
+            setattr(self, name, v)
+        self.repetition_penalty = _finite_number(self.repetition_penalty, "repetition_penalty")
+        if not self.repetition_penalty > 0.0:
+            raise ValueError("repetition_penalty must be > 0")
+        if self.logit_bias is not None:
+            if not isinstance(self.logit_bias, dict):
+                raise ValueError("logit_bias must be an object {token id: bias}")
+            if len(self.logit_bias) > MAX_LOGIT_BIAS:
+                raise ValueError(f"logit_bias holds at most {MAX_LOGIT_BIAS} entries")
+            bias: Dict[int, float] = {}
+            for k, v in self.logit_bias.items():
+                if isinstance(k, str):  # JSON object keys are strings
+                    try:
+                        k = int(k.strip())
+                    except ValueError:
+                        raise ValueError(f"logit_bias key {k!r} is not a token id") from None
+                if isinstance(k, bool) or not isinstance(k, int) or k < 0:
+                    raise ValueError(f"logit_bias key {k!r} is not a token id")
+                v = _finite_number(v, "logit_bias value")
+                if not (-100.0 <= v <= 100.0):
+                    raise ValueError("logit_bias values must be in [-100, 100]")
+                if k in bias:
+                    raise ValueError(f"logit_bias names token {k} twice")
+                bias[k] = v
+            self.logit_bias = bias or None
 
     @property
     def greedy(self) -> bool:
         return self.temperature == 0.0 or self.top_k == 1
+
+    @property
+    def processes_logits(self) -> bool:
+        """Any penalty or bias set: the request's rows go through ops.logit_process before sampling."""
+        return bool(self.presence_penalty != 0.0 or self.frequency_penalty != 0.0 or self.repetition_penalty != 1.0
+                    or self.logit_bias)
 
 
 @dataclass
@@ -107,7 +159,8 @@ class GenerationInputs:
 
 
 _SAMPLING_KEYS = ("max_tokens", "temperature", "top_k", "top_p", "seed", "ignore_eos", "stop_token_ids",
-                  "logprobs", "prompt_logprobs")
+                  "logprobs", "prompt_logprobs", "presence_penalty", "frequency_penalty", "repetition_penalty",
+                  "logit_bias")
 
 
 def normalize_request(inputs: Any, tokenizer=None, max_model_len: Optional[int] = None) -> GenerationInputs:
@@ -133,6 +186,8 @@ def normalize_request(inputs: Any, tokenizer=None, max_model_len: Optional[int] 
     if vs and (min(ids) < 0 or max(ids) >= vs):
         raise ValueError("prompt token id out of vocabulary range")
     sp = SamplingParams(**{k: inputs[k] for k in _SAMPLING_KEYS if k in inputs})
+    if vs and sp.logit_bias and max(sp.logit_bias) >= vs:
+        raise ValueError("logit_bias token id out of vocabulary range")
     if max_model_len is not None and len(ids) + sp.max_tokens > max_model_len:
         raise ValueError(f"prompt ({len(ids)}) + max_tokens ({sp.max_tokens}) exceeds max_model_len {max_model_len}")
     return GenerationInputs(prompt_token_ids=ids, sampling=sp, prompt=prompt,
