@@ -421,6 +421,51 @@ void logit_process(Tensor logits, Tensor slot, Tensor state, Tensor params, Tens
                                     bias_vals.data_ptr<float>(), (int)bias_ids.size(1), cp, lp, lparts, cur_stream()));
 }
 
+// Constrained decoding on logits [rows, vocab] in place (token_guide.hip). slot int32 [>= rows]; desc int32 [slots,
+// 4]; rowptr int32 [R]; edges int32 [E, 2]; cur / err int32 [slots]; advance_ids int64 [>= rows] and lm_part int32
+// [>= rows, parts, 2] optional. The launcher itself refuses vocab % 8 != 0, a bad stride and oversized arenas.
+void token_guide(Tensor logits, Tensor slot, Tensor desc, Tensor rowptr, Tensor edges, Tensor cur, Tensor err,
+                 c10::optional<Tensor> advance_ids, c10::optional<Tensor> lm_part) {
+  CHK_CUDA(logits);
+  CHK_BF16(logits);
+  check_rows(logits, "logits");
+  const int64_t rows = logits.size(0), vocab = logits.size(1);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0, "token_guide: logits must be 16-B aligned");
+  TORCH_CHECK(slot.is_cuda() && slot.scalar_type() == at::kInt && slot.is_contiguous() && slot.numel() >= rows,
+              "token_guide: slot int32 [rows]");
+  TORCH_CHECK(desc.is_cuda() && desc.scalar_type() == at::kInt && desc.is_contiguous() && desc.dim() == 2 &&
+                  desc.size(1) == 4 && reinterpret_cast<uintptr_t>(desc.data_ptr()) % 16 == 0,
+              "token_guide: desc int32 [slots, 4]");
+  const int64_t slots = desc.size(0);
+  TORCH_CHECK(rowptr.is_cuda() && rowptr.scalar_type() == at::kInt && rowptr.is_contiguous() && rowptr.dim() == 1,
+              "token_guide: rowptr int32 [R]");
+  TORCH_CHECK(edges.is_cuda() && edges.scalar_type() == at::kInt && edges.is_contiguous() && edges.dim() == 2 &&
+                  edges.size(1) == 2 && reinterpret_cast<uintptr_t>(edges.data_ptr()) % 8 == 0,
+              "token_guide: edges int32 [E, 2]");
+  TORCH_CHECK(cur.is_cuda() && cur.scalar_type() == at::kInt && cur.is_contiguous() && cur.numel() >= slots &&
+                  err.is_cuda() && err.scalar_type() == at::kInt && err.is_contiguous() && err.numel() >= slots,
+              "token_guide: cur / err int32 [slots]");
+  const int64_t* ap = nullptr;
+  if (advance_ids.has_value()) {
+    TORCH_CHECK(advance_ids->is_cuda() && advance_ids->scalar_type() == at::kLong && advance_ids->is_contiguous() &&
+                    advance_ids->numel() >= rows, "token_guide: advance_ids int64 [rows]");
+    ap = advance_ids->data_ptr<int64_t>();
+  }
+  uint32_t* lp = nullptr;
+  int lparts = 0;
+  if (lm_part.has_value()) {
+    TORCH_CHECK(lm_part->is_cuda() && lm_part->scalar_type() == at::kInt && lm_part->dim() == 3 &&
+                    lm_part->size(0) >= rows && lm_part->size(2) == 2 && lm_part->is_contiguous(),
+                "token_guide: lm_part [rows, parts, 2] int32");
+    lp = reinterpret_cast<uint32_t*>(lm_part->data_ptr<int>());
+    lparts = (int)lm_part->size(1);
+  }
+  HIP_OK(die::launch_token_guide(bf(logits), logits.stride(0), (int)rows, (int)vocab, slot.data_ptr<int>(), (int)slots,
+                                  desc.data_ptr<int>(), rowptr.data_ptr<int>(), rowptr.numel(), edges.data_ptr<int>(),
+                                  edges.size(0), cur.data_ptr<int>(), err.data_ptr<int>(), ap, lp, lparts,
+                                  cur_stream()));
+}
+
 // A decode step's sampling from the LM head's candidates (sample(..., lm_part)) that also advances the step's
 // inputs as decode_advance does (ids / pos / ctx / slots / step, the window's token row, the step counter cnt[0]),
 // one workgroup per row; ticket: int32 [1], zero, re-armed by the kernel.
@@ -1111,6 +1156,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("copy_blocks", &copy_blocks);
   m.def("token_logprobs", &token_logprobs);
   m.def("logit_process", &logit_process);
+  m.def("token_guide", &token_guide);
   m.def("sample_advance", &sample_advance);
   m.def("move_blocks", &move_blocks);
   m.def("gather_blocks_rows", &gather_blocks_rows);

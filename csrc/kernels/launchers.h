@@ -121,6 +121,24 @@ hipError_t launch_logit_process(bf16_t* logits, int64_t stride, int rows, int vo
                                 const float* bias_vals, int bias_cap, const int64_t* count_ids, uint32_t* lm_part,
                                 int lm_parts, hipStream_t s);
 
+// constrained decoding on rows [rows, stride] in place (token_guide.hip): row r -> slot[r] (< 0 or >= num_slots:
+// untouched); desc [num_slots, 4] = (state_base, n_states, edge_base, n_edges) into the arenas rowptr [rowptr_len]
+// and edges [edges_len, 2] = (tok, next); cur / err [num_slots]; advance_ids (optional) [rows]: this step's input
+// ids, the state advances over them first; lm_part (optional) [rows, lm_parts, 2]: the row's greedy candidates,
+// rewritten to the best allowed entry. A barred entry becomes bf16 -inf, an allowed one keeps its bits.
+// hipErrorInvalidValue for vocab % 8 != 0, stride < vocab or % 8, a null table, an arena above the sizes below or
+// a vocabulary whose bitmap exceeds 48 KiB.
+constexpr int GUIDE_MAX_STATES = 16384;        // per request (src/guided.py)
+constexpr int GUIDE_MAX_EDGES = 262144;        // per request: twice the largest vocabulary
+constexpr int GUIDE_ROWPTR_ARENA = 262144;     // int32 entries
+constexpr int GUIDE_EDGE_ARENA = 4194304;      // (tok, next) pairs: 32 MiB
+constexpr int GUIDE_ERR_NO_EDGE = 1;           // err bits: the advance token has no edge in the current state
+constexpr int GUIDE_ERR_TABLE = 2;             // a descriptor, state, row pointer or edge outside its bounds
+hipError_t launch_token_guide(bf16_t* logits, int64_t stride, int rows, int vocab, const int* slot, int num_slots,
+                              const int* desc, const int* rowptr, int64_t rowptr_len, const int* edges,
+                              int64_t edges_len, int* cur, int* err, const int64_t* advance_ids, uint32_t* lm_part,
+                              int lm_parts, hipStream_t s);
+
 hipError_t launch_topk_softmax(float* w, int* ids, const bf16_t* gating, int T, int E, int K, bool renorm,
                                hipStream_t s);
 hipError_t launch_moe_route(float* w, int* ids, const bf16_t* x, int64_t ldx, const bf16_t* wg, int T, int H, int E,

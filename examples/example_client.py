@@ -7,6 +7,8 @@
     python examples/example_client.py --model llama --prompt "Hello" --max-tokens 64 --stream  # token stream
     python examples/example_client.py --model llama --prompt "Hello" --logprobs 5   # per-token logprobs + top 5
     python examples/example_client.py --model llama --prompt "Hello" --repetition-penalty 1.2 --logit-bias '{"50256": -100}'
+    python examples/example_client.py --model llama --prompt "Is water wet? " --guided-choice yes no
+    python examples/example_client.py --model llama --prompt "A date: " --guided-regex '\d{4}-\d{2}-\d{2}'
 """
 
 import argparse
@@ -34,6 +36,10 @@ async def main():
                     help="per-token logprobs of the raw distribution: 0 = the chosen token's, 1..20 = also the top N")
     ap.add_argument("--repetition-penalty", type=float, default=None, help="> 0; 1.0 = off")
     ap.add_argument("--logit-bias", default=None, metavar="JSON", help='{"token id": bias in [-100, 100]}, <= 300 entries')
+    ap.add_argument("--guided-choice", nargs="+", default=None, metavar="TEXT",
+                    help="the output is exactly one of these strings, then EOS")
+    ap.add_argument("--guided-regex", default=None, metavar="PATTERN",
+                    help="the output fully matches this pattern (the byte-level subset of src/guided.py), then EOS")
     ap.add_argument("--request-key", default=None, help="session key for shard affinity")
     ap.add_argument("-n", type=int, default=1)
     ap.add_argument("--concurrency", type=int, default=1)
@@ -48,6 +54,10 @@ async def main():
             inputs["repetition_penalty"] = a.repetition_penalty
         if a.logit_bias is not None:
             inputs["logit_bias"] = json.loads(a.logit_bias)
+        if a.guided_choice is not None:
+            inputs["guided_choice"] = a.guided_choice
+        if a.guided_regex is not None:
+            inputs["guided_regex"] = a.guided_regex
     else:
         inputs = json.loads(a.inputs) if a.inputs else {"text": "hello"}
     c = InferenceClient(a.address)

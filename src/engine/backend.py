@@ -73,6 +73,8 @@ class LLMBackend:
         self.tokenizer = load_tokenizer(config.model_path or None, engine.arch.vocab_size)
         if not isinstance(self.tokenizer, ByteTokenizer):
             engine.eos_token_id = getattr(self.tokenizer, "eos_token_id", engine.eos_token_id)
+            # no byte table for a multi-byte vocabulary yet: the engine refuses guided_regex
+            engine.token_bytes = None
         self.async_engine = AsyncLLMEngine(engine, name=config.model_name)
         self.role = config.role
         self._decode_link = None

@@ -291,7 +291,10 @@ def sampling_to_dict(sp: SamplingParams) -> Dict[str, Any]:
             "presence_penalty": sp.presence_penalty, "frequency_penalty": sp.frequency_penalty,
             "repetition_penalty": sp.repetition_penalty,
             # string keys: the packet travels as JSON / msgpack maps, SamplingParams converts them back
-            "logit_bias": None if not sp.logit_bias else {str(k): v for k, v in sp.logit_bias.items()}}
+            "logit_bias": None if not sp.logit_bias else {str(k): v for k, v in sp.logit_bias.items()},
+            "allowed_token_ids": None if sp.allowed_token_ids is None else list(sp.allowed_token_ids),
+            "guided_choice": None if sp.guided_choice is None else [list(c) for c in sp.guided_choice],
+            "guided_regex": sp.guided_regex}
 
 
 def packet_for_import(d: Dict[str, Any], device) -> KVPacket:

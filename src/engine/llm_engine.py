@@ -28,6 +28,7 @@ from src.config import EngineConfig
 from src.engine.block_manager import KVBlockManager
 from src.engine.model_runner import KVPool, ModelRunner
 from src.engine.scheduler import Scheduler, SchedulerOutput
+from src.guided import byte_table, compile_guide
 from src.engine.sequence import Sequence, SeqStatus
 from src.models.llama import CausalLM
 from src.models.presets import ArchConfig, get_preset
@@ -105,6 +106,10 @@ class LLMEngine:
         self.device = model.device
         self.max_model_len = min(max_model_len, model.max_position)
         self.eos_token_id = eos_token_id
+        # id -> bytes | None, what guided_regex lifts its byte automaton to tokens through. The default is the
+        # byte-level tokenizer's (ids 3..258 are one byte each); whoever pairs the engine with another tokenizer
+        # sets it to that tokenizer's table, or to None (guided_regex is then refused)
+        self.token_bytes = byte_table(model.arch.vocab_size)
         if self.device.type == "cuda" and getattr(cfg, "tuned_gemm_table", True):
             from src.ops.gemm_table import enable_prefill_gemm_table
 
@@ -194,6 +199,7 @@ class LLMEngine:
             # an out-of-range id would be an out-of-bounds embedding read on the GPU
             raise ValueError(f"prompt token id outside [0, {self.arch.vocab_size})")
         self._check_logit_processing(sampling)
+        guide = self._compile_guide(sampling)
         if sampling.prompt_logprobs is not None:
             # every prompt row's logits are computed (keep_rows=None), which TP followers do not mirror and a
             # prefill worker's one-token export does not carry
@@ -206,6 +212,8 @@ class LLMEngine:
         if sampling.prompt_logprobs is not None:
             seq.prompt_logprobs_out = [None] * len(prompt_ids)
         seq._on_token_entry = _takes_entry(on_token)  # type: ignore[attr-defined]
+        if guide is not None:  # a ValueError when the arena has no room: nothing was registered yet
+            self.runner.guide_admit(seq, guide)
         if export_kv:  # disaggregated prefill: stop after the first token and hand the prompt KV over
             seq.sampling.max_tokens = 1
             seq.export_kv = True  # type: ignore[attr-defined]
@@ -227,10 +235,39 @@ class LLMEngine:
         if sampling.logit_bias and max(sampling.logit_bias) >= self.arch.vocab_size:
             raise ValueError(f"logit_bias token id outside [0, {self.arch.vocab_size})")
 
-    def _release_logit_state(self, seq: Sequence) -> None:
+    def _compile_guide(self, sampling: SamplingParams):
+        """The token automaton of a guided request (None: not guided), or the ValueError that refuses it: a runner
+        without the device state, an id beyond the vocabulary, guided_choice / guided_regex without an
+        end-of-sequence token or with ignore_eos, guided_regex without a byte table, an automaton over the caps,
+        a pattern that matches nothing."""
+        if not getattr(sampling, "guided", False):
+            return None
+        if not getattr(self.runner, "supports_token_guide", False):
+            raise ValueError("allowed_token_ids / guided_choice / guided_regex are not supported on a "
+                             "tensor-parallel engine")
+        return compile_guide(sampling, self.arch.vocab_size, self.eos_token_id, self.token_bytes)
+
+    def _release_logit_state(self, seq: Sequence, preempted: bool = False) -> None:
         rel = getattr(self.runner, "release_logit_state", None)
         if rel is not None:
             rel(seq)
+        rel = getattr(self.runner, "release_guide_state", None)
+        if rel is not None:  # a preempted sequence returns: it keeps its reference to the arena region
+            rel(seq, keep_region=preempted)
+
+    def _fail_guide_errors(self, seqs, finished: List[Sequence]) -> None:
+        """A guided sequence whose device-side automaton reported an error (no edge for a sampled token, a table
+        out of bounds: ops.GUIDE_ERR_*) ends with finish_reason "error": its later tokens would not be
+        constrained."""
+        errs = getattr(self.runner, "guide_errors", None)
+        for seq, bits in (errs(seqs) if errs is not None else ()):
+            if seq.status == SeqStatus.FINISHED:
+                continue
+            logger.error("request %s: constrained decoding failed on the device (error bits %d)", seq.request_id, bits)
+            self.stats["guide_errors"] = self.stats.get("guide_errors", 0) + 1
+            self.scheduler.finish(seq, "error")
+            finished.append(seq)
+            self._complete(seq)
 
     def add_imported(self, packet, sampling: SamplingParams,
                      on_finish: Optional[Callable[[Sequence], None]] = None) -> Sequence:
@@ -254,6 +291,7 @@ class LLMEngine:
         if packet.block_size != self.cfg.block_size:
             raise ValueError("block size mismatch between prefill and decode workers")
         self._check_logit_processing(sampling)
+        guide = self._compile_guide(sampling)
         self._last_import = time.perf_counter()
         seq = Sequence(packet.request_id, list(packet.prompt_ids), dataclasses.replace(sampling),
                        on_finish=on_finish, imported_kv=True)
@@ -279,6 +317,12 @@ class LLMEngine:
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(packet.ready)
             packet.kv.record_stream(cur)
+        if guide is not None:
+            try:
+                self.runner.guide_admit(seq, guide)
+            except ValueError:
+                self.blocks.free(seq)
+                raise
         import_blocks(self.pool.planes(), seq.block_table[:nb], packet.kv)
         seq.num_computed = seq.prompt_len
         self.seqs[seq.request_id] = seq
@@ -315,13 +359,14 @@ class LLMEngine:
             now = time.perf_counter()
             self.stats["decode_time"] += now - t0
             self._apply_window(seqs, toks_k, finished, self._take_logprobs())
+            self._fail_guide_errors(seqs, finished)
             if self.runner.inflight is not None:
                 self.stats["queued_windows"] = self.stats.get("queued_windows", 0) + 1
                 self.stats["steps"] += 1
                 return finished
         out: SchedulerOutput = self.scheduler.schedule()
         for s in out.preempted:  # recomputed or swapped out: its logit-processing slot is rebuilt when it returns
-            self._release_logit_state(s)
+            self._release_logit_state(s, preempted=s.status != SeqStatus.FINISHED)
             if s.status == SeqStatus.FINISHED:  # rejected at admission
                 s.finish_time = time.perf_counter()
                 finished.append(s)
@@ -371,6 +416,7 @@ class LLMEngine:
                 if seq.first_token_time is None:
                     seq.first_token_time = now
                 self._append(seq, tok, finished, logprob_entry(lp0, i, seq.sampling.logprobs))
+            self._fail_guide_errors([c.seq for c in chunks], finished)
         else:
             k = self._decode_window(out.decode)
             if k > 1:
@@ -383,6 +429,7 @@ class LLMEngine:
             self.stats["decode_time"] += now - t0
             self._step_est = 0.8 * self._step_est + 0.2 * (now - t0) / max(1, len(toks_k))
             self._apply_window(out.decode, toks_k, finished, self._take_logprobs())
+            self._fail_guide_errors(out.decode, finished)
         self.stats["steps"] += 1
         if self.cfg.kv_block_ttl_s:
             self.blocks.evict_expired()
@@ -667,4 +714,7 @@ class LLMEngine:
         s["decode_weight_layout"] = self.decode_weight_layout
         s["logprob_launches"] = getattr(self.runner, "logprob_launches", 0)  # ops.token_logprobs launches
         s["logit_process_launches"] = getattr(self.runner, "logit_process_launches", 0)  # ops.logit_process
+        s["token_guide_launches"] = getattr(self.runner, "token_guide_launches", 0)  # ops.token_guide
+        used = getattr(self.runner, "guide_arena_edges_used", None)
+        s["guide_arena_edges_used"] = used() if used is not None else 0  # edges of the automata held on the device
         return s

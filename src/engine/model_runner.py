@@ -17,6 +17,7 @@ Model runner: turns a scheduled step into GPU work on one HIP stream.
 from __future__ import annotations
 
 import bisect
+import collections
 import logging
 import os
 from typing import Dict, List, Optional, Sequence as Seq
@@ -29,6 +30,7 @@ from src.config import EngineConfig
 from src.engine.block_manager import native_runtime
 from src.engine.scheduler import PrefillChunk
 from src.engine.sequence import Sequence
+from src.guided import Automaton, FirstFit, walk
 from src.models.llama import AttnMetadata, CausalLM
 
 logger = logging.getLogger(__name__)
@@ -66,6 +68,8 @@ class ModelRunner:
     # penalties / logit_bias (SamplingParams.processes_logits): per-sequence state on this runner's device; a
     # runner whose steps other ranks mirror would need mirrored state (TPModelRunner: False, the engine refuses)
     supports_logit_processing = True
+    # constrained decoding (SamplingParams.guided): the automaton's state lives on this runner's device too
+    supports_token_guide = True
 
     def __init__(self, model: CausalLM, pool: KVPool, cfg: EngineConfig, max_model_len: int):
         self.model = model
@@ -160,6 +164,25 @@ class ModelRunner:
         self.graph_logits_proc: Dict[int, torch.Tensor] = {}
         self.logit_process_launches = 0  # eager launches and processed graph replays
         self._proc = False                      # the step being assembled has a row that asks (_fill_sampling)
+        # constrained decoding (ops.token_guide): row r -> d_guide_slot[r] -> that sequence's descriptor, current
+        # state and error word; the automata themselves lie in two arenas shared by all slots, one region per
+        # distinct spec (ref-counted; unreferenced regions stay until their room is needed). _guide_alloc
+        # allocates the tables when first needed.
+        self.h_guide_slot = torch.full((self.max_seqs,), -1, dtype=i32, pin_memory=pin)
+        self.d_guide_slot = torch.full((self.max_seqs,), -1, dtype=i32, device=dev)
+        self.d_guide = None                     # (desc, rowptr, edges, cur, err)
+        self._guide_slots: Dict[int, int] = {}  # seq_id -> slot
+        self._guide_free: List[int] = []
+        self._guide_refs: Dict[int, tuple] = {}  # seq_id -> the spec key of the region it references
+        self._guide_regions: Dict[tuple, dict] = {}  # spec key -> {"auto", "rp", "ed", "refs"}
+        self._guide_lru: "collections.OrderedDict[tuple, None]" = collections.OrderedDict()  # unreferenced regions
+        self._guide_rp: Optional[FirstFit] = None
+        self._guide_ed: Optional[FirstFit] = None
+        self._guide_ev = None
+        self.graphs_guided: Dict[int, torch.cuda.CUDAGraph] = {}  # LM head -> logit_process -> token_guide -> tail
+        self.graph_logits_guided: Dict[int, torch.Tensor] = {}
+        self.token_guide_launches = 0           # eager launches and guided graph replays
+        self._guided = False                    # the step being assembled has a guided row (_fill_sampling)
         # decode attention streams K/V as once-read data (DIE_ATTN_KV_ONCE=0: the default cache policy, for A/B)
         self.kv_once = os.environ.get("DIE_ATTN_KV_ONCE", "1") != "0"
         if self.is_cuda:
@@ -267,28 +290,179 @@ class ModelRunner:
         if slot is not None:
             self._pen_free.append(slot)
 
-    def _fill_pen(self, seqs: Seq[Sequence], n_pad: int, all_outputs: bool) -> bool:
+    def _fill_pen(self, seqs: Seq[Sequence], n_pad: int, all_outputs: bool, force: bool = False) -> bool:
         """d_pen_slot[:n_pad] for the step (-1: padding, and rows that did not ask); False and nothing written
-        when no row asks — the raw graphs never read it."""
-        if not self._asks(seqs):
+        when no row asks — the raw graphs never read it. force (a guided step, whose graphs hold the
+        ops.logit_process launch too): written even then, all -1."""
+        asks = self._asks(seqs)
+        if not asks and not force:
             return False
+        if force:
+            self._pen_alloc()
         n = len(seqs)
         ns = self.h_pen_slot.numpy()
         ns[:n] = [self._pen_build(s, all_outputs) if s.sampling.processes_logits else -1 for s in seqs]
         ns[n:n_pad] = -1
         self.d_pen_slot[:n_pad].copy_(self.h_pen_slot[:n_pad], non_blocking=self.is_cuda)
-        return True
+        return asks
 
     def _launch_logit_process(self, logits: torch.Tensor, n: int, count_ids=None, lm_part=None) -> None:
         ops.logit_process(logits, self.d_pen_slot[:n], *self.d_pen, count_ids=count_ids, lm_part=lm_part)
         self.logit_process_launches += 1
 
+    # ------------------------------------------------ constrained decoding
+    def _guide_alloc(self) -> None:
+        """The tables of ops.token_guide (per-slot descriptor, current state, error word; the two arenas) and the
+        arenas' host bookkeeping: at the first request that needs them — or at capture_graphs, whose guided
+        graphs bake the tables' addresses in."""
+        if self.d_guide is not None:
+            return
+        dev, m, i32 = self.device, self.max_seqs, torch.int32
+        self.d_guide = (torch.zeros(m, 4, dtype=i32, device=dev),
+                        torch.zeros(ops.GUIDE_ROWPTR_ARENA, dtype=i32, device=dev),
+                        torch.zeros(ops.GUIDE_EDGE_ARENA, 2, dtype=i32, device=dev),
+                        torch.zeros(m, dtype=i32, device=dev), torch.zeros(m, dtype=i32, device=dev))
+        self.h_guide = torch.zeros(6, dtype=i32, pin_memory=self.is_cuda)      # one slot's desc, cur, err
+        self.h_guide_err = torch.zeros(m, dtype=i32, pin_memory=self.is_cuda)  # err, read back with the tokens
+        self._guide_free = list(range(m - 1, -1, -1))
+        self._guide_rp, self._guide_ed = FirstFit(ops.GUIDE_ROWPTR_ARENA), FirstFit(ops.GUIDE_EDGE_ARENA)
+
+    @staticmethod
+    def _guides(seqs) -> bool:
+        """THE predicate of the guided decode path: one of the rows asked for constrained decoding."""
+        return any(s.sampling.guided for s in seqs)
+
+    def _mode(self, seqs) -> int:
+        """Which graph set a decode batch replays: 2 guided (a row is guided), 1 processed (a row set a penalty or
+        a bias), 0 raw."""
+        return 2 if self._guides(seqs) else 1 if self._asks(seqs) else 0
+
+    @torch.inference_mode()
+    def guide_admit(self, seq: Sequence, auto: Automaton) -> None:
+        """Reference the arena region of the sequence's automaton (LLMEngine.add_request: a ValueError here
+        refuses the request). Sequences with the same spec share one region; a new one is uploaded first-fit,
+        evicting unreferenced regions, least recently used first, until it fits."""
+        self._guide_alloc()
+        reg = self._guide_regions.get(auto.key)
+        if reg is None:
+            n_rp, n_ed = auto.n_states + 1, auto.n_edges
+            while True:
+                rp = self._guide_rp.alloc(n_rp)
+                ed = self._guide_ed.alloc(n_ed) if rp is not None else None
+                if ed is not None:
+                    break
+                if rp is not None:
+                    self._guide_rp.release(rp, n_rp)
+                if not self._guide_lru:
+                    raise ValueError("no room for the request's guide: the constrained-decoding arena is full")
+                old, _ = self._guide_lru.popitem(last=False)
+                self._guide_drop(old)
+            _, d_rp, d_ed, _, _ = self.d_guide
+            # on the compute stream: behind every queued window that may still read what lay here
+            d_rp[rp:rp + n_rp].copy_(torch.from_numpy(auto.row_ptr))
+            d_ed[ed:ed + n_ed].copy_(torch.from_numpy(np.stack([auto.edge_tok, auto.edge_next], axis=1)))
+            reg = self._guide_regions[auto.key] = {"auto": auto, "rp": rp, "ed": ed, "refs": 0}
+        self._guide_lru.pop(auto.key, None)
+        reg["refs"] += 1
+        self._guide_refs[seq.seq_id] = auto.key
+
+    def _guide_drop(self, key: tuple) -> None:
+        reg = self._guide_regions.pop(key)
+        self._guide_rp.release(reg["rp"], reg["auto"].n_states + 1)
+        self._guide_ed.release(reg["ed"], reg["auto"].n_edges)
+
+    def _guide_build(self, seq: Sequence, all_outputs: bool) -> int:
+        """The sequence's slot. A sequence without one gets one, and its state is rebuilt on the host, whatever
+        brought it (a fresh prompt, a recompute, a swap-in, a disaggregated import): the automaton walked over
+        every output except the next decode step's input (the step advances over that one itself) —
+        all_outputs (a prefill step's sampled rows, which do not advance): over every output, and an existing
+        slot is rebuilt (a decode row of a mixed step). The upload rides the compute stream."""
+        slot = self._guide_slots.get(seq.seq_id)
+        if slot is not None and not all_outputs:
+            return slot
+        reg = self._guide_regions[self._guide_refs[seq.seq_id]]
+        if slot is None:
+            slot = self._guide_free.pop()
+            self._guide_slots[seq.seq_id] = slot
+        if self._guide_ev is not None:  # the staging buffer's previous upload
+            self._guide_ev.synchronize()
+        auto = reg["auto"]
+        pre = list(getattr(seq, "_preempted_outputs", None) or ())
+        state = walk(auto, 0, pre + (seq.output_ids if all_outputs else seq.output_ids[:-1]))
+        self.h_guide.numpy()[:] = (reg["rp"], auto.n_states, reg["ed"], auto.n_edges, state, 0)
+        d_desc, _, _, d_cur, d_err = self.d_guide
+        nb = self.is_cuda
+        d_desc[slot].copy_(self.h_guide[0:4], non_blocking=nb)
+        d_cur[slot:slot + 1].copy_(self.h_guide[4:5], non_blocking=nb)
+        d_err[slot:slot + 1].copy_(self.h_guide[5:6], non_blocking=nb)
+        if self.is_cuda:
+            self._guide_ev = torch.cuda.Event()
+            self._guide_ev.record(torch.cuda.current_stream(self.device))
+        return slot
+
+    def release_guide_state(self, seq: Sequence, keep_region: bool = False) -> None:
+        """Give the sequence's slot back (finish, abort, preemption, swap-out) and, unless keep_region (a
+        preempted sequence returns: its place in the arena was granted at add_request), its reference to the
+        arena region; a region nobody references stays until its room is needed. A window still queued may go on
+        advancing the slot; whoever takes it next rewrites it behind that window (stream order)."""
+        slot = self._guide_slots.pop(seq.seq_id, None)
+        if slot is not None:
+            self._guide_free.append(slot)
+        if keep_region:
+            return
+        key = self._guide_refs.pop(seq.seq_id, None)
+        if key is not None:
+            reg = self._guide_regions[key]
+            reg["refs"] -= 1
+            if reg["refs"] == 0:
+                self._guide_lru[key] = None
+
+    def guide_arena_edges_used(self) -> int:
+        return self._guide_ed.used if self._guide_ed is not None else 0
+
+    def _fill_guide(self, seqs: Seq[Sequence], n_pad: int, all_outputs: bool) -> bool:
+        """d_guide_slot[:n_pad] for the step (-1: padding, and rows that are not guided); False and nothing
+        written when no row is guided — only the guided graphs read it."""
+        if not self._guides(seqs):
+            return False
+        n = len(seqs)
+        ns = self.h_guide_slot.numpy()
+        ns[:n] = [self._guide_build(s, all_outputs) if s.sampling.guided else -1 for s in seqs]
+        ns[n:n_pad] = -1
+        self.d_guide_slot[:n_pad].copy_(self.h_guide_slot[:n_pad], non_blocking=self.is_cuda)
+        return True
+
+    def _launch_token_guide(self, logits: torch.Tensor, n: int, advance_ids=None, lm_part=None) -> None:
+        ops.token_guide(logits, self.d_guide_slot[:n], *self.d_guide, advance_ids=advance_ids, lm_part=lm_part)
+        self.token_guide_launches += 1
+
+    def _guide_err_to_host(self) -> None:
+        """Queue the sticky error words behind a guided step: they come back with its tokens."""
+        if self.is_cuda:
+            self.h_guide_err.copy_(self.d_guide[4], non_blocking=True)
+
+    def guide_errors(self, seqs: Seq[Sequence]) -> List[tuple]:
+        """(sequence, error bits) of the guided sequences whose slot reported an error in a step already read
+        back (ops.GUIDE_ERR_*): the engine fails those requests."""
+        if not self._guide_slots:
+            return []
+        err = self.h_guide_err if self.is_cuda else self.d_guide[4]
+        out = []
+        for s in seqs:
+            slot = self._guide_slots.get(s.seq_id)
+            if slot is not None and int(err[slot]):
+                out.append((s, int(err[slot])))
+        return out
+
     def _fill_sampling(self, seqs: Seq[Sequence], n_pad: int, prefill: bool = False) -> bool:
         """Write per-row sampling params; returns True when every row is greedy.
         Skips the H2D copies when the rows are all greedy (the kernel's greedy
         path ignores them) — the common decode case costs nothing here.
-        Also maps the rows that ask for logit processing to their slots (self._proc: one of them does)."""
-        self._proc = self._fill_pen(seqs, n_pad, all_outputs=prefill)
+        Also maps the rows that ask for logit processing or constrained decoding to their slots (self._proc /
+        self._guided: one of them does)."""
+        self._guided = self._fill_guide(seqs, n_pad, all_outputs=prefill)
+        # a guided decode step replays graphs that hold the ops.logit_process launch too: its slots must be current
+        self._proc = self._fill_pen(seqs, n_pad, all_outputs=prefill, force=self._guided and not prefill)
         greedy = all(s.sampling.greedy for s in seqs)
         if greedy:
             key = ("greedy", n_pad)
@@ -409,15 +583,19 @@ class ModelRunner:
             nl[:nd] = nl[done]
         greedy = self._fill_sampling([chunks[i].seq for i in done], nd, prefill=True) if nd else True
         proc = bool(nd) and self._proc
+        guide = bool(nd) and self._guided
         lp_top = self._lp_top(chunks[i].seq for i in done) if nd else -1
         plan = self._prompt_logprob_plan(chunks)
         self.last_logprobs = self.last_prompt_logprobs = None
         self._h2d(t, n, with_cu=True)
         max_q = max(c.length for c in chunks)
         self._sync_step(self.KIND_PREFILL, t, n, max_q, nd)
-        ids = self._exec_prefill(t, n, max_q, nd, greedy, kv_hook=kv_hook, lp_top=lp_top, plan=plan, process=proc)
+        ids = self._exec_prefill(t, n, max_q, nd, greedy, kv_hook=kv_hook, lp_top=lp_top, plan=plan, process=proc,
+                                 guide=guide)
         res: List[Optional[int]] = [None] * n
         if nd:
+            if guide:
+                self._guide_err_to_host()
             if lp_top >= 0:
                 self._lp_to_host(0, 1)
             vals = self._to_host(ids, nd)
@@ -475,7 +653,8 @@ class ModelRunner:
         return res
 
     def _exec_prefill(self, t: int, n: int, max_q: int, nd: int, greedy: bool, kv_hook=None, lp_top: int = -1,
-                      plan: Optional[List[tuple]] = None, process: bool = False) -> Optional[torch.Tensor]:
+                      plan: Optional[List[tuple]] = None, process: bool = False,
+                      guide: bool = False) -> Optional[torch.Tensor]:
         # the last layer runs only for the sampled rows (CausalLM._last_layer_kept_rows; DIE_PRUNE_LAST=0: all);
         # a step that scores prompt tokens (prompt_logprobs) needs every row
         keep = self.d_last[:nd] if self.prune_last and not plan else None
@@ -492,6 +671,8 @@ class ModelRunner:
         logits = self.model.compute_logits(hidden)
         if process:  # penalties / bias of the rows that ask (their counts hold every output: nothing to count here)
             self._launch_logit_process(logits, nd)
+        if guide:  # constrained rows: masked to their state's tokens (the state holds every output: no advance here)
+            self._launch_token_guide(logits, nd)
         ids = self._sample(logits, nd, greedy, self.d_out)
         if lp_top >= 0:  # the first generated token's logprobs (the leader only: followers have nothing to report)
             self._launch_logprobs(logits, ids, nd, 0, lp_top)
@@ -511,7 +692,7 @@ class ModelRunner:
             sc = self.dec_scratch
             ops.embed_sumsq(self.d_ids[:pad], self.model.embed, sc["ssp0"], out=sc["h_in"][:pad])
 
-    def _decode_forward(self, n: int, process: bool = False) -> torch.Tensor:
+    def _decode_forward(self, n: int, process: bool = False, guide: bool = False) -> torch.Tensor:
         tail = self._fused_tail(n)
         meta = AttnMetadata(is_prefill=False, slot_mapping=self.d_slots[:n], block_tables=self.d_bt[:n],
                             ctx_lens=self.d_ctx[:n], max_ctx=self.max_model_len, part_o=self.part_o,
@@ -527,6 +708,10 @@ class ModelRunner:
             # between the LM head and the sampling tail: counts this step's input ids (the previous samples), rewrites
             # the rows that ask in place and makes their greedy candidates agree with the rewritten rows
             self._launch_logit_process(logits, n, count_ids=self.d_ids[:n], lm_part=amax[:n] if amax is not None else None)
+        if guide:
+            # after the penalties and biases, so that no bias can lift a barred token: advances the guided rows'
+            # automata over this step's input ids, masks the rows and makes their greedy candidates agree
+            self._launch_token_guide(logits, n, advance_ids=self.d_ids[:n], lm_part=amax[:n] if amax is not None else None)
         if not self.is_cuda:
             return ops.sample(logits, self.d_temp[:n], self.d_topk[:n], self.d_topp[:n], self.d_seed[:n],
                               self.d_step[:n])
@@ -584,6 +769,24 @@ class ModelRunner:
                 self.graph_logits_proc[b] = self._last_logits
             torch.cuda.synchronize(self.device)
             self.logit_process_launches = 0  # warm-up and capture served no request
+        if self.supports_logit_processing and self.supports_token_guide:
+            # a third set, LM head -> ops.logit_process -> ops.token_guide -> the unchanged tail, for batches with a
+            # guided row (_guides); rows that did not ask have slot -1 in both kernels. The two sets above stay
+            # exactly what they were.
+            self._guide_alloc()
+            self.d_pen_slot.fill_(-1)
+            self.d_guide_slot.fill_(-1)
+            for b in sizes:
+                self._decode_forward(b, process=True, guide=True)
+            torch.cuda.synchronize(self.device)
+            for b in reversed(sizes):
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, pool=self._graph_pool):
+                    self._decode_forward(b, process=True, guide=True)
+                self.graphs_guided[b] = g
+                self.graph_logits_guided[b] = self._last_logits
+            torch.cuda.synchronize(self.device)
+            self.logit_process_launches = self.token_guide_launches = 0
         self.graph_sizes = sizes
         logger.info("captured decode hipGraphs for batch sizes %s", sizes)
 
@@ -611,13 +814,15 @@ class ModelRunner:
             self.h_ctl[1] = n
             self.d_ctl.copy_(self.h_ctl, non_blocking=True)
         self._sync_step(self.KIND_DECODE, n, pad)
-        proc = self._proc
-        ids = self._exec_decode(n, pad, proc)
+        mode = 2 if self._guided else int(self._proc)
+        ids = self._exec_decode(n, pad, mode)
+        if mode == 2:
+            self._guide_err_to_host()
         top = self._lp_top(seqs)
         self.last_logprobs = None
         if top < 0:
             return self._to_host(ids, n)
-        glog = self.graph_logits_proc if proc else self.graph_logits
+        glog = (self.graph_logits, self.graph_logits_proc, self.graph_logits_guided)[mode]
         self._launch_logprobs(glog[pad] if pad in self.graphs else self._last_logits, ids, n, 0, top)
         self._lp_to_host(0, 1)
         toks = self._to_host(ids, n)
@@ -655,7 +860,7 @@ class ModelRunner:
         self.d_ctl.copy_(self.h_ctl, non_blocking=True)
         self._sync_window(n, pad, k)
         top = self._lp_top(seqs)
-        self._replay_window(pad, n, k, 0, top, self._proc)
+        self._replay_window(pad, n, k, 0, top, 2 if self._guided else int(self._proc))
         self._queue_fault_readback()
         if k_next > 1:
             ev = torch.cuda.Event()
@@ -668,26 +873,33 @@ class ModelRunner:
         self.last_logprobs = self._lp_read(0, k, n, top) if top >= 0 else None
         return self.h_tokens[:k, :n].tolist()
 
-    def _replay_window(self, pad: int, n: int, k: int, base: int, top: int, proc: bool) -> None:
+    def _replay_window(self, pad: int, n: int, k: int, base: int, top: int, mode: int) -> None:
         """k replays queued back to back, their tokens into rows [base, base + k); top >= 0 (a row asked for
         logprobs): one ops.token_logprobs launch behind each replay — it reads that step's logits and sampled ids
         before the next replay overwrites them (stream order) — and the logprob rows come back with the tokens.
-        proc (a row asks for logit processing, _asks): the graphs with the ops.logit_process launch and their
-        logits; otherwise the raw graphs, launch for launch as without the feature."""
-        g = (self.graphs_proc if proc else self.graphs)[pad]
-        if proc:
+        mode (_mode) 1, a row asks for logit processing: the graphs with the ops.logit_process launch and their
+        logits; 2, a row is guided: the graphs with the ops.token_guide launch behind it, and the slots' error
+        words come back with the tokens; 0: the raw graphs, launch for launch as without either feature."""
+        g = (self.graphs, self.graphs_proc, self.graphs_guided)[mode][pad]
+        if mode:
             self.logit_process_launches += k
+        if mode == 2:
+            self.token_guide_launches += k
         if top < 0:
             for _ in range(k):
                 g.replay()
             self.h_tokens[base:base + k].copy_(self.d_tokens[base:base + k], non_blocking=True)
+            if mode == 2:
+                self._guide_err_to_host()
             return
-        logits = (self.graph_logits_proc if proc else self.graph_logits)[pad]
+        logits = (self.graph_logits, self.graph_logits_proc, self.graph_logits_guided)[mode][pad]
         for i in range(k):
             g.replay()
             self._launch_logprobs(logits, self.d_out, n, base + i, top)
         self.h_tokens[base:base + k].copy_(self.d_tokens[base:base + k], non_blocking=True)
         self._lp_to_host(base, base + k)
+        if mode == 2:
+            self._guide_err_to_host()
 
     def _queue_continuation(self, seqs: List[Sequence], pending: int, k: int, base: int) -> None:
         """Queue k more decode steps for `seqs` behind a window of `pending` steps whose tokens the
@@ -709,7 +921,7 @@ class ModelRunner:
         self.d_ctl[0:1].fill_(base)  # token rows [base, base + k)
         self._sync_continuation(par, pad, k, base)
         top = self._lp_top(seqs)
-        self._replay_window(pad, n, k, base, top, self._asks(seqs))
+        self._replay_window(pad, n, k, base, top, self._mode(seqs))
         self._queue_fault_readback()
         ev = torch.cuda.Event()
         ev.record(torch.cuda.current_stream(self.device))
@@ -735,12 +947,14 @@ class ModelRunner:
         self.last_logprobs = self._lp_read(b, b + k, n, w["lp_top"]) if w["lp_top"] >= 0 else None
         return self.h_tokens[b:b + k, :n].tolist()
 
-    def _exec_decode(self, n: int, pad: int, process: bool = False) -> torch.Tensor:
+    def _exec_decode(self, n: int, pad: int, mode: int = 0) -> torch.Tensor:
         g = self.graphs.get(pad)
         if g is not None:
-            if process:
-                g = self.graphs_proc[pad]
+            if mode:
+                g = (self.graphs_proc, self.graphs_guided)[mode - 1][pad]
                 self.logit_process_launches += 1
+                self.token_guide_launches += mode == 2
             g.replay()
             return self.d_out
-        return self._decode_forward(n, process)
+        # eager: a guided step launches ops.logit_process only when a row asks for it
+        return self._decode_forward(n, self._proc if mode == 2 else bool(mode), mode == 2)

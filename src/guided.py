@@ -1,0 +1,644 @@
+"""
+Constrained decoding on the host: three front ends (``allowed_token_ids``, ``guided_choice``, ``guided_regex``)
+compile to ONE target form, a token automaton in CSR, which ``ops.token_guide`` walks on the device.
+
+    row_ptr[S + 1]   edges of state s: [row_ptr[s], row_ptr[s + 1])
+    edge_tok[E]      ascending and unique within a state
+    edge_next[E]
+    start state 0
+
+Invariant: every reachable state has at least one edge (no dead ends), so a step always has a token to draw.
+
+* ``allowed_token_ids``: one state with self-loops.
+* ``guided_choice``: a trie; a completed choice has an EOS edge to a sink whose only edge is EOS -> sink (windows
+  run past a finished sequence: the sink keeps those steps legal).
+* ``guided_regex``: a byte-level subset of regular expressions -> Thompson NFA -> subset construction -> byte DFA
+  with unreachable and dead states pruned -> lifted to tokens through a byte table ``token_bytes: id -> bytes |
+  None``; accepting states get the EOS edge. The subset: literals (non-ASCII as their UTF-8 bytes), the escapes
+  ``\\d \\w \\s \\D \\W \\S \\n \\t \\r`` and ``\\`` + punctuation, ``.``, classes ``[...]`` / ``[^...]`` with
+  ranges, groups ``(...)``, ``|`` and the quantifiers ``* + ? {m} {m,} {m,n}``. ``.``, negated classes and the
+  upper-case escapes range over ASCII bytes only (``.`` excludes ``\\n``). Anything else is a ValueError naming
+  the position.
+
+Pure numpy / Python: imported by ``src.preproc`` for early validation, never touches torch.
+"""
+
+from __future__ import annotations
+
+import collections
+import threading
+from dataclasses import dataclass
+from typing import Dict, FrozenSet, Iterable, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+# per-request caps (csrc/kernels/launchers.h GUIDE_MAX_STATES / GUIDE_MAX_EDGES)
+GUIDE_MAX_STATES = 16384
+GUIDE_MAX_EDGES = 262144           # twice the largest vocabulary
+GUIDE_MAX_CHOICES = 1024
+GUIDE_MAX_CHOICE_TOKENS = 65536
+_QUANT_MAX = 1024                  # {m,n} bound: larger counts only ever end at the state cap
+
+
+@dataclass(frozen=True, eq=False)
+class Automaton:
+    row_ptr: np.ndarray    # int32 [S + 1]
+    edge_tok: np.ndarray   # int32 [E]
+    edge_next: np.ndarray  # int32 [E]
+    key: tuple             # the canonical spec it was compiled from (arena regions are shared by it)
+
+    @property
+    def n_states(self) -> int:
+        return len(self.row_ptr) - 1
+
+    @property
+    def n_edges(self) -> int:
+        return len(self.edge_tok)
+
+    def edges(self, state: int) -> Tuple[np.ndarray, np.ndarray]:
+        lo, hi = int(self.row_ptr[state]), int(self.row_ptr[state + 1])
+        return self.edge_tok[lo:hi], self.edge_next[lo:hi]
+
+
+def walk(automaton: Automaton, state: int, tokens: Iterable[int]) -> int:
+    """The state after ``tokens`` from ``state``. A token without an edge is a ValueError: the runner rebuilds
+    device state from tokens the automaton itself allowed, so this never happens to a healthy sequence."""
+    for t in tokens:
+        toks, nxt = automaton.edges(state)
+        i = int(np.searchsorted(toks, t))
+        if i >= len(toks) or int(toks[i]) != int(t):
+            raise ValueError(f"token {int(t)} has no edge in guide state {state}")
+        state = int(nxt[i])
+    return state
+
+
+def _check_caps(n_states: int, n_edges: int) -> None:
+    if n_states > GUIDE_MAX_STATES:
+        raise ValueError(f"the guide's automaton has more than {GUIDE_MAX_STATES} states")
+    if n_edges > GUIDE_MAX_EDGES:
+        raise ValueError(f"the guide's automaton has more than {GUIDE_MAX_EDGES} edges")
+
+
+def _from_state_edges(per_state: List[Dict[int, int]], key: tuple) -> Automaton:
+    """CSR from {token: next} per state (start = 0)."""
+    n_edges = sum(len(e) for e in per_state)
+    _check_caps(len(per_state), n_edges)
+    row_ptr = np.zeros(len(per_state) + 1, dtype=np.int32)
+    tok = np.empty(n_edges, dtype=np.int32)
+    nxt = np.empty(n_edges, dtype=np.int32)
+    at = 0
+    for s, e in enumerate(per_state):
+        if not e:
+            raise AssertionError("guide state without an edge")
+        ks = sorted(e)
+        tok[at:at + len(ks)] = ks
+        nxt[at:at + len(ks)] = [e[k] for k in ks]
+        at += len(ks)
+        row_ptr[s + 1] = at
+    return Automaton(row_ptr, tok, nxt, key)
+
+
+# ------------------------------------------------------------------ allowed_token_ids / guided_choice
+def _check_vocab(ids: Iterable[int], vocab: Optional[int], what: str) -> None:
+    if vocab is not None:
+        for t in ids:
+            if not 0 <= t < vocab:
+                raise ValueError(f"{what} token id {t} outside [0, {vocab})")
+
+
+def compile_allowed(ids: Sequence[int], vocab: Optional[int] = None) -> Automaton:
+    ids = sorted(set(int(t) for t in ids))
+    if not ids:
+        raise ValueError("allowed_token_ids must not be empty")
+    _check_vocab(ids, vocab, "allowed_token_ids")
+    return _from_state_edges([{t: 0 for t in ids}], ("allowed", tuple(ids)))
+
+
+def compile_choice(choices: Sequence[Sequence[int]], eos: int, vocab: Optional[int] = None) -> Automaton:
+    canon = sorted(set(tuple(int(t) for t in c) for c in choices))
+    if not canon or any(not c for c in canon):
+        raise ValueError("guided_choice needs at least one choice and no empty one")
+    for c in canon:
+        _check_vocab(c, vocab, "guided_choice")
+        if eos in c:
+            raise ValueError("a guided_choice must not contain the end-of-sequence token")
+    states: List[Dict[int, int]] = [{}]
+    ends = []
+    for c in canon:
+        s = 0
+        for t in c:
+            n = states[s].get(t)
+            if n is None:
+                n = len(states)
+                states.append({})
+                states[s][t] = n
+                if n >= GUIDE_MAX_STATES:
+                    _check_caps(n + 2, 0)
+            s = n
+        ends.append(s)
+    sink = len(states)
+    states.append({eos: sink})
+    for s in ends:
+        states[s][eos] = sink
+    return _from_state_edges(states, ("choice", tuple(canon), int(eos)))
+
+
+# ------------------------------------------------------------------ guided_regex: parser
+_ASCII = frozenset(range(128))
+_DIGIT = frozenset(range(0x30, 0x3A))
+_WORD = frozenset(list(range(0x30, 0x3A)) + list(range(0x41, 0x5B)) + list(range(0x61, 0x7B)) + [0x5F])
+_SPACE = frozenset(b" \t\n\r\f\v")
+_ESC_CLASS = {"d": _DIGIT, "w": _WORD, "s": _SPACE, "D": _ASCII - _DIGIT, "W": _ASCII - _WORD, "S": _ASCII - _SPACE}
+_ESC_CHAR = {"n": 0x0A, "t": 0x09, "r": 0x0D}
+_PUNCT = frozenset("!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~")
+
+# AST: ("set", frozenset of bytes) | ("cat", [nodes]) | ("alt", [nodes]) | ("rep", node, m, n or None)
+
+
+class _Parser:
+    def __init__(self, pattern: str):
+        self.p = pattern
+        self.i = 0
+
+    def err(self, what: str, pos: Optional[int] = None):
+        raise ValueError(f"guided_regex: {what} at position {self.i if pos is None else pos}")
+
+    def peek(self) -> Optional[str]:
+        return self.p[self.i] if self.i < len(self.p) else None
+
+    def parse(self):
+        node = self.alt()
+        if self.i < len(self.p):
+            self.err("unbalanced ')'")
+        return node
+
+    def alt(self):
+        branches = [self.cat()]
+        while self.peek() == "|":
+            self.i += 1
+            branches.append(self.cat())
+        return branches[0] if len(branches) == 1 else ("alt", branches)
+
+    def cat(self):
+        items = []
+        while self.peek() is not None and self.peek() not in "|)":
+            items.append(self.quantified())
+        return ("cat", items)
+
+    def quantified(self):
+        at = self.i
+        node = self.atom()
+        while True:
+            c = self.peek()
+            if c == "*":
+                m, n = 0, None
+            elif c == "+":
+                m, n = 1, None
+            elif c == "?":
+                m, n = 0, 1
+            elif c == "{":
+                m, n = self.braces()
+            else:
+                return node
+            if c != "{":
+                self.i += 1
+            if self.peek() == "?":
+                self.err("lazy quantifiers are not supported")
+            if self.peek() == "+":
+                self.err("possessive quantifiers are not supported")
+            if self.peek() in ("*", "{"):
+                self.err("a quantifier cannot follow a quantifier")
+            node = ("rep", node, m, n)
+        return node
+
+    def braces(self) -> Tuple[int, Optional[int]]:
+        start = self.i
+        self.i += 1
+        m = self.number()
+        if m is None:
+            self.err("'{' must open a quantifier {m}, {m,} or {m,n}", start)
+        n: Optional[int] = m
+        if self.peek() == ",":
+            self.i += 1
+            n = self.number()
+        if self.peek() != "}":
+            self.err("unterminated quantifier", start)
+        self.i += 1
+        if n is not None and n < m:
+            self.err("quantifier {m,n} with n < m", start)
+        if m > _QUANT_MAX or (n is not None and n > _QUANT_MAX):
+            self.err(f"quantifier count above {_QUANT_MAX}", start)
+        return m, n
+
+    def number(self) -> Optional[int]:
+        j = self.i
+        while self.i < len(self.p) and self.p[self.i] in "0123456789":
+            self.i += 1
+        return int(self.p[j:self.i]) if self.i > j else None
+
+    def escape(self, in_class: bool):
+        """After the backslash: a byte set (class escape) or a single byte."""
+        at = self.i - 1
+        c = self.peek()
+        if c is None:
+            self.err("a pattern cannot end in '\\'", at)
+        self.i += 1
+        if c in _ESC_CLASS:
+            return _ESC_CLASS[c]
+        if c in _ESC_CHAR:
+            return frozenset([_ESC_CHAR[c]])
+        if c in _PUNCT:
+            return frozenset([ord(c)])
+        if c in "0123456789":
+            self.err("backreferences are not supported", at)
+        if c in "AbBZzG":
+            self.err("anchors are not supported", at)
+        self.err(f"unsupported escape '\\{c}'", at)
+
+    def atom(self):
+        c = self.peek()
+        at = self.i
+        if c == "(":
+            self.i += 1
+            if self.peek() == "?":
+                nxt = self.p[self.i + 1: self.i + 3]
+                if nxt[:1] in ("=", "!") or nxt in ("<=", "<!"):
+                    self.err("lookaround is not supported", at)
+                if nxt[:1] in ("P", "<") or nxt[:1] == ":":
+                    self.err("only plain groups (...) are supported", at)
+                self.err("flags are not supported", at)
+            node = self.alt()
+            if self.peek() != ")":
+                self.err("unterminated group", at)
+            self.i += 1
+            return node
+        if c == "[":
+            return ("set", self.char_class())
+        if c == ".":
+            self.i += 1
+            return ("set", _ASCII - {0x0A})
+        if c in ("^", "$"):
+            self.err("anchors are not supported (the whole output is matched)")
+        if c in "*+?{":
+            self.err("a quantifier with nothing to repeat")
+        if c in "]}":
+            self.err(f"unbalanced '{c}'")
+        self.i += 1
+        if c == "\\":
+            return ("set", self.escape(False))
+        b = c.encode("utf-8")
+        if len(b) == 1:
+            return ("set", frozenset(b))
+        return ("cat", [("set", frozenset([x])) for x in b])
+
+    def class_item(self):
+        """One member of a class: (byte or None, set). A single byte can open a range."""
+        c = self.peek()
+        if c is None:
+            return None
+        if c == "\\":
+            self.i += 1
+            s = self.escape(True)
+            return (next(iter(s)) if len(s) == 1 and self.p[self.i - 1] not in _ESC_CLASS else None), s
+        if ord(c) > 127:
+            self.err("non-ASCII characters are not supported inside a class")
+        if c == "[" and self.p[self.i + 1: self.i + 2] == ":":
+            self.err("POSIX classes are not supported")
+        self.i += 1
+        return ord(c), frozenset([ord(c)])
+
+    def char_class(self) -> FrozenSet[int]:
+        start = self.i
+        self.i += 1
+        negate = self.peek() == "^"
+        if negate:
+            self.i += 1
+        members: set = set()
+        first = True
+        while True:
+            c = self.peek()
+            if c is None:
+                self.err("unterminated class", start)
+            if c == "]" and not first:
+                self.i += 1
+                break
+            first = False
+            at = self.i
+            lo, s = self.class_item()
+            if self.peek() == "-" and self.p[self.i + 1: self.i + 2] not in ("]", ""):
+                if lo is None:
+                    self.err("a class escape cannot open a range", at)
+                self.i += 1
+                hi, _ = self.class_item()
+                if hi is None:
+                    self.err("a class escape cannot close a range", at)
+                if hi < lo:
+                    self.err("reversed range in a class", at)
+                members.update(range(lo, hi + 1))
+            else:
+                members.update(s)
+        out = frozenset(members)
+        if negate:
+            out = _ASCII - out
+        if not out:
+            self.err("a class that matches nothing", start)
+        return out
+
+
+def parse_regex(pattern: str):
+    """The pattern's AST; ValueError (naming the position) for anything outside the supported subset."""
+    if not isinstance(pattern, str) or not pattern:
+        raise ValueError("guided_regex must be a non-empty string")
+    return _Parser(pattern).parse()
+
+
+# ------------------------------------------------------------------ guided_regex: NFA -> DFA
+class _NFA:
+    def __init__(self):
+        self.eps: List[List[int]] = []
+        self.trans: List[List[Tuple[FrozenSet[int], int]]] = []
+
+    def state(self) -> int:
+        if len(self.eps) > 64 * GUIDE_MAX_STATES:
+            raise ValueError(f"the guide's automaton has more than {GUIDE_MAX_STATES} states")
+        self.eps.append([])
+        self.trans.append([])
+        return len(self.eps) - 1
+
+    def build(self, node) -> Tuple[int, int]:
+        """Thompson fragment (entry, exit) of an AST node."""
+        kind = node[0]
+        if kind == "set":
+            a, b = self.state(), self.state()
+            self.trans[a].append((node[1], b))
+            return a, b
+        if kind == "cat":
+            a = b = self.state()
+            for item in node[1]:
+                x, y = self.build(item)
+                self.eps[b].append(x)
+                b = y
+            return a, b
+        if kind == "alt":
+            a, b = self.state(), self.state()
+            for br in node[1]:
+                x, y = self.build(br)
+                self.eps[a].append(x)
+                self.eps[y].append(b)
+            return a, b
+        _, sub, m, n = node
+        a = b = self.state()
+        for _ in range(m):
+            x, y = self.build(sub)
+            self.eps[b].append(x)
+            b = y
+        if n is None:  # sub*
+            x, y = self.build(sub)
+            hub = self.state()
+            self.eps[b].append(hub)
+            self.eps[hub].append(x)
+            self.eps[y].append(hub)
+            return a, hub
+        end = self.state()
+        for _ in range(n - m):  # (sub(sub(...)?)?)?
+            x, y = self.build(sub)
+            self.eps[b].append(end)
+            self.eps[b].append(x)
+            b = y
+        self.eps[b].append(end)
+        return a, end
+
+
+def _reach(n: int, src: np.ndarray, dst: np.ndarray, seeds: np.ndarray) -> np.ndarray:
+    """bool [n]: the nodes reachable from `seeds` over the edges src -> dst (breadth first, every edge once)."""
+    order = np.argsort(src, kind="stable")
+    d = np.asarray(dst)[order]
+    ptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.bincount(src, minlength=n), out=ptr[1:])
+    seen = np.zeros(n, dtype=bool)
+    front = np.unique(np.asarray(seeds, dtype=np.int64))
+    seen[front] = True
+    while len(front):
+        cnt = ptr[front + 1] - ptr[front]
+        total = int(cnt.sum())
+        if not total:
+            break
+        first = np.repeat(ptr[front] - (np.cumsum(cnt) - cnt), cnt)
+        nb = np.unique(d[first + np.arange(total)])
+        front = nb[~seen[nb]]
+        seen[front] = True
+    return seen
+
+
+def regex_to_dfa(pattern: str) -> Tuple[np.ndarray, np.ndarray]:
+    """(trans int32 [S, 256] with -1 = no transition, accepting bool [S]) of the pruned byte DFA, start state 0:
+    every state is reachable and can reach an accepting one. ValueError: unsupported syntax, a pattern that
+    matches nothing, more than GUIDE_MAX_STATES states."""
+    nfa = _NFA()
+    entry, exit_ = nfa.build(parse_regex(pattern))
+
+    def closure(states) -> FrozenSet[int]:
+        seen = set(states)
+        stack = list(states)
+        while stack:
+            for t in nfa.eps[stack.pop()]:
+                if t not in seen:
+                    seen.add(t)
+                    stack.append(t)
+        return frozenset(seen)
+
+    start = closure([entry])
+    index = {start: 0}
+    order = [start]
+    rows: List[List[int]] = []
+    i = 0
+    while i < len(order):
+        cur = order[i]
+        i += 1
+        by_byte: Dict[int, set] = {}
+        for s in cur:
+            for bs, t in nfa.trans[s]:
+                for b in bs:
+                    by_byte.setdefault(b, set()).add(t)
+        row = [-1] * 256
+        memo: Dict[FrozenSet[int], int] = {}
+        for b, targets in by_byte.items():
+            tk = frozenset(targets)
+            j = memo.get(tk)
+            if j is None:
+                cl = closure(tk)
+                j = index.get(cl)
+                if j is None:
+                    j = index[cl] = len(order)
+                    order.append(cl)
+                    if len(order) > GUIDE_MAX_STATES:
+                        raise ValueError(f"the guide's automaton has more than {GUIDE_MAX_STATES} states")
+                memo[tk] = j
+            row[b] = j
+        rows.append(row)
+    trans = np.asarray(rows, dtype=np.int32).reshape(len(order), 256)
+    accept = np.fromiter((exit_ in s for s in order), dtype=bool, count=len(order))
+    # dead states: those that reach no accepting state (reachability over the reversed transitions)
+    frm, byte = np.nonzero(trans >= 0)
+    live = _reach(len(order), trans[frm, byte], frm, np.nonzero(accept)[0])
+    if not live[0]:
+        raise ValueError("guided_regex matches nothing")
+    renum = np.full(len(order), -1, dtype=np.int32)
+    renum[live] = np.arange(int(live.sum()), dtype=np.int32)  # state 0 stays 0: it is live and first
+    trans = np.where(trans >= 0, renum[np.maximum(trans, 0)], -1)[live].astype(np.int32)
+    return trans, accept[live]
+
+
+def dfa_accepts(trans: np.ndarray, accept: np.ndarray, data: bytes) -> bool:
+    s = 0
+    for b in data:
+        s = int(trans[s, b])
+        if s < 0:
+            return False
+    return bool(accept[s])
+
+
+def byte_table(vocab: int) -> List[Optional[bytes]]:
+    """ByteTokenizer's table: ids 3..258 are one byte each, everything else has no bytes."""
+    return [bytes([i - 3]) if 3 <= i < 259 and i < vocab else None for i in range(min(vocab, 259))] + \
+        [None] * max(0, vocab - 259)
+
+
+def compile_regex(pattern: str, token_bytes: Sequence[Optional[bytes]], eos: int,
+                  vocab: Optional[int] = None) -> Automaton:
+    trans, accept = regex_to_dfa(pattern)
+    n = trans.shape[0]
+    vocab = len(token_bytes) if vocab is None else min(vocab, len(token_bytes))
+    src_l, tok_l, nxt_l = [], [], []
+    all_states = np.arange(n, dtype=np.int32)
+    for t in range(vocab):
+        bs = token_bytes[t]
+        if not bs or t == eos:
+            continue
+        st = all_states
+        for b in bs:
+            st = np.where(st >= 0, trans[np.maximum(st, 0), b], -1)
+        ok = np.nonzero(st >= 0)[0]
+        if len(ok):
+            src_l.append(ok.astype(np.int32))
+            tok_l.append(np.full(len(ok), t, dtype=np.int32))
+            nxt_l.append(st[ok].astype(np.int32))
+    sink = n
+    acc = np.nonzero(accept)[0].astype(np.int32)
+    src_l += [acc, np.asarray([sink], dtype=np.int32)]
+    tok_l += [np.full(len(acc), eos, dtype=np.int32), np.asarray([eos], dtype=np.int32)]
+    nxt_l += [np.full(len(acc), sink, dtype=np.int32), np.asarray([sink], dtype=np.int32)]
+    src, tok, nxt = np.concatenate(src_l), np.concatenate(tok_l), np.concatenate(nxt_l)
+    # the byte DFA has no dead state, but a byte without a token can leave one in the token automaton: keep the
+    # states that still reach the sink, then those reachable from the start
+    good = _reach(n + 1, nxt, src, np.asarray([sink]))
+    if not good[0]:
+        raise ValueError("guided_regex matches nothing this tokenizer can produce")
+    keep = good[src] & good[nxt]
+    src, tok, nxt = src[keep], tok[keep], nxt[keep]
+    reach = _reach(n + 1, src, nxt, np.asarray([0]))
+    keep = reach[src]
+    src, tok, nxt = src[keep], tok[keep], nxt[keep]
+    renum = np.full(n + 1, -1, dtype=np.int32)
+    renum[reach] = np.arange(int(reach.sum()), dtype=np.int32)
+    src, nxt = renum[src], renum[nxt]
+    n_states = int(reach.sum())
+    _check_caps(n_states, len(src))
+    order = np.lexsort((tok, src))
+    src, tok, nxt = src[order], tok[order], nxt[order]
+    row_ptr = np.zeros(n_states + 1, dtype=np.int32)
+    np.cumsum(np.bincount(src, minlength=n_states), out=row_ptr[1:])
+    return Automaton(row_ptr, tok.astype(np.int32), nxt.astype(np.int32), ("regex", pattern, int(eos), id_of(token_bytes)))
+
+
+_TABLE_IDS: Dict[int, tuple] = {}
+
+
+def id_of(token_bytes) -> int:
+    """A small stable number per byte-table object (a cache key must not hold, or hash, a 128K-entry table); the
+    table is kept alive so that its identity cannot be reused."""
+    ent = _TABLE_IDS.get(id(token_bytes))
+    if ent is None:
+        ent = _TABLE_IDS[id(token_bytes)] = (token_bytes, len(_TABLE_IDS))
+    return ent[1]
+
+
+# ------------------------------------------------------------------ the one entry point, cached
+_CACHE: "collections.OrderedDict[tuple, Automaton]" = collections.OrderedDict()
+_CACHE_MAX = 64
+_LOCK = threading.Lock()
+
+
+def compile_guide(sampling, vocab: int, eos: Optional[int], token_bytes: Optional[Sequence[Optional[bytes]]] = None
+                  ) -> Automaton:
+    """The automaton of a request's guide (SamplingParams.guided is true), from a small LRU keyed by the
+    canonical spec. ValueError for everything the engine must refuse."""
+    if sampling.allowed_token_ids is not None:
+        spec = ("allowed", tuple(sorted(sampling.allowed_token_ids)), vocab)
+    else:
+        if eos is None:
+            raise ValueError("guided_choice / guided_regex are not supported on an engine without an "
+                             "end-of-sequence token")
+        if sampling.ignore_eos:
+            raise ValueError("guided_choice / guided_regex cannot be combined with ignore_eos")
+        if sampling.guided_choice is not None:
+            spec = ("choice", tuple(sorted(set(tuple(c) for c in sampling.guided_choice))), vocab, eos)
+        else:
+            if token_bytes is None:
+                raise ValueError("guided_regex is not supported on an engine without a byte table of its "
+                                 "tokenizer (only the byte-level tokenizer provides one)")
+            spec = ("regex", sampling.guided_regex, vocab, eos, id_of(token_bytes))
+    with _LOCK:
+        a = _CACHE.get(spec)
+        if a is not None:
+            _CACHE.move_to_end(spec)
+            return a
+    if spec[0] == "allowed":
+        a = compile_allowed(spec[1], vocab)
+    elif spec[0] == "choice":
+        a = compile_choice(spec[1], eos, vocab)
+    else:
+        a = compile_regex(spec[1], token_bytes, eos, vocab)
+    a = Automaton(a.row_ptr, a.edge_tok, a.edge_next, spec)
+    with _LOCK:
+        _CACHE[spec] = a
+        while len(_CACHE) > _CACHE_MAX:
+            _CACHE.popitem(last=False)
+    return a
+
+
+# ------------------------------------------------------------------ arena bookkeeping (host side)
+class FirstFit:
+    """A first-fit free list over [0, size): the runner's bookkeeping for the device arenas."""
+
+    def __init__(self, size: int):
+        self.size = size
+        self.free: List[List[int]] = [[0, size]]  # [offset, length], ascending, coalesced
+
+    def alloc(self, n: int) -> Optional[int]:
+        for i, (off, ln) in enumerate(self.free):
+            if ln >= n:
+                if ln == n:
+                    del self.free[i]
+                else:
+                    self.free[i] = [off + n, ln - n]
+                return off
+        return None
+
+    def release(self, off: int, n: int) -> None:
+        if n <= 0:
+            return
+        i = 0
+        while i < len(self.free) and self.free[i][0] < off:
+            i += 1
+        self.free.insert(i, [off, n])
+        if i + 1 < len(self.free) and off + n == self.free[i + 1][0]:
+            self.free[i][1] += self.free[i + 1][1]
+            del self.free[i + 1]
+        if i > 0 and self.free[i - 1][0] + self.free[i - 1][1] == off:
+            self.free[i - 1][1] += self.free[i][1]
+            del self.free[i]
+
+    @property
+    def used(self) -> int:
+        return self.size - sum(ln for _, ln in self.free)

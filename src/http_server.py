@@ -8,7 +8,9 @@ coordinator's framed-RPC API. It holds no model state — every request becomes 
     POST /v1/completions   {"model", "prompt": str | [token ids], "max_tokens", "temperature",
                             "top_p", "top_k", "seed", "stop_token_ids", "ignore_eos", "stream",
                             "logprobs": 0..20, "echo", "presence_penalty", "frequency_penalty" (-2..2),
-                            "repetition_penalty" (> 0), "logit_bias": {token id: -100..100}, <= 300 entries}
+                            "repetition_penalty" (> 0), "logit_bias": {token id: -100..100}, <= 300 entries,
+                            at most one of "allowed_token_ids": [ids], "guided_choice": [str | [ids]],
+                            "guided_regex": str}
                            stream=true answers with server-sent events ("data: {...}" chunks,
                            then "data: [DONE]"), text and token ids per chunk.
                            logprobs=N: choice.logprobs = {"tokens", "token_logprobs", "top_logprobs":
@@ -26,6 +28,11 @@ coordinator's framed-RPC API. It holds no model state — every request becomes 
     Penalties and logit_bias (both endpoints) rewrite the logits on the GPU before sampling; a bad value is a
     400, and so is a request that sets them on a model served tensor-parallel. With them, logprobs are those
     of the processed distribution (before temperature / top-k / top-p); without them nothing changes.
+    Constrained decoding (both endpoints): allowed_token_ids bars every other token at every step, guided_choice
+    yields exactly one of its choices and then EOS, guided_regex an output that fully matches the pattern (the
+    byte-level subset of src/guided.py) and then EOS. Barred tokens have logprob -inf (-9999.0 here). A malformed
+    value, two of the three at once, unsupported regex syntax, ignore_eos with a choice or a pattern, or any of
+    them on a model served tensor-parallel is a 400.
     GET  /v1/models        the coordinator's registered models
     GET  /health           200 when the coordinator answers its health RPC
     GET  /metrics          Prometheus text format (requests, errors, latency, tokens)
@@ -49,7 +56,9 @@ from src.preproc import SamplingParams
 from src.utils import setup_logging
 
 _LOGIT_PROCESSING = ("presence_penalty", "frequency_penalty", "repetition_penalty", "logit_bias")
-_SAMPLING = ("max_tokens", "temperature", "top_p", "top_k", "seed", "stop_token_ids", "ignore_eos") + _LOGIT_PROCESSING
+_GUIDED = ("allowed_token_ids", "guided_choice", "guided_regex")
+_SAMPLING = ("max_tokens", "temperature", "top_p", "top_k", "seed", "stop_token_ids", "ignore_eos") + \
+    _LOGIT_PROCESSING + _GUIDED
 _ROLES = ("system", "user", "assistant", "tool")
 MAX_LOGPROBS = 20
 
@@ -154,6 +163,14 @@ class Gateway:
         inp.setdefault("max_tokens", 16)
         # ranges and types of the penalties / bias: refused here with a 400, not by a worker after routing
         SamplingParams(**{k: inp[k] for k in _LOGIT_PROCESSING if k in inp})
+        # the same for constrained decoding (shapes, "at most one", the regex subset, ignore_eos); a text choice
+        # is tokenised by the worker: here it only has to be a non-empty string
+        chk = {k: inp[k] for k in _GUIDED + ("ignore_eos",) if k in inp}
+        if isinstance(chk.get("guided_choice"), list):
+            if any(isinstance(c, str) and not c for c in chk["guided_choice"]):
+                raise ValueError("guided_choice holds an empty string")
+            chk["guided_choice"] = [[0] if isinstance(c, str) else c for c in chk["guided_choice"]]
+        SamplingParams(**chk)
         if chat:  # logprobs: bool, top_logprobs: int
             want = body.get("logprobs")
             if want is not None and not isinstance(want, bool):

@@ -280,6 +280,33 @@ def logit_process(logits: torch.Tensor, slot: torch.Tensor, state: torch.Tensor,
     return logits
 
 
+# constrained decoding (launchers.h): the per-request caps the host compiler enforces (src/guided.py) and the arenas
+GUIDE_MAX_STATES = 16384      # states of one request's automaton
+GUIDE_MAX_EDGES = 262144      # edges of one request's automaton: twice the largest vocabulary
+GUIDE_ROWPTR_ARENA = 262144   # int32 row pointers shared by all slots
+GUIDE_EDGE_ARENA = 4194304    # (tok, next) int32 pairs shared by all slots: 32 MiB
+GUIDE_ERR_NO_EDGE = ref.GUIDE_ERR_NO_EDGE
+GUIDE_ERR_TABLE = ref.GUIDE_ERR_TABLE
+
+
+def token_guide(logits: torch.Tensor, slot: torch.Tensor, desc: torch.Tensor, rowptr: torch.Tensor,
+                edges: torch.Tensor, cur: torch.Tensor, err: torch.Tensor,
+                advance_ids: Optional[torch.Tensor] = None, lm_part: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Constrained decoding on ``logits`` [rows, vocab] bf16 IN PLACE, before the sampler reads them: every entry
+    the row's token automaton does not allow next becomes ``-inf``, an allowed entry keeps its exact bits
+    (:func:`reference.token_guide_rows` is the contract). Row r uses the tables of ``slot[r]`` (int32; < 0: the row
+    is left untouched): ``desc`` int32 [slots, 4] = (state_base, n_states, edge_base, n_edges) into the arenas
+    ``rowptr`` int32 [R] (CSR row pointers, relative to edge_base) and ``edges`` int32 [E, 2] = (tok, next);
+    ``cur`` int32 [slots] the current state and ``err`` int32 [slots] sticky error bits (GUIDE_ERR_*).
+    ``advance_ids`` int64 [rows]: the step's input tokens (the previous samples), which the state advances over
+    first. ``lm_part`` [rows, parts, 2] int32: the LM head's greedy candidates of these rows, overwritten with the
+    best allowed entry so that :func:`sample` / :func:`sample_advance` with ``lm_part`` return it."""
+    if not logits.is_cuda:
+        return ref.token_guide_rows(logits, slot, desc, rowptr, edges, cur, err, advance_ids, lm_part)
+    _kern().token_guide(logits, slot, desc, rowptr, edges, cur, err, advance_ids, lm_part)
+    return logits
+
+
 def sample_advance(logits, temperature, top_k, top_p, seeds, steps, out, lm_part, ids, pos, ctx, slots, bt, tokens,
                    cnt, n_real, block_size: int, ticket, embed=None) -> torch.Tensor:
     """:func:`sample` from the LM head's candidates (``lm_part``) fused with :func:`decode_advance`: every row's

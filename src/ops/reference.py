@@ -224,6 +224,71 @@ def logit_process_rows(logits, slot, state, params, bias_cnt, bias_ids, bias_val
     return logits
 
 
+GUIDE_ERR_NO_EDGE = 1  # err bits of token_guide: the advance token has no edge in the current state
+GUIDE_ERR_TABLE = 2    # a descriptor, state, row pointer or edge outside its bounds: the row is left untouched
+
+
+def token_guide_rows(logits, slot, desc, rowptr, edges, cur, err, advance_ids=None, lm_part=None):
+    """ops.token_guide on host tensors (the contract of csrc/kernels/token_guide.hip): row r -> slot[r] -> desc
+    (state_base, n_states, edge_base, n_edges) into rowptr / edges [E, 2]; the state advances over advance_ids[r]
+    first (no edge: err |= 1, state kept); entries outside the state's edge tokens become -inf, the others keep
+    their bits; lm_part candidates overwritten with the best allowed entry (largest value, then lowest index).
+    Anything out of bounds: err |= 2 and row, candidates and state stay untouched."""
+    vocab = logits.shape[1]
+    n_rp, n_ed = rowptr.shape[0], edges.shape[0]
+    for r in range(logits.shape[0]):
+        s = int(slot[r])
+        if s < 0 or s >= desc.shape[0]:
+            continue
+        sb, ns, eb, ne = (int(v) for v in desc[s])
+        c = int(cur[s])
+        if sb < 0 or ns < 1 or sb + ns + 1 > n_rp or eb < 0 or ne < 0 or eb + ne > n_ed or not 0 <= c < ns:
+            err[s] |= GUIDE_ERR_TABLE
+            continue
+        flags = 0
+        bad = False
+        if advance_ids is not None:
+            lo, hi = int(rowptr[sb + c]), int(rowptr[sb + c + 1])
+            if lo < 0 or hi < lo or hi > ne:
+                err[s] |= GUIDE_ERR_TABLE
+                continue
+            hit = (edges[eb + lo: eb + hi, 0].long() == int(advance_ids[r])).nonzero()
+            if hit.numel():
+                nx = int(edges[eb + lo + int(hit[0]), 1])
+                if not 0 <= nx < ns:
+                    bad = True
+                c = nx
+            else:
+                flags = GUIDE_ERR_NO_EDGE
+        if not bad:
+            lo, hi = int(rowptr[sb + c]), int(rowptr[sb + c + 1])
+            bad = lo < 0 or hi < lo or hi > ne
+        if not bad:
+            toks = edges[eb + lo: eb + hi, 0].long()
+            bad = bool(((toks < 0) | (toks >= vocab)).any())
+        if bad:
+            err[s] |= GUIDE_ERR_TABLE
+            continue
+        cur[s] = c
+        err[s] |= flags
+        allowed = torch.zeros(vocab, dtype=torch.bool)
+        allowed[toks] = True
+        logits[r, :vocab] = torch.where(allowed, logits[r, :vocab],
+                                        torch.tensor(float("-inf"), dtype=logits.dtype))
+        if lm_part is not None:
+            x = logits[r, :vocab].float()
+            ok = allowed & ~torch.isnan(x)  # a NaN never wins a comparison (sampling.hip's better())
+            x = torch.where(ok, x, torch.tensor(float("-inf")))
+            v = x.max()
+            first = ((x == v) & ok).nonzero()  # lowest allowed index holding the maximum
+            lm_part[r, :, 0] = torch.tensor(float("-inf")).view(torch.int32)
+            lm_part[r, :, 1] = 0x7fffffff
+            if first.numel():
+                lm_part[r, 0, 0] = x[int(first[0])].view(torch.int32)  # that entry's own bits (-0.0 equals +0.0)
+                lm_part[r, 0, 1] = int(first[0])
+    return logits
+
+
 def topk_softmax(gating: torch.Tensor, k: int, renorm: bool = True):
     p = torch.softmax(gating.float(), dim=-1)
     w, ids = torch.topk(p, k, dim=-1)

@@ -72,6 +72,7 @@ class TPModelRunner(ModelRunner):
     mirrors_windows = True
     # followers sample too: penalties / logit_bias would need every rank to mirror the per-sequence state
     supports_logit_processing = False
+    supports_token_guide = False  # likewise: the automaton's state would have to advance on every rank
     HDR = 8
 
     def __init__(self, model: CausalLM, pool: KVPool, cfg: EngineConfig, max_model_len: int):

@@ -93,6 +93,14 @@ class SamplingParams:
     frequency_penalty: float = 0.0
     repetition_penalty: float = 1.0
     logit_bias: Optional[Dict[int, float]] = None
+    # constrained decoding (src/guided.py compiles each to a token automaton that ops.token_guide walks on the
+    # device; every token outside the automaton's current edge set is barred, its logit -inf). At most one:
+    # allowed_token_ids: every step samples only from these ids (no end-of-sequence logic: EOS only if listed);
+    # guided_choice: token-id lists, the output is exactly one of them followed by EOS;
+    # guided_regex: the decoded output fully matches the pattern (src/guided.py: the byte-level subset), then EOS.
+    allowed_token_ids: Optional[List[int]] = None
+    guided_choice: Optional[List[List[int]]] = None
+    guided_regex: Optional[str] = None
 
     def __post_init__(self):
         if self.max_tokens < 1:
@@ -138,6 +146,45 @@ class SamplingParams:
                     raise ValueError(f"logit_bias names token {k} twice")
                 bias[k] = v
             self.logit_bias = bias or None
+        self._check_guided()
+
+    def _check_guided(self) -> None:
+        if sum(v is not None for v in (self.allowed_token_ids, self.guided_choice, self.guided_regex)) > 1:
+            raise ValueError("at most one of allowed_token_ids, guided_choice and guided_regex may be set")
+
+        def ids_of(v, name):
+            if not isinstance(v, (list, tuple)) or not v:
+                raise ValueError(f"{name} must be a non-empty list of token ids")
+            for t in v:
+                if isinstance(t, bool) or not isinstance(t, int) or t < 0:
+                    raise ValueError(f"{name}: {t!r} is not a token id")
+            return list(v)
+
+        if self.allowed_token_ids is not None:
+            ids = ids_of(self.allowed_token_ids, "allowed_token_ids")
+            if len(set(ids)) != len(ids):
+                raise ValueError("allowed_token_ids names a token twice")
+            self.allowed_token_ids = ids
+        if self.guided_choice is not None:
+            from src.guided import GUIDE_MAX_CHOICE_TOKENS, GUIDE_MAX_CHOICES
+
+            if not isinstance(self.guided_choice, (list, tuple)) or not (1 <= len(self.guided_choice) <= GUIDE_MAX_CHOICES):
+                raise ValueError(f"guided_choice must be a list of 1..{GUIDE_MAX_CHOICES} token-id lists")
+            seen, out = set(), []
+            for c in self.guided_choice:
+                c = tuple(ids_of(c, "guided_choice"))
+                if c not in seen:  # duplicates removed, the first occurrence's place kept
+                    seen.add(c)
+                    out.append(list(c))
+            if sum(len(c) for c in out) > GUIDE_MAX_CHOICE_TOKENS:
+                raise ValueError(f"guided_choice holds more than {GUIDE_MAX_CHOICE_TOKENS} tokens")
+            self.guided_choice = out
+        if self.guided_regex is not None:
+            from src.guided import parse_regex
+
+            parse_regex(self.guided_regex)  # ValueError naming the position for anything outside the subset
+        if self.ignore_eos and (self.guided_choice is not None or self.guided_regex is not None):
+            raise ValueError("guided_choice / guided_regex cannot be combined with ignore_eos")
 
     @property
     def greedy(self) -> bool:
@@ -148,6 +195,11 @@ class SamplingParams:
         """Any penalty or bias set: the request's rows go through ops.logit_process before sampling."""
         return bool(self.presence_penalty != 0.0 or self.frequency_penalty != 0.0 or self.repetition_penalty != 1.0
                     or self.logit_bias)
+
+    @property
+    def guided(self) -> bool:
+        """Constrained decoding asked for: the request's rows go through ops.token_guide before sampling."""
+        return self.allowed_token_ids is not None or self.guided_choice is not None or self.guided_regex is not None
 
 
 @dataclass
@@ -160,7 +212,7 @@ class GenerationInputs:
 
 _SAMPLING_KEYS = ("max_tokens", "temperature", "top_k", "top_p", "seed", "ignore_eos", "stop_token_ids",
                   "logprobs", "prompt_logprobs", "presence_penalty", "frequency_penalty", "repetition_penalty",
-                  "logit_bias")
+                  "logit_bias", "allowed_token_ids", "guided_choice", "guided_regex")
 
 
 def normalize_request(inputs: Any, tokenizer=None, max_model_len: Optional[int] = None) -> GenerationInputs:
@@ -185,13 +237,29 @@ def normalize_request(inputs: Any, tokenizer=None, max_model_len: Optional[int] 
     vs = getattr(tok, "vocab_size", None)
     if vs and (min(ids) < 0 or max(ids) >= vs):
         raise ValueError("prompt token id out of vocabulary range")
-    sp = SamplingParams(**{k: inputs[k] for k in _SAMPLING_KEYS if k in inputs})
+    fields = {k: inputs[k] for k in _SAMPLING_KEYS if k in inputs}
+    gc = fields.get("guided_choice")
+    if isinstance(gc, (list, tuple)) and any(isinstance(c, str) for c in gc):
+        # text choices: the canonical tokenisation without BOS; the engine API only ever sees ids
+        fields["guided_choice"] = [_encode_plain(tok, c) if isinstance(c, str) else c for c in gc]
+    sp = SamplingParams(**fields)
     if vs and sp.logit_bias and max(sp.logit_bias) >= vs:
         raise ValueError("logit_bias token id out of vocabulary range")
+    if vs and sp.guided:
+        named = sp.allowed_token_ids or [t for c in sp.guided_choice or () for t in c]
+        if named and max(named) >= vs:
+            raise ValueError("allowed_token_ids / guided_choice token id out of vocabulary range")
     if max_model_len is not None and len(ids) + sp.max_tokens > max_model_len:
         raise ValueError(f"prompt ({len(ids)}) + max_tokens ({sp.max_tokens}) exceeds max_model_len {max_model_len}")
     return GenerationInputs(prompt_token_ids=ids, sampling=sp, prompt=prompt,
                             return_text=bool(inputs.get("return_text", True)))
+
+
+def _encode_plain(tok, text: str) -> List[int]:
+    """``text`` as token ids without BOS or any other special token."""
+    if isinstance(tok, ByteTokenizer):
+        return tok.encode(text, add_bos=False)
+    return list(tok.encode(text, add_special_tokens=False))
 
 
 _POOL_TOKENIZERS: Dict[Tuple[Optional[str], int], Any] = {}
