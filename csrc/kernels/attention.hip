@@ -388,13 +388,23 @@ static_assert(V3_LDS <= 160 * 1024, "one v3 workgroup per CU");
 // row straight into this step's LDS image. The separate RoPE/KV-write and RMSNorm kernels of
 // the decode layer disappear. Everything the prologue needs arrives by LDS-DMA, staged in the
 // merge area (idle at a task start), so no ordinary load stalls the chunk stream.
+//
+// Argument order: the file is built with kernarg preload, which hands a wave the head of the argument list in
+// SGPRs at launch — 14 dwords (16 user SGPRs less the kernarg pointer), whole arguments only, so never a part
+// of the by-value struct. First comes what the task loop and the scalar loads of the context length and the block
+// ids need (the entry's dependent chain), then `head` (bit 0: fz.ts set, bits 8..: fz.sk) and the cache pointers of
+// the first chunk's DMA; the rest (outputs, the query, the fused prologue's operands) is loaded from the kernarg
+// segment as before, in flight together with those scalar loads.
 template <int G, bool FUSED, int KV_AUX>
 __global__ void __launch_bounds__(256, 1) attn_decode_v3_kernel(
-    bf16_t* __restrict__ out, float* __restrict__ part_o, float* __restrict__ part_ml, int* __restrict__ counters,
-    const bf16_t* __restrict__ q, int64_t q_stride, bf16_t* __restrict__ k_cache, bf16_t* __restrict__ v_cache,
-    const int* __restrict__ block_tables, int bt_stride, const int* __restrict__ ctx_lens, int num_seqs, int hq,
-    int hkv, float scale_log2, int maxp, int cpp, AttnDecodeFuse fz, const int64_t* __restrict__ slot_mapping) {
+    const int* __restrict__ block_tables, const int* __restrict__ ctx_lens, int bt_stride, int num_seqs, int hkv,
+    int maxp, int cpp, uint32_t head, bf16_t* __restrict__ k_cache, bf16_t* __restrict__ v_cache, int hq,
+    float scale_log2, AttnDecodeFuse fz, const int64_t* __restrict__ slot_mapping, const bf16_t* __restrict__ q,
+    int64_t q_stride, bf16_t* __restrict__ out, float* __restrict__ part_o, float* __restrict__ part_ml,
+    int* __restrict__ counters) {
   constexpr int QI = (G * 256 + 1023) / 1024;  // LDS-DMA instructions for the query rows
+  const bool has_ts = (head & 1u) != 0;
+  const int fsk = (int)(head >> 8);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* ml = reinterpret_cast<float*>(smem + 2 * V3_BUF);
   float* ob = reinterpret_cast<float*>(smem + 2 * V3_BUF + V3_ML);
@@ -408,7 +418,7 @@ __global__ void __launch_bounds__(256, 1) attn_decode_v3_kernel(
   // diagnostics (bench/micro_attn_timeline.py): [entry, first chunk landed, prologue done, stream done,
   // end, xcc] of the workgroup's LAST task, s_memrealtime (100 MHz)
   long long tsv[5] = {0, 0, 0, 0, 0};
-  if (fz.ts != nullptr) tsv[0] = __builtin_amdgcn_s_memrealtime();
+  if (has_ts) tsv[0] = __builtin_amdgcn_s_memrealtime();
 
 #pragma unroll 1
   for (int t = blockIdx.x; t < n_tasks; t += gridDim.x) {
@@ -455,8 +465,8 @@ __global__ void __launch_bounds__(256, 1) attn_decode_v3_kernel(
     const bool has_new = FUSED && c1 == nch;  // this part holds the step's new token (key ctx-1)
     char* fa = smem + 2 * V3_BUF;            // FUSED staging (merge area, idle at a task start)
     // slab rows x 128 fp32: [s][q heads] then [s][k, v]; a part without the new token stages only the q rows
-    const int frows = fz.sk * (G + 2);
-    const int qrows = fz.sk * G;
+    const int frows = fsk * (G + 2);
+    const int qrows = fsk * G;
     const int fs_off = ((frows + 1) / 2) * 1024;
     // Issue order: the prologue's small operands first, then chunk c0, so the prologue (FUSED: slab
     // sum, norm scale, RoPE, KV write) runs while the chunk streams in; only a counted vmcnt separates
@@ -517,7 +527,7 @@ __global__ void __launch_bounds__(256, 1) attn_decode_v3_kernel(
       const uint32_t cs = lds_addr(fa + fs_off + 1024);
       auto slab_sum = [&](int j, int d) {  // staged row of split sl: q head j at sl * G + j, k / v at qrows + 2 sl
         float v = 0.f;
-        for (int sl = 0; sl < fz.sk; ++sl)
+        for (int sl = 0; sl < fsk; ++sl)
           v += lds_ld32(lds_addr(fa + (((j < G ? sl * G : qrows + 2 * sl - G) + j) * D + d) * 4));
         return v * rn;
       };
@@ -557,7 +567,7 @@ __global__ void __launch_bounds__(256, 1) attn_decode_v3_kernel(
       // landed before the patch is written). Waves otherwise run decoupled through the chunks instead
       // of at the pace of the slowest wave's loads.
       if (c == c0 || (FUSED && has_new && c + 1 == c1)) __builtin_amdgcn_s_barrier();
-      if (fz.ts != nullptr && c == c0) tsv[1] = __builtin_amdgcn_s_memrealtime();
+      if (has_ts && c == c0) tsv[1] = __builtin_amdgcn_s_memrealtime();
       const char* base = smem + b * V3_BUF;
       if constexpr (FUSED) {
         if (has_new && c == c0) {
@@ -592,7 +602,7 @@ __global__ void __launch_bounds__(256, 1) attn_decode_v3_kernel(
         for (int kk = 0; kk < 8; ++kk)
           qf[kk] = row < G ? as_frag(*reinterpret_cast<const uint4*>(smem + V3_CHUNK + row * 256 + (2 * kk + h) * 16))
                            : zero_frag();
-        if (fz.ts != nullptr) tsv[2] = __builtin_amdgcn_s_memrealtime();
+        if (has_ts) tsv[2] = __builtin_amdgcn_s_memrealtime();
       }
       {
         const int kb = c * DEC_KEYS + 32 * wave;  // keys >= ctx: clamped rows, masked to -inf
@@ -603,7 +613,7 @@ __global__ void __launch_bounds__(256, 1) attn_decode_v3_kernel(
       // buffer b is refilled (next iteration's DMA, this wave's own rows) only after this wave's reads
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     }
-    if (fz.ts != nullptr) tsv[3] = __builtin_amdgcn_s_memrealtime();
+    if (has_ts) tsv[3] = __builtin_amdgcn_s_memrealtime();
 
     // merge the 4 waves' (m, l, O) through LDS
     if (row < G) {
@@ -719,7 +729,7 @@ __global__ void __launch_bounds__(256, 1) attn_decode_v3_kernel(
     }
     lds_barrier();  // merge area and buffers are reused by the next task
   }
-  if (fz.ts != nullptr && tid == 0) {
+  if (has_ts && tid == 0) {
     tsv[4] = __builtin_amdgcn_s_memrealtime();
     int xcc;
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(xcc));
@@ -841,10 +851,11 @@ hipError_t launch_attn_decode(bf16_t* out, float* part_o, float* part_ml, int* c
     // kv_once: the K / V chunk stream is loaded as once-read data (nt). A launch argument, not a process-wide
     // switch: the engine leaves it on also for batches whose sequences share prefix blocks (read by several
     // workgroups in one step: bench/kv_eviction_bench.py measured no loss, docs/performance.md); false is the A/B side
-#define D3_LAUNCH(GG, FU, AUX, FZ, SM)                                                                           \
-  hipLaunchKernelGGL((attn_decode_v3_kernel<GG, FU, AUX>), grid, block, V3_LDS, s, out, part_o, part_ml, counters, \
-                     q, q_stride, k_cache, v_cache, block_tables, bt_stride, ctx_lens, num_seqs, hq, hkv, sl2,   \
-                     maxp3, cpp, FZ, SM)
+#define D3_LAUNCH(GG, FU, AUX, FZ, SM)                                                                            \
+  hipLaunchKernelGGL((attn_decode_v3_kernel<GG, FU, AUX>), grid, block, V3_LDS, s, block_tables, ctx_lens,        \
+                     bt_stride, num_seqs, hkv, maxp3, cpp,                                                        \
+                     (uint32_t)((FZ).ts != nullptr ? 1u : 0u) | ((uint32_t)(FZ).sk << 8), k_cache, v_cache, hq,   \
+                     sl2, FZ, SM, q, q_stride, out, part_o, part_ml, counters)
 #define D3_CASE(GG)                                                                \
   case GG:                                                                        \
     if (fz && kv_once)                                                            \

@@ -54,6 +54,18 @@ __device__ __forceinline__ void glds16(const void* src, char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((global_cvoid*)src, (lds_void*)lds_wave_base, 16, 0, AUX);
 }
 
+// The kernel's `head` word: everything small that the entry reads before its first LDS-DMA, in one preloaded
+// dword (see gemm_decode_kernel): flags, the EPI 4 / 6 statistics tile count and the split-K count (grid y).
+constexpr uint32_t HEAD_TILED = 1u;   // fz.tiled
+constexpr uint32_t HEAD_TS = 2u;      // fz.ts != nullptr
+constexpr uint32_t HEAD_ROWS = 4u;    // fz.grp_rows != nullptr
+constexpr int HEAD_TILES_SHIFT = 8;   // 9 bits: fz.ssp_tiles (<= DECODE_SSP_MAX_TILES = 256)
+constexpr uint32_t HEAD_TILES_MASK = 0x1ffu;
+constexpr int HEAD_NY_SHIFT = 20;     // 12 bits: split-K slices
+constexpr int HEAD_NY_MAX = 4095;
+static_assert(DECODE_SSP_MAX_TILES <= (int)HEAD_TILES_MASK && HEAD_TILES_SHIFT + 9 <= HEAD_NY_SHIFT,
+              "tile count fits its field");
+
 template <int N>
 __device__ __forceinline__ void wait_vm() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
@@ -151,8 +163,9 @@ __device__ __forceinline__ uint32_t car_tile_exchange(f4 (&own)[EPT], const Gemm
 // so it should not displace the activations / KV in L2 and MALL (MI355X_MICROARCH.md "nt-weights").
 template <int WR, int EPI, int S, bool NT, int KC, int XR, int SKC = 0>
 __device__ __forceinline__ void gd_body(char* smem, void* Yv, int64_t ldy, const bf16_t* __restrict__ X, int64_t ldx,
-                                        const bf16_t* __restrict__ W, int M, int N_out, int K,
-                                        const GemmDecodeFuse& fz, const int bx, const int by, const int ny) {
+                                        const bf16_t* __restrict__ W, int M, int N_out, int K, const uint32_t head,
+                                        const int* __restrict__ grp_off, const float* __restrict__ ssp_in,
+                                        const GemmDecodeFuse& fz, const int bx, const int by) {
   constexpr int ROWB = KC * 2;                 // bytes per image row
   constexpr int CPR = KC / 8;                  // 16-byte chunks per row
   constexpr int RPP = 64 / CPR;                // rows per 1-KiB DMA piece
@@ -173,18 +186,21 @@ __device__ __forceinline__ void gd_body(char* smem, void* Yv, int64_t ldy, const
   static_assert((S - 1) * PER_WAVE <= 63 && S >= 2, "vmcnt field is 6 bits");
   static_assert(S * SLOT <= 160 * 1024, "ring exceeds LDS");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ny = (int)(head >> HEAD_NY_SHIFT);
+  const int ssp_tiles = (int)((head >> HEAD_TILES_SHIFT) & HEAD_TILES_MASK);
+  const bool tiled = (head & HEAD_TILED) != 0, gather = (head & HEAD_ROWS) != 0;
   int r0 = 0;
-  if (fz.grp_off != nullptr) {
+  if (grp_off != nullptr) {
     // grouped (MoE) form: blockIdx.z = group; its rows of X/Y are [off[e], off[e+1]) of the
     // token-sorted activations, its weights those of expert e / grp_div (an expert with more rows than
     // the image is split into grp_div segments). Empty groups cost nothing.
     // (The launcher picks XR from the largest possible group.) With grp_rows the activation rows are
     // gathered from the token order on the fly (no separate gather launch).
     const int e = blockIdx.z;
-    r0 = fz.grp_off[e];
-    M = min(fz.grp_off[e + 1] - r0, XR);
+    r0 = grp_off[e];
+    M = min(grp_off[e + 1] - r0, XR);
     if (M <= 0) return;
-    if (fz.grp_rows == nullptr) X += (int64_t)r0 * ldx;
+    if (!gather) X += (int64_t)r0 * ldx;
     W += (int64_t)(e / fz.grp_div) * fz.grp_wstride;
     Yv = reinterpret_cast<char*>(Yv) + (int64_t)r0 * ldy * (EPI == 2 || EPI == 3 ? 4 : 2);
   }
@@ -196,9 +212,41 @@ __device__ __forceinline__ void gd_body(char* smem, void* Yv, int64_t ldy, const
   const int k0 = c_lo * KC;
   const int nch = (by + 1) * tch / ny - c_lo;
 
+  // EPI 4: this thread's share of the producer's per-tile sums of squares (row tid % RR, tiles
+  // tid / RR + NSL * i), loaded before any LDS-DMA and first used in the epilogue, so no wait lands
+  // inside the weight stream. Index clamped, masked later (no branches).
+  constexpr int NSL = NTH / RR;                // tile slices
+  constexpr int MAXT = RR <= 32 ? DECODE_SSP_MAX_TILES : DECODE_SSP_MAX_TILES_WIDE;
+  constexpr int NPF = (MAXT + NSL - 1) / NSL;  // prefetched statistics per thread (<= MAXT tiles)
+  float ssv[EPI == 4 || EPI == 6 ? NPF : 1];
+  if constexpr (EPI == 4 || EPI == 6) {
+#pragma unroll
+    for (int i = 0; i < NPF; ++i)
+      ssv[i] = ssp_in[min(tid / RR + NSL * i, ssp_tiles - 1) * SSP_LD + (tid % RR)];
+  }
+
   // Per-lane source rows for this wave's DMA pieces (fixed across chunks).
   const bf16_t* src[PER_WAVE];
   bool isw[PER_WAVE];
+  const int64_t wstep = tiled ? (int64_t)(WR / RPP) * 512 : KC;  // W elements per K-chunk
+  // piece p of chunk c; a piece is all-weight or all-activation rows: wave-uniform branch
+  auto issue_piece = [&](int c, int p) {
+    char* slot = smem + (c % S) * SLOT;
+    if (isw[p]) {
+      if (NT)
+        glds16<2>(src[p] + (int64_t)c * wstep, slot + (wave + 4 * p) * 1024);
+      else
+        glds16<0>(src[p] + (int64_t)c * wstep, slot + (wave + 4 * p) * 1024);
+    } else {
+      glds16<0>(src[p] + (int64_t)c * KC, slot + (wave + 4 * p) * 1024);
+    }
+  };
+  auto issue = [&](int c) {
+#pragma unroll
+    for (int p = 0; p < PER_WAVE; ++p) issue_piece(c, p);
+  };
+  // Everything the addresses need arrives in SGPRs with the wave (the kernel's preloaded arguments), so chunk 0's
+  // piece p goes out as soon as its own address exists, not after the whole address table (same issue order).
 #pragma unroll
   for (int p = 0; p < PER_WAVE; ++p) {
     const int piece = wave + 4 * p;
@@ -211,44 +259,16 @@ __device__ __forceinline__ void gd_body(char* smem, void* Yv, int64_t ldy, const
       base = W + (int64_t)grow * K;
     } else {
       const int xr = min(row - WR, M - 1);
-      base = fz.grp_rows != nullptr ? X + (int64_t)(fz.grp_rows[r0 + xr] / fz.grp_k) * ldx : X + (int64_t)xr * ldx;
+      base = gather ? X + (int64_t)(fz.grp_rows[r0 + xr] / fz.grp_k) * ldx : X + (int64_t)xr * ldx;
     }
     src[p] = base + k0 + lch * 8;
-    if (row < WR && fz.tiled) {
+    if (row < WR && tiled) {
       // pre-packed weights (gd_pack_weights): tile bx's K-chunk c is WR/RPP contiguous 1-KiB pieces
       // already in LDS-image order (rows, swizzle and all), so each piece is one linear 1-KiB read
       src[p] = W + ((int64_t)bx * (K / KC) + k0 / KC) * (WR / RPP) * 512 + piece * 512 + lane * 8;
     }
     isw[p] = row < WR;
-  }
-  const int64_t wstep = fz.tiled ? (int64_t)(WR / RPP) * 512 : KC;  // W elements per K-chunk
-  auto issue = [&](int c) {
-    char* slot = smem + (c % S) * SLOT;
-#pragma unroll
-    for (int p = 0; p < PER_WAVE; ++p) {
-      // a piece is all-weight or all-activation rows: wave-uniform branch
-      if (isw[p]) {
-        if (NT)
-          glds16<2>(src[p] + (int64_t)c * wstep, slot + (wave + 4 * p) * 1024);
-        else
-          glds16<0>(src[p] + (int64_t)c * wstep, slot + (wave + 4 * p) * 1024);
-      } else {
-        glds16<0>(src[p] + (int64_t)c * KC, slot + (wave + 4 * p) * 1024);
-      }
-    }
-  };
-
-  // EPI 4: this thread's share of the producer's per-tile sums of squares (row tid % RR, tiles
-  // tid / RR + NSL * i), loaded before any LDS-DMA and first used in the epilogue, so no wait lands
-  // inside the weight stream. Index clamped, masked later (no branches).
-  constexpr int NSL = NTH / RR;                // tile slices
-  constexpr int MAXT = RR <= 32 ? DECODE_SSP_MAX_TILES : DECODE_SSP_MAX_TILES_WIDE;
-  constexpr int NPF = (MAXT + NSL - 1) / NSL;  // prefetched statistics per thread (<= MAXT tiles)
-  float ssv[EPI == 4 || EPI == 6 ? NPF : 1];
-  if constexpr (EPI == 4 || EPI == 6) {
-#pragma unroll
-    for (int i = 0; i < NPF; ++i)
-      ssv[i] = fz.ssp_in[min(tid / RR + NSL * i, fz.ssp_tiles - 1) * SSP_LD + (tid % RR)];
+    if (nch > 0) issue_piece(0, p);
   }
 
   f4 acc[MT][NTW];
@@ -258,7 +278,7 @@ __device__ __forceinline__ void gd_body(char* smem, void* Yv, int64_t ldy, const
     for (int b = 0; b < NTW; ++b) acc[a][b] = f4{0.f, 0.f, 0.f, 0.f};
 
 #pragma unroll
-  for (int c = 0; c < S - 1; ++c)
+  for (int c = 1; c < S - 1; ++c)
     if (c < nch) issue(c);
 
   const int fr = lane & 15, kg = lane >> 4;
@@ -448,7 +468,7 @@ __device__ __forceinline__ void gd_body(char* smem, void* Yv, int64_t ldy, const
     float* rs = part + NTH;
     float acc_ss = 0.f;
 #pragma unroll
-    for (int i = 0; i < NPF; ++i) acc_ss += tid / RR + NSL * i < fz.ssp_tiles ? ssv[i] : 0.f;
+    for (int i = 0; i < NPF; ++i) acc_ss += tid / RR + NSL * i < ssp_tiles ? ssv[i] : 0.f;
     part[tid] = acc_ss;  // tid = slice * RR + row
     __syncthreads();
     if (tid < RR) {
@@ -618,16 +638,23 @@ __device__ __forceinline__ void gd_body(char* smem, void* Yv, int64_t ldy, const
   }
 }
 
+// Argument order: the file is built with kernarg preload, which hands a wave the head of the argument list in
+// SGPRs at launch — 14 dwords (16 user SGPRs less the kernarg pointer), whole arguments only, so never a part
+// of the by-value struct. The first 14 dwords are therefore exactly what the entry reads before its first
+// LDS-DMA (W, X, ldx, K, M, N_out, the `head` word, fz.grp_off and fz.ssp_in, lifted out of fz by the launcher);
+// the outputs and the struct (epilogue operands) follow and are loaded from the kernarg segment as before.
 template <int WR, int EPI, int S, bool NT, int KC, int XR, int SKC = 0>
-__global__ void __launch_bounds__(NTH) gemm_decode_kernel(void* __restrict__ Yv, int64_t ldy,
-                                                          const bf16_t* __restrict__ X, int64_t ldx,
-                                                          const bf16_t* __restrict__ W, int M, int N_out, int K,
-                                                          GemmDecodeFuse fz) {
+__global__ void __launch_bounds__(NTH) gemm_decode_kernel(const bf16_t* __restrict__ W, const bf16_t* __restrict__ X,
+                                                          int64_t ldx, int K, int M, int N_out, uint32_t head,
+                                                          const int* __restrict__ grp_off,
+                                                          const float* __restrict__ ssp_in, void* __restrict__ Yv,
+                                                          int64_t ldy, GemmDecodeFuse fz) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   long long t0 = 0;
-  if (fz.ts != nullptr) t0 = __builtin_amdgcn_s_memrealtime();
-  gd_body<WR, EPI, S, NT, KC, XR, SKC>(smem, Yv, ldy, X, ldx, W, M, N_out, K, fz, blockIdx.x, blockIdx.y, gridDim.y);
-  if (fz.ts != nullptr && threadIdx.x == 0) {  // diagnostics only (bench/micro_gd_timeline.py)
+  if (head & HEAD_TS) t0 = __builtin_amdgcn_s_memrealtime();
+  gd_body<WR, EPI, S, NT, KC, XR, SKC>(smem, Yv, ldy, X, ldx, W, M, N_out, K, head, grp_off, ssp_in, fz, blockIdx.x,
+                                       blockIdx.y);
+  if ((head & HEAD_TS) && threadIdx.x == 0) {  // diagnostics only (bench/micro_gd_timeline.py)
     const long long t1 = __builtin_amdgcn_s_memrealtime();
     const int wg = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     int xcc;
@@ -652,12 +679,17 @@ static hipError_t launch_gd_s(void* Y, int64_t ldy, const bf16_t* X, int64_t ldx
                                                              gemm_decode_kernel<WR, EPI, S, false, KC, XR, SKC>, NTH,
                                                              lds);
   const dim3 grid(N_out / ((EPI == 1 || EPI == 4 || EPI == 6) ? WR / 2 : WR), sk, fz.grp_n);
+  // launch_gemm_decode bounds sk and fz.ssp_tiles to their fields
+  const uint32_t head = (fz.tiled ? HEAD_TILED : 0u) | (fz.ts != nullptr ? HEAD_TS : 0u) |
+                        (fz.grp_rows != nullptr ? HEAD_ROWS : 0u) |
+                        ((uint32_t)((EPI == 4 || EPI == 6) ? fz.ssp_tiles : 0) << HEAD_TILES_SHIFT) |
+                        ((uint32_t)sk << HEAD_NY_SHIFT);
   if (nt)
-    hipLaunchKernelGGL((gemm_decode_kernel<WR, EPI, S, true, KC, XR, SKC>), grid, dim3(NTH), lds, s, Y, ldy, X, ldx,
-                       W, M, N_out, K, fz);
+    hipLaunchKernelGGL((gemm_decode_kernel<WR, EPI, S, true, KC, XR, SKC>), grid, dim3(NTH), lds, s, W, X, ldx, K, M,
+                       N_out, head, fz.grp_off, fz.ssp_in, Y, ldy, fz);
   else
-    hipLaunchKernelGGL((gemm_decode_kernel<WR, EPI, S, false, KC, XR, SKC>), grid, dim3(NTH), lds, s, Y, ldy, X,
-                       ldx, W, M, N_out, K, fz);
+    hipLaunchKernelGGL((gemm_decode_kernel<WR, EPI, S, false, KC, XR, SKC>), grid, dim3(NTH), lds, s, W, X, ldx, K,
+                       M, N_out, head, fz.grp_off, fz.ssp_in, Y, ldy, fz);
   return hipGetLastError();
 }
 
@@ -741,7 +773,8 @@ hipError_t launch_gemm_decode(void* Y, int64_t ldy, const bf16_t* X, int64_t ldx
                               int K, int mode, int wr, int kc, int sk, bool nt, const GemmDecodeFuse& fz,
                               hipStream_t s) {
   if (M <= 0) return hipSuccess;
-  if (M > 128 || sk < 1 || (mode != 2 && mode != 3 && mode != 6 && sk != 1)) return hipErrorInvalidValue;
+  if (M > 128 || sk < 1 || sk > HEAD_NY_MAX || (mode != 2 && mode != 3 && mode != 6 && sk != 1))
+    return hipErrorInvalidValue;
   if (fz.amax != nullptr && (mode != 0 || fz.amax_parts < 1 ||
                              ((reinterpret_cast<uintptr_t>(Y) | (uintptr_t)(ldy * 2)) & 15)))
     return hipErrorInvalidValue;  // candidates come with mode 0's 16-byte store path

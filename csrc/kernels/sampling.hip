@@ -141,13 +141,16 @@ __device__ __forceinline__ ArgMax row_argmax(const bf16_t* row, int lo, int hi, 
 // slice's (max, index) goes to part[r][split] with write-through stores and the slice's last arriver (agent-
 // scope ticket cnt[r], re-armed) picks the row's winner — MI355X_MICROARCH.md inter-workgroup table, first
 // row. A sampled (non-greedy) row is handled whole by split 0, the others exit.
-__global__ void __launch_bounds__(SNT) sample_kernel(int64_t* __restrict__ out, const bf16_t* __restrict__ logits,
-                                                     int64_t stride, int vocab, const float* __restrict__ temperature,
+// Argument order: the file is built with kernarg preload (the first 14 argument dwords arrive in SGPRs with the
+// wave), so what is read before the first load of a candidate or a logit comes first; the outputs, the draw's
+// seeds and the advance follow.
+__global__ void __launch_bounds__(SNT) sample_kernel(const float* __restrict__ temperature,
                                                      const int* __restrict__ top_k, const float* __restrict__ top_p,
-                                                     const int64_t* __restrict__ seeds,
+                                                     const uint32_t* __restrict__ lm_part, int lm_parts, int vocab,
+                                                     const bf16_t* __restrict__ logits, int64_t stride,
+                                                     int64_t* __restrict__ out, const int64_t* __restrict__ seeds,
                                                      const int64_t* __restrict__ steps, uint32_t* __restrict__ part,
-                                                     int* __restrict__ cnt, const uint32_t* __restrict__ lm_part,
-                                                     int lm_parts, SampleAdvance adv) {
+                                                     int* __restrict__ cnt, SampleAdvance adv) {
   __shared__ ArgMax red[SNT / 64];
   __shared__ float redf[SNT / 64];
   __shared__ float hist[256];
@@ -330,8 +333,8 @@ hipError_t launch_sample(int64_t* out, const bf16_t* logits, int64_t stride, int
     return hipErrorInvalidValue;
   // with the LM head's candidates a greedy row is one short reduction: no split (a sampled row is whole anyway)
   if (lm_part != nullptr) splits = 1;
-  hipLaunchKernelGGL(sample_kernel, dim3(rows, splits), dim3(SNT), 0, s, out, logits, stride, vocab, temperature,
-                     top_k, top_p, seeds, steps, part, cnt, lm_part, lm_parts, adv);
+  hipLaunchKernelGGL(sample_kernel, dim3(rows, splits), dim3(SNT), 0, s, temperature, top_k, top_p, lm_part, lm_parts,
+                     vocab, logits, stride, out, seeds, steps, part, cnt, adv);
   return hipGetLastError();
 }
 

@@ -29,6 +29,10 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 KERNELS = ["norm_act", "rope_cache", "attention", "sampling", "logit_process", "token_guide", "moe", "gemm_decode",
            "decode_step", "allreduce"]
 CONTRACT_ON = {"attention", "gemm_decode"}
+# the decode step's kernels get the head of their argument list in SGPRs at wave launch (gfx950 kernarg preload:
+# 16 user SGPRs, 14 of them argument dwords); their signatures are ordered for it
+PRELOAD_ON = {"attention", "gemm_decode", "sampling"}
+PRELOAD_FLAGS = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 
 
 def _torch_paths():
@@ -71,8 +75,9 @@ def build_kernels(force: bool = False, jobs: int = 8, verbose: bool = False) -> 
         if force or _newer(obj, [src] + hdrs + [os.path.abspath(__file__)]):
             # the decode kernels fuse multiply-adds per source expression only (not across statements)
             contract = ["-ffp-contract=on"] if k in CONTRACT_ON else []
-            jobs_list.append([HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", *contract, "-I",
-                              CSRC, "-c", src, "-o", obj])
+            preload = PRELOAD_FLAGS if k in PRELOAD_ON else []
+            jobs_list.append([HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", *contract, *preload,
+                              "-I", CSRC, "-c", src, "-o", obj])
     bsrc = os.path.join(CSRC, "bindings.cpp")
     bobj = os.path.join(OBJ, "bindings.o")
     objs.append(bobj)
