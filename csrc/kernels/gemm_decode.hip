@@ -80,6 +80,18 @@ __device__ __forceinline__ int swz(int r) {
   else return (r ^ (r >> 1)) & 3;  // 64-byte rows
 }
 
+// silu(v) * u = v / (1 + e^-v) * u. The fast exp (exp2 of a scaled argument, v_exp_f32) overflows to +inf for
+// -v > 88.72, where the quotient would flush to -0 although v e^v u can still be a normal number (|v e^v| up to
+// 2.6e-37): there 1 + e^-v == e^-v in fp32, so the result is (v u) e^v with the exponent lifted by 64 into the
+// instruction's normal range and taken back by an exact power of two. Every other v keeps its bits.
+__device__ __forceinline__ float silu_mul(float v, float u) {
+  const float e = __expf(-v);
+  float r = v / (1.f + e) * u;
+  if (__float_as_uint(e) == 0x7f800000u)
+    r = (v * u) * __builtin_amdgcn_exp2f(__builtin_fmaf(v, 0x1.715476p+0f, 64.f)) * 0x1p-64f;
+  return r;
+}
+
 }  // namespace gd
 
 using namespace gd;
@@ -547,7 +559,7 @@ __device__ __forceinline__ void gd_body(char* smem, void* Yv, int64_t ldy, const
       if (e < RR * NO && m < M) {
         const float r = rsv[m];
         const float gv = g[i] * r, uv = u[i] * r;
-        reinterpret_cast<bf16_t*>(Yv)[(int64_t)m * ldy + n0 + j] = f2bf(gv / (1.f + __expf(-gv)) * uv);
+        reinterpret_cast<bf16_t*>(Yv)[(int64_t)m * ldy + n0 + j] = f2bf(silu_mul(gv, uv));
       }
     }
     return;
@@ -629,7 +641,7 @@ __device__ __forceinline__ void gd_body(char* smem, void* Yv, int64_t ldy, const
         v *= r;
         u *= r;
       }
-      v = v / (1.f + __expf(-v)) * u;
+      v = silu_mul(v, u);
     }
     if (EPI == 2)
       reinterpret_cast<float*>(Yv)[((int64_t)by * M + m) * ldy + n0 + j] = v;
