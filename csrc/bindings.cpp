@@ -466,6 +466,51 @@ void token_guide(Tensor logits, Tensor slot, Tensor desc, Tensor rowptr, Tensor 
                                   cur_stream()));
 }
 
+// Embedding pooling (pooling.hip): hidden bf16 [T, H] (row stride allowed); segs int32 [S, 8]; acc fp32 [slots, H]
+// (optional: only mean pooling reads or writes it); out fp32 [S, H]; part fp32 [P, H] and tickets int32 [>= S]
+// (optional, both or neither: the scratch of segments split over max_parts > 1 workgroups). The launcher itself
+// refuses H % 8 != 0, a bad stride, bad dims and a bad max_parts.
+void pool_embed(Tensor out, c10::optional<Tensor> acc, Tensor hidden, Tensor segs, int64_t dims, bool normalize,
+                c10::optional<Tensor> part, c10::optional<Tensor> tickets, int64_t max_parts) {
+  CHK_CUDA(hidden);
+  CHK_BF16(hidden);
+  TORCH_CHECK(hidden.dim() == 2 && hidden.stride(1) == 1, "pool_embed: hidden bf16 [T, H] with contiguous rows");
+  const int64_t T = hidden.size(0), H = hidden.size(1);
+  TORCH_CHECK(T < (int64_t)1 << 31 && H < (int64_t)1 << 31, "pool_embed: hidden too large");
+  TORCH_CHECK(segs.is_cuda() && segs.scalar_type() == at::kInt && segs.is_contiguous() && segs.dim() == 2 &&
+                  segs.size(1) == 8, "pool_embed: segs int32 [S, 8]");
+  const int64_t S = segs.size(0);
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat && out.is_contiguous() && out.dim() == 2 &&
+                  out.size(0) >= S && out.size(1) == H, "pool_embed: out fp32 [S, H]");
+  float* ap = nullptr;
+  int64_t slots = 0;
+  if (acc.has_value()) {
+    TORCH_CHECK(acc->is_cuda() && acc->scalar_type() == at::kFloat && acc->is_contiguous() && acc->dim() == 2 &&
+                    acc->size(1) == H && acc->size(0) < (int64_t)1 << 31, "pool_embed: acc fp32 [slots, H]");
+    ap = acc->data_ptr<float>();
+    slots = acc->size(0);
+  }
+  TORCH_CHECK(part.has_value() == tickets.has_value(), "pool_embed: part and tickets go together");
+  float* pp = nullptr;
+  int* tp = nullptr;
+  int64_t pcap = 0, tcap = 0;
+  if (part.has_value()) {
+    TORCH_CHECK(part->is_cuda() && part->scalar_type() == at::kFloat && part->is_contiguous() && part->dim() == 2 &&
+                    part->size(1) == H && part->size(0) < (int64_t)1 << 31, "pool_embed: part fp32 [P, H]");
+    TORCH_CHECK(tickets->is_cuda() && tickets->scalar_type() == at::kInt && tickets->is_contiguous() &&
+                    tickets->dim() == 1 && tickets->numel() < (int64_t)1 << 31, "pool_embed: tickets int32 [>= S]");
+    pp = part->data_ptr<float>();
+    tp = tickets->data_ptr<int>();
+    pcap = part->size(0);
+    tcap = tickets->numel();
+  }
+  TORCH_CHECK(dims >= 0 && dims <= H, "pool_embed: dims in [0, H]");
+  TORCH_CHECK(max_parts >= 1 && max_parts <= die::POOL_MAX_PARTS, "pool_embed: max_parts in [1, ", die::POOL_MAX_PARTS, "]");
+  HIP_OK(die::launch_pool_embed(out.data_ptr<float>(), ap, (int)slots, bf(hidden), hidden.stride(0), (int)T, (int)H,
+                                segs.data_ptr<int>(), (int)S, (int)dims, normalize, pp, (int)pcap, tp, (int)tcap,
+                                (int)max_parts, cur_stream()));
+}
+
 // A decode step's sampling from the LM head's candidates (sample(..., lm_part)) that also advances the step's
 // inputs as decode_advance does (ids / pos / ctx / slots / step, the window's token row, the step counter cnt[0]),
 // one workgroup per row; ticket: int32 [1], zero, re-armed by the kernel.
@@ -1157,6 +1202,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("token_logprobs", &token_logprobs);
   m.def("logit_process", &logit_process);
   m.def("token_guide", &token_guide);
+  m.def("pool_embed", &pool_embed);
   m.def("sample_advance", &sample_advance);
   m.def("move_blocks", &move_blocks);
   m.def("gather_blocks_rows", &gather_blocks_rows);

@@ -139,6 +139,23 @@ hipError_t launch_token_guide(bf16_t* logits, int64_t stride, int rows, int voca
                               int64_t edges_len, int* cur, int* err, const int64_t* advance_ids, uint32_t* lm_part,
                               int lm_parts, hipStream_t s);
 
+// embedding pooling of a prefill step's final-norm rows (pooling.hip): hidden bf16 [T, stride >= H]; segs int32
+// [num_segs, 8] = (first row, rows, acc slot, total prompt length, flags, part base, parts, 0); acc fp32 [slots, H]
+// (mean pooling's partial sums across chunks); out fp32 [num_segs, H], of which a FINAL (or last-pooling) segment
+// writes its first (dims ? dims : H) columns. A mean segment with parts > 1 has its rows split over that many
+// workgroups (grid y = max_parts >= every segment's parts): their fp32 partials go through part [part_cap, H] at
+// rows [part base, part base + parts) and the last arriver of tickets[segment] (int32, zero, re-armed) combines them
+// in part order. hipErrorInvalidValue for H % 8 != 0, stride < H or % 8, dims % 8 != 0 or > H, max_parts outside
+// [1, POOL_MAX_PARTS], max_parts > 1 without scratch or with fewer tickets than segments, a null or misaligned tensor.
+constexpr int POOL_MEAN = 1;    // flags: mean over the segment's rows (else: its last row)
+constexpr int POOL_FIRST = 2;   //        the request's first chunk: acc[slot] is not read
+constexpr int POOL_FINAL = 4;   //        the request's last chunk: divide, normalise, write out (else: store acc[slot])
+constexpr int POOL_MAX_PARTS = 64;    // workgroups per segment
+constexpr int POOL_PART_ROWS = 256;   // the callers' policy: rows per part (src/ops: pool_parts)
+hipError_t launch_pool_embed(float* out, float* acc, int slots, const bf16_t* hidden, int64_t stride, int T, int H,
+                             const int* segs, int num_segs, int dims, bool normalize, float* part, int part_cap,
+                             int* tickets, int ticket_cap, int max_parts, hipStream_t s);
+
 hipError_t launch_topk_softmax(float* w, int* ids, const bf16_t* gating, int T, int E, int K, bool renorm,
                                hipStream_t s);
 hipError_t launch_moe_route(float* w, int* ids, const bf16_t* x, int64_t ldx, const bf16_t* wg, int T, int H, int E,

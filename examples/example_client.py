@@ -9,6 +9,7 @@
     python examples/example_client.py --model llama --prompt "Hello" --repetition-penalty 1.2 --logit-bias '{"50256": -100}'
     python examples/example_client.py --model llama --prompt "Is water wet? " --guided-choice yes no
     python examples/example_client.py --model llama --prompt "A date: " --guided-regex '\d{4}-\d{2}-\d{2}'
+    python examples/example_client.py --model llama --prompt "a sentence to embed" --embed mean   # the prompt's vector
 """
 
 import argparse
@@ -40,6 +41,8 @@ async def main():
                     help="the output is exactly one of these strings, then EOS")
     ap.add_argument("--guided-regex", default=None, metavar="PATTERN",
                     help="the output fully matches this pattern (the byte-level subset of src/guided.py), then EOS")
+    ap.add_argument("--embed", nargs="?", const="last", default=None, choices=["last", "mean"], metavar="POOLING",
+                    help="return the prompt's embedding (last-token or mean pooling, L2-normalised) instead of text")
     ap.add_argument("--request-key", default=None, help="session key for shard affinity")
     ap.add_argument("-n", type=int, default=1)
     ap.add_argument("--concurrency", type=int, default=1)
@@ -58,6 +61,8 @@ async def main():
             inputs["guided_choice"] = a.guided_choice
         if a.guided_regex is not None:
             inputs["guided_regex"] = a.guided_regex
+        if a.embed is not None:
+            inputs = {"prompt": a.prompt, "pooling": a.embed}
     else:
         inputs = json.loads(a.inputs) if a.inputs else {"text": "hello"}
     c = InferenceClient(a.address)
@@ -89,7 +94,12 @@ async def main():
     t0 = time.perf_counter()
     rs = await asyncio.gather(*(one(i) for i in range(a.n)))
     el = time.perf_counter() - t0
-    if a.n == 1:
+    if a.n == 1 and a.embed is not None and rs[0].get("success"):
+        out = rs[0]["outputs"]
+        vec = out["embedding"]
+        print(f"{len(vec)} dimensions, {out['prompt_tokens']} prompt tokens: "
+              f"[{', '.join(f'{v:.4f}' for v in vec[:8])}, ...]")
+    elif a.n == 1:
         print(json.dumps(rs[0], indent=2)[:4000])
     else:
         ok = sum(1 for r in rs if r.get("success"))

@@ -6,7 +6,8 @@ LLMBackend: the worker-side model session for ``arch in {"llama","mixtral"}``
 ``predict(inputs)`` accepts the LLM request format documented in
 :func:`src.preproc.normalize_request` and returns
 ``{"token_ids", "text", "num_prompt_tokens", "num_output_tokens",
-"finish_reason", "ttft_ms", "latency_ms", "tpot_ms"}``.
+"finish_reason", "ttft_ms", "latency_ms", "tpot_ms"}``. A request with ``pooling`` (an embedding request) returns
+``{"embedding": [floats], "prompt_tokens", "finish_reason": "embed", ...}`` instead and cannot be streamed.
 """
 
 from __future__ import annotations
@@ -201,6 +202,9 @@ class LLMBackend:
             raise
         rid = uuid.uuid4().hex
         t0 = time.perf_counter()
+        if gi.sampling.pooling is not None and self._decode_link is not None:
+            self.error_count += 1
+            raise ValueError("pooling is not supported on the disaggregated prefill path")
         if self._decode_link is not None and gi.sampling.max_tokens > 1:
             return await self._prefill_then_ship(rid, gi, t0)
         timeout = inputs.get("timeout_s") if isinstance(inputs, dict) else None
@@ -227,6 +231,14 @@ class LLMBackend:
         lat = (time.perf_counter() - t0) * 1e3
         self.total_latency += lat / 1e3
         reason = "timeout" if timed_out and seq.finish_reason == "abort" else (seq.finish_reason or "length")
+        if gi.sampling.pooling is not None:  # an embedding request: the vector, nothing to detokenise
+            emb = seq.embedding
+            if emb is None:  # aborted or timed out before its prompt was done
+                self.error_count += 1
+                raise RuntimeError(f"embedding request ended without a vector ({reason})")
+            return {"embedding": emb.tolist(), "prompt_tokens": seq.prompt_len,
+                    "num_prompt_tokens": seq.prompt_len, "num_output_tokens": 0, "finish_reason": reason,
+                    "pooling": gi.sampling.pooling, "latency_ms": seq.latency_ms()}
         out = await self._output(seq.output_ids, gi.return_text, prompt_len=seq.prompt_len, finish_reason=reason,
                                  ttft_ms=seq.ttft_ms(), latency_ms=seq.latency_ms())
         return await self._add_logprobs(out, seq, gi.sampling, gi.return_text)
@@ -240,6 +252,8 @@ class LLMBackend:
         ahead (a small model can finish the whole generation before this coroutine first wakes: coalescing
         everything queued would then send one frame for the whole request). Later tokens are coalesced per
         wake-up (bursts of up to ``decode_window`` per host round trip)."""
+        if isinstance(inputs, dict) and inputs.get("pooling") is not None:
+            raise ValueError("pooling cannot be combined with stream")
         q: asyncio.Queue = asyncio.Queue()
         task = asyncio.ensure_future(self.predict(inputs, request_id, on_token=q.put_nowait))
         with_text = not isinstance(inputs, dict) or bool(inputs.get("return_text", True))

@@ -73,8 +73,9 @@ class KVBlockManager:
         assert not seq.block_table
         matched: List[int] = []
         # prompt_logprobs needs the logits of every prompt position: nothing is matched (the blocks are still
-        # published afterwards)
-        if self.prefix_caching and not seq.imported_kv and getattr(seq.sampling, "prompt_logprobs", None) is None:
+        # published afterwards); mean pooling needs the hidden state of every prompt position, likewise
+        if (self.prefix_caching and not seq.imported_kv and getattr(seq.sampling, "prompt_logprobs", None) is None
+                and getattr(seq.sampling, "pooling", None) != "mean"):
             hashes = self._prompt_hashes(seq)
             max_match = (seq.prompt_len - 1) // self.block_size
             matched = list(self.bm.match_prefix(hashes[:max_match]))

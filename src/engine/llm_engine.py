@@ -193,7 +193,13 @@ class LLMEngine:
                     on_token: Optional[Callable[[Sequence, int], None]] = None) -> Sequence:
         if request_id in self.seqs:
             raise ValueError(f"duplicate request id {request_id}")
-        if len(prompt_ids) + sampling.max_tokens > self.max_model_len:
+        pooling = getattr(sampling, "pooling", None)
+        if pooling is not None:  # an embedding request generates nothing: only its prompt has to fit
+            if not prompt_ids:
+                raise ValueError("empty prompt")
+            if len(prompt_ids) > self.max_model_len:
+                raise ValueError(f"prompt exceeds max_model_len={self.max_model_len}")
+        elif len(prompt_ids) + sampling.max_tokens > self.max_model_len:
             raise ValueError(f"prompt + max_tokens exceeds max_model_len={self.max_model_len}")
         if prompt_ids and (min(prompt_ids) < 0 or max(prompt_ids) >= self.arch.vocab_size):
             # an out-of-range id would be an out-of-bounds embedding read on the GPU
@@ -207,6 +213,21 @@ class LLMEngine:
                 raise ValueError("prompt_logprobs is not supported on a tensor-parallel engine")
             if export_kv:
                 raise ValueError("prompt_logprobs is not supported on the disaggregated prefill path")
+        if pooling is not None:
+            # the pooled rows are this runner's own (followers mirror sampled rows only), and a prefill worker
+            # exports KV and one token, not a vector
+            if getattr(self.model, "tp", None) is not None and self.model.tp.enabled:
+                raise ValueError("pooling is not supported on a tensor-parallel engine")
+            if export_kv:
+                raise ValueError("pooling is not supported on the disaggregated prefill path")
+            if on_token is not None:
+                raise ValueError("pooling cannot be combined with streaming")
+            if not hasattr(self.runner, "pool_embed_launches"):
+                raise ValueError("pooling is not supported by this engine's runner")
+            if (sampling.embed_dimensions or 0) > self.arch.hidden_size:
+                raise ValueError(f"embed_dimensions exceeds the model's hidden size {self.arch.hidden_size}")
+            if self.arch.hidden_size % 8:
+                raise ValueError("pooling needs a hidden size that is a multiple of 8")
         seq = Sequence(request_id, list(prompt_ids), dataclasses.replace(sampling), on_finish=on_finish,
                        user_data=user_data, on_token=on_token)
         if sampling.prompt_logprobs is not None:
@@ -254,6 +275,9 @@ class LLMEngine:
         rel = getattr(self.runner, "release_guide_state", None)
         if rel is not None:  # a preempted sequence returns: it keeps its reference to the arena region
             rel(seq, keep_region=preempted)
+        rel = getattr(self.runner, "release_pool_state", None)
+        if rel is not None:  # mean pooling's partial sums: a recompute starts them again
+            rel(seq)
 
     def _fail_guide_errors(self, seqs, finished: List[Sequence]) -> None:
         """A guided sequence whose device-side automaton reported an error (no edge for a sampled token, a table
@@ -410,6 +434,14 @@ class LLMEngine:
                     continue
                 seq.num_computed = c.start + c.length
                 if tok is None:
+                    if seq.sampling.pooling is not None and c.completes_prompt:
+                        # an embedding request ends with its prompt: no token, no decode
+                        self.blocks.register_prompt_blocks(seq)
+                        self.stats["prefix_hit_tokens"] += seq.num_prefix_hit
+                        seq.first_token_time = now
+                        self.scheduler.finish(seq, "embed")
+                        finished.append(seq)
+                        self._complete(seq)
                     continue
                 self.blocks.register_prompt_blocks(seq)
                 self.stats["prefix_hit_tokens"] += seq.num_prefix_hit
@@ -705,6 +737,18 @@ class LLMEngine:
             self.step()
         return [res[i] for i in range(len(prompts))]
 
+    def embed(self, prompts: List[List[int]], pooling: str = "last", normalize: bool = True,
+              dimensions: Optional[int] = None) -> list:
+        """Offline batch embedding (blocking): one float32 numpy vector per prompt."""
+        sp = SamplingParams(pooling=pooling, embed_normalize=normalize, embed_dimensions=dimensions)
+        res: Dict[int, object] = {}
+        for i, p in enumerate(prompts):
+            self.add_request(f"emb-{i}-{time.monotonic_ns()}", p, sp,
+                             on_finish=lambda s, i=i: res.__setitem__(i, s.embedding))
+        while self.has_work():
+            self.step()
+        return [res[i] for i in range(len(prompts))]
+
     def get_stats(self) -> dict:
         s = dict(self.stats)
         s.update(self.scheduler.stats())
@@ -715,6 +759,7 @@ class LLMEngine:
         s["logprob_launches"] = getattr(self.runner, "logprob_launches", 0)  # ops.token_logprobs launches
         s["logit_process_launches"] = getattr(self.runner, "logit_process_launches", 0)  # ops.logit_process
         s["token_guide_launches"] = getattr(self.runner, "token_guide_launches", 0)  # ops.token_guide
+        s["pool_embed_launches"] = getattr(self.runner, "pool_embed_launches", 0)  # ops.pool_embed
         used = getattr(self.runner, "guide_arena_edges_used", None)
         s["guide_arena_edges_used"] = used() if used is not None else 0  # edges of the automata held on the device
         return s

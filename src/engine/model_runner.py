@@ -183,6 +183,15 @@ class ModelRunner:
         self.graph_logits_guided: Dict[int, torch.Tensor] = {}
         self.token_guide_launches = 0           # eager launches and guided graph replays
         self._guided = False                    # the step being assembled has a guided row (_fill_sampling)
+        # embeddings (ops.pool_embed): requests with SamplingParams.pooling end with their prompt and return its
+        # pooled final-norm hidden state. Mean pooling keeps its partial sums across chunks in an fp32 slot arena
+        # [max_seqs, H]; arena, segment descriptors and output rows are allocated by _pool_alloc at the first such
+        # request, so an engine nobody asks keeps its memory plan.
+        self.d_pool = None                      # (acc, segs, out)
+        self.h_pool = None                      # pinned (segs, out)
+        self._pool_slots: Dict[int, int] = {}   # seq_id -> arena slot (mean pooling, while its prompt is in flight)
+        self._pool_free: List[int] = []
+        self.pool_embed_launches = 0
         # decode attention streams K/V as once-read data (DIE_ATTN_KV_ONCE=0: the default cache policy, for A/B)
         self.kv_once = os.environ.get("DIE_ATTN_KV_ONCE", "1") != "0"
         if self.is_cuda:
@@ -545,6 +554,100 @@ class ModelRunner:
     def _raise_on_fault(self) -> None:
         """Raise if an error word read by :meth:`_queue_fault_readback` is set."""
 
+    # --------------------------------------------------------- embeddings
+    def _pool_alloc(self) -> None:
+        """The tables of ops.pool_embed (mean pooling's fp32 slot arena, segment descriptors, output rows, the row
+        split's scratch) and their pinned twins: at the first request that needs them."""
+        if self.d_pool is not None:
+            return
+        dev, pin, m, h = self.device, self.is_cuda, self.max_seqs, self.model.arch.hidden_size
+        f32, i32 = torch.float32, torch.int32
+        self.d_pool = (torch.zeros(m, h, dtype=f32, device=dev), torch.zeros(m, 8, dtype=i32, device=dev),
+                       torch.zeros(m, h, dtype=f32, device=dev))
+        # the row split of long mean segments (ops.pool_parts): at most one part per POOL_PART_ROWS rows of a step
+        # and one more per segment; tickets are zero and re-armed by the kernel
+        self.d_pool_scratch = (torch.zeros(self.max_tokens // ops.POOL_PART_ROWS + m, h, dtype=f32, device=dev),
+                               torch.zeros(m, dtype=i32, device=dev)) if self.is_cuda else None
+        self.h_pool = (torch.zeros(m, 8, dtype=i32, pin_memory=pin), torch.zeros(m, h, dtype=f32, pin_memory=pin))
+        self._pool_free = list(range(m - 1, -1, -1))
+
+    def release_pool_state(self, seq: Sequence) -> None:
+        """Give a mean-pooling sequence's arena slot back (finish, abort, preemption: a recompute starts again at
+        position 0 with POOL_FIRST)."""
+        slot = self._pool_slots.pop(seq.seq_id, None)
+        if slot is not None:
+            self._pool_free.append(slot)
+
+    def _pool_plan(self, chunks: List[PrefillChunk], pooled: List[int]):
+        """The step's pooling segments, from the host's cu_q: (chunk index, mean, first row, rows) per segment —
+        every chunk of a mean request, the completing chunk of a last request — grouped by (dimensions,
+        normalize) so that each group is one launch."""
+        cu = self.h_cu.numpy()
+        plan = []
+        for i in pooled:
+            c = chunks[i]
+            mean = c.seq.sampling.pooling == "mean"
+            if mean or c.completes_prompt:
+                plan.append((i, mean, int(cu[i]), c.length))
+        plan.sort(key=lambda e: (chunks[e[0]].seq.sampling.embed_dimensions or 0,
+                                 chunks[e[0]].seq.sampling.embed_normalize))
+        return plan
+
+    def _launch_pool_embed(self, hidden: torch.Tensor, chunks: List[PrefillChunk], plan, kept0: Optional[int]) -> None:
+        """Queue the step's pooling launches behind its forward and the copy of their vectors to the pinned buffer.
+        kept0 (a pruned last layer): hidden holds only the kept rows and the j-th last-pooling segment's row is
+        kept0 + j, in plan order of the chunks; None: hidden holds every row of the step."""
+        self._pool_alloc()
+        d_acc, d_segs, d_out = self.d_pool
+        h_segs, h_out = self.h_pool
+        ns = h_segs.numpy()
+        order = {i: j for j, i in enumerate(sorted(e[0] for e in plan if not e[1]))}
+        groups, finals = [], []
+        part_base = 0  # rows of the split scratch handed out in this step
+        for k, (i, mean, row0, rows) in enumerate(plan):
+            c = chunks[i]
+            seq, sp = c.seq, c.seq.sampling
+            parts = 1
+            if mean:
+                slot = self._pool_slots.get(seq.seq_id)
+                if slot is None:
+                    slot = self._pool_slots[seq.seq_id] = self._pool_free.pop()
+                parts = ops.pool_parts(rows) if self.is_cuda else 1
+                ns[k] = ops.pool_segment(row0, rows, slot, seq.prompt_len, True, c.start == 0, c.completes_prompt,
+                                         part_base, parts)
+                part_base += parts
+                if c.completes_prompt:
+                    finals.append(seq)
+            elif kept0 is not None:
+                ns[k] = ops.pool_segment(kept0 + order[i], 1)
+            else:
+                ns[k] = ops.pool_segment(row0, rows)
+            key = (sp.embed_dimensions or 0, sp.embed_normalize)
+            if not groups or groups[-1][0] != key:
+                groups.append([key, k, k, 1])  # key, first segment, end, the widest split
+            groups[-1][2], groups[-1][3] = k + 1, max(groups[-1][3], parts)
+        # only now: a slot given back inside the loop could go to another segment of the same launch, whose
+        # workgroup would write it while this one reads it. Whoever takes it later writes it behind this launch
+        # (stream order).
+        for seq in finals:
+            self.release_pool_state(seq)
+        n = len(plan)
+        d_segs[:n].copy_(h_segs[:n], non_blocking=self.is_cuda)
+        for (dims, norm), lo, hi, mp in groups:
+            ops.pool_embed(hidden, d_segs[lo:hi], d_acc, d_out[lo:hi], dims=dims, normalize=norm,
+                           scratch=self.d_pool_scratch, max_parts=mp)
+            self.pool_embed_launches += 1
+        h_out[:n].copy_(d_out[:n], non_blocking=self.is_cuda)
+
+    def _pool_read(self, chunks: List[PrefillChunk], plan) -> None:
+        """After the step's synchronise: the finished vectors onto their sequences."""
+        h_out = self.h_pool[1].numpy()
+        for k, (i, _, _, _) in enumerate(plan):
+            c = chunks[i]
+            if c.completes_prompt:
+                d = c.seq.sampling.embed_dimensions or h_out.shape[1]
+                c.seq.embedding = h_out[k, :d].copy()
+
     # ------------------------------------------------------------ prefill
     KIND_STOP, KIND_PREFILL, KIND_DECODE, KIND_HEARTBEAT = 0, 1, 2, 3
 
@@ -576,11 +679,19 @@ class ModelRunner:
                                          self.h_pos.data_ptr(), self.h_slots.data_ptr(), self.h_cu.data_ptr(),
                                          self.h_ctx.data_ptr(), self.h_bt.data_ptr(), self.bt_width,
                                          self.h_last.data_ptr())
-        done = [i for i, c in enumerate(chunks) if c.completes_prompt]
+        # chunks of embedding requests (SamplingParams.pooling) sample nothing: they are not in done
+        pooled = [i for i, c in enumerate(chunks) if c.seq.sampling.pooling is not None]
+        done = [i for i, c in enumerate(chunks)
+                if c.completes_prompt and (not pooled or c.seq.sampling.pooling is None)]
         nd = len(done)
-        if nd and nd != n:
+        pplan = self._pool_plan(chunks, pooled) if pooled else None
+        # last pooling: the completing chunk's last row joins the kept rows of the last-layer pruning, after the
+        # sampled rows; a mean chunk needs every row of the step
+        kept = done + sorted(e[0] for e in pplan if not e[1]) if pplan else done
+        pool_all = bool(pooled) and any(chunks[i].seq.sampling.pooling == "mean" for i in pooled)
+        if kept and (len(kept) != n or pooled):
             nl = self.h_last.numpy()
-            nl[:nd] = nl[done]
+            nl[:len(kept)] = nl[kept]
         greedy = self._fill_sampling([chunks[i].seq for i in done], nd, prefill=True) if nd else True
         proc = bool(nd) and self._proc
         guide = bool(nd) and self._guided
@@ -590,8 +701,12 @@ class ModelRunner:
         self._h2d(t, n, with_cu=True)
         max_q = max(c.length for c in chunks)
         self._sync_step(self.KIND_PREFILL, t, n, max_q, nd)
-        ids = self._exec_prefill(t, n, max_q, nd, greedy, kv_hook=kv_hook, lp_top=lp_top, plan=plan, process=proc,
-                                 guide=guide)
+        if not pooled:
+            ids = self._exec_prefill(t, n, max_q, nd, greedy, kv_hook=kv_hook, lp_top=lp_top, plan=plan, process=proc,
+                                     guide=guide)
+        else:
+            ids = self._exec_prefill(t, n, max_q, nd, greedy, kv_hook=kv_hook, lp_top=lp_top, plan=plan, process=proc,
+                                     guide=guide, pool=(chunks, pplan, len(kept), pool_all))
         res: List[Optional[int]] = [None] * n
         if nd:
             if guide:
@@ -611,6 +726,8 @@ class ModelRunner:
             self._queue_fault_readback()
             torch.cuda.current_stream(self.device).synchronize()
             self._raise_on_fault()
+        if pplan:
+            self._pool_read(chunks, pplan)
         return res
 
     PROMPT_LOGPROB_SLAB = 1024  # rows of prompt logits at a time (<= 256 MiB of bf16 logits at a 128K vocabulary)
@@ -654,10 +771,12 @@ class ModelRunner:
 
     def _exec_prefill(self, t: int, n: int, max_q: int, nd: int, greedy: bool, kv_hook=None, lp_top: int = -1,
                       plan: Optional[List[tuple]] = None, process: bool = False,
-                      guide: bool = False) -> Optional[torch.Tensor]:
+                      guide: bool = False, pool: Optional[tuple] = None) -> Optional[torch.Tensor]:
         # the last layer runs only for the sampled rows (CausalLM._last_layer_kept_rows; DIE_PRUNE_LAST=0: all);
         # a step that scores prompt tokens (prompt_logprobs) needs every row
         keep = self.d_last[:nd] if self.prune_last and not plan else None
+        if pool is not None:
+            return self._exec_prefill_pooled(t, n, max_q, nd, greedy, kv_hook, lp_top, plan, process, guide, pool)
         meta = AttnMetadata(is_prefill=True, slot_mapping=self.d_slots[:t], block_tables=self.d_bt[:n],
                             ctx_lens=self.d_ctx[:n], cu_q=self.d_cu[: n + 1], max_q_len=max_q, kv_hook=kv_hook,
                             keep_rows=keep)
@@ -675,6 +794,36 @@ class ModelRunner:
             self._launch_token_guide(logits, nd)
         ids = self._sample(logits, nd, greedy, self.d_out)
         if lp_top >= 0:  # the first generated token's logprobs (the leader only: followers have nothing to report)
+            self._launch_logprobs(logits, ids, nd, 0, lp_top)
+        return ids
+
+    def _exec_prefill_pooled(self, t: int, n: int, max_q: int, nd: int, greedy: bool, kv_hook, lp_top: int, plan,
+                             process: bool, guide: bool, pool: tuple) -> Optional[torch.Tensor]:
+        """_exec_prefill for a step with chunks of embedding requests: the kept rows are the nd sampled rows and,
+        behind them, the last-pooling rows (d_last[:kn]); a mean chunk (pool_all) keeps every row, as a
+        prompt_logprobs plan does, and so does a step whose rows are all kept. Only the first nd kept rows go to the
+        LM head; a step without sampled rows skips it."""
+        chunks, pplan, kn, pool_all = pool
+        pruned = self.prune_last and not plan and not pool_all and kn != t
+        meta = AttnMetadata(is_prefill=True, slot_mapping=self.d_slots[:t], block_tables=self.d_bt[:n],
+                            ctx_lens=self.d_ctx[:n], cu_q=self.d_cu[: n + 1], max_q_len=max_q, kv_hook=kv_hook,
+                            keep_rows=self.d_last[:kn] if pruned else None)
+        hidden = self.model.forward(self.d_ids[:t], self.d_pos[:t], meta, self.pool.tensor)
+        pruned = pruned and hidden.shape[0] != t  # a path that computed every row (the slab path of small steps)
+        if plan:
+            self.last_prompt_logprobs = self._prompt_logprobs(hidden, plan)
+        if pplan:
+            self._launch_pool_embed(hidden, chunks, pplan, nd if pruned else None)
+        if not nd:
+            return None
+        hidden = hidden[:nd] if pruned else hidden.index_select(0, self.d_last[:nd])
+        logits = self.model.compute_logits(hidden)
+        if process:
+            self._launch_logit_process(logits, nd)
+        if guide:
+            self._launch_token_guide(logits, nd)
+        ids = self._sample(logits, nd, greedy, self.d_out)
+        if lp_top >= 0:
             self._launch_logprobs(logits, ids, nd, 0, lp_top)
         return ids
 

@@ -49,6 +49,9 @@ class Sequence:
     # SamplingParams.prompt_logprobs: one entry per prompt position, None at position 0 (None: not requested)
     prompt_logprobs_out: Optional[List[Optional[dict]]] = None
 
+    # SamplingParams.pooling: the pooled prompt state, float32 numpy [dimensions] (None until the prompt is done)
+    embedding: Any = None
+
     def __len__(self) -> int:
         return len(self.prompt_ids) + len(self.output_ids)
 

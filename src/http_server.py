@@ -33,6 +33,17 @@ coordinator's framed-RPC API. It holds no model state — every request becomes 
     byte-level subset of src/guided.py) and then EOS. Barred tokens have logprob -inf (-9999.0 here). A malformed
     value, two of the three at once, unsupported regex syntax, ignore_eos with a choice or a pattern, or any of
     them on a model served tensor-parallel is a 400.
+    POST /v1/embeddings    {"model", "input": str | [str] | [token ids] | [[token ids]] (<= 2048 items),
+                            "encoding_format": "float" | "base64", "dimensions": multiple of 8,
+                            "pooling": "last" | "mean", "normalize": bool}
+                           One embedding per input item: the pooled final-norm hidden state of the item's tokens
+                           ("last", the default: the last token's; "mean": the mean over all tokens), cut to its
+                           first "dimensions" components, L2-normalised unless normalize is false. Every item is
+                           one infer RPC, all in flight at once, so the worker batches them into shared prefill
+                           steps. Answers {"object": "list", "data": [{"object": "embedding", "index",
+                           "embedding"}], "model", "usage": {"prompt_tokens", "total_tokens"}}; base64 is the
+                           little-endian float32 bytes. A bad value, "stream", or a model served tensor-parallel
+                           or with disaggregated prefill is a 400.
     GET  /v1/models        the coordinator's registered models
     GET  /health           200 when the coordinator answers its health RPC
     GET  /metrics          Prometheus text format (requests, errors, latency, tokens)
@@ -42,7 +53,9 @@ from __future__ import annotations
 
 import argparse
 import asyncio
+import base64
 import json
+import struct
 import time
 import uuid
 from typing import Any, Dict, Optional
@@ -61,6 +74,7 @@ _SAMPLING = ("max_tokens", "temperature", "top_p", "top_k", "seed", "stop_token_
     _LOGIT_PROCESSING + _GUIDED
 _ROLES = ("system", "user", "assistant", "tool")
 MAX_LOGPROBS = 20
+MAX_EMBED_INPUTS = 2048  # items of one /v1/embeddings request (the OpenAI API's cap)
 
 
 def _logprob_count(v: Any, name: str) -> int:
@@ -135,10 +149,21 @@ class Gateway:
         self.m_ttft = Histogram("die_http_ttft_seconds", "time to first token (engine)", ["model"],
                                 registry=self.reg, buckets=(0.005, 0.01, 0.025, 0.05, 0.1, 0.25, 0.5, 1, 2, 5))
 
+        # embeddings: families of their own (the completion families keep their label sets)
+        self.m_emb_req = Counter("die_http_embedding_requests", "embedding requests", ["model"], registry=self.reg)
+        self.m_emb_err = Counter("die_http_embedding_errors", "failed embedding requests", ["model"],
+                                 registry=self.reg)
+        self.m_emb_items = Counter("die_http_embedding_inputs", "embedded input items", ["model"], registry=self.reg)
+        self.m_emb_tok = Counter("die_http_embedding_prompt_tokens", "embedded prompt tokens", ["model"],
+                                 registry=self.reg)
+        self.m_emb_lat = Histogram("die_http_embedding_latency_seconds", "embedding request latency", ["model"],
+                                   registry=self.reg, buckets=(0.005, 0.01, 0.05, 0.1, 0.25, 0.5, 1, 2, 5, 10, 30))
+
     def app(self) -> web.Application:
         a = web.Application()
         a.router.add_post("/v1/completions", self.completions)
         a.router.add_post("/v1/chat/completions", self.chat_completions)
+        a.router.add_post("/v1/embeddings", self.embeddings)
         a.router.add_get("/v1/models", self.models)
         a.router.add_get("/health", self.health)
         a.router.add_get("/metrics", self.metrics)
@@ -268,6 +293,80 @@ class Gateway:
         await resp.write(b"data: [DONE]\n\n")
         await resp.write_eof()
         return resp
+
+    @staticmethod
+    def _embedding_inputs(body: Dict[str, Any]) -> list:
+        """One infer payload per item of "input"; a ValueError for anything malformed."""
+        if body.get("stream"):
+            raise ValueError("embeddings cannot be streamed")
+        x = body.get("input")
+        if isinstance(x, str):
+            items = [x]
+        elif isinstance(x, list) and x and all(isinstance(t, int) and not isinstance(t, bool) for t in x):
+            items = [x]
+        elif isinstance(x, list):
+            items = x
+        else:
+            raise ValueError("input must be a string, a list of strings, a list of token ids or a list of those")
+        if not items:
+            raise ValueError("input is empty")
+        if len(items) > MAX_EMBED_INPUTS:
+            raise ValueError(f"input holds more than {MAX_EMBED_INPUTS} items")
+        fmt = body.get("encoding_format", "float")
+        if fmt not in ("float", "base64"):
+            raise ValueError("encoding_format must be float or base64")
+        pooling = body.get("pooling", "last")
+        normalize = body.get("normalize", True)
+        common: Dict[str, Any] = {"pooling": pooling, "embed_normalize": normalize, "return_text": False}
+        if body.get("dimensions") is not None:
+            common["embed_dimensions"] = body["dimensions"]
+        # values and types: refused here with a 400, not by a worker after routing
+        SamplingParams(**{k: v for k, v in common.items() if k != "return_text"})
+        out = []
+        for it in items:
+            if isinstance(it, str) and it:
+                out.append(dict(common, prompt=it))
+            elif isinstance(it, list) and it and all(isinstance(t, int) and not isinstance(t, bool) and t >= 0
+                                                     for t in it):
+                out.append(dict(common, prompt_token_ids=it))
+            else:
+                raise ValueError("every input item must be a non-empty string or a non-empty list of token ids")
+        return out
+
+    async def embeddings(self, req: web.Request) -> web.Response:
+        t0 = time.perf_counter()
+        try:
+            body = await req.json()
+            model = body["model"]
+            payloads = self._embedding_inputs(body)
+        except (ValueError, KeyError, TypeError, json.JSONDecodeError) as e:
+            return web.json_response({"error": {"message": f"bad request: {e}", "type": "invalid_request"}},
+                                     status=400)
+        self.m_emb_req.labels(model).inc()
+        # one RPC per item, all in flight at once: the worker's engine batches them into shared prefill steps
+        reps = await asyncio.gather(*(self.client.infer(model, p, cache=body.get("cache", True)) for p in payloads))
+        b64 = body.get("encoding_format") == "base64"
+        data, tokens = [], 0
+        for i, rep in enumerate(reps):
+            out = rep.get("outputs") if rep.get("success") else None
+            if not isinstance(out, dict) or "embedding" not in out:
+                self.m_emb_err.labels(model).inc()
+                msg = str(rep.get("error", "the model returned no embedding"))
+                # a request the engine refused (tensor parallelism, disaggregated prefill, a bad value) is the
+                # client's error
+                refused = any(w in msg for w in ("not supported on", "exceeds", "out of vocabulary"))
+                status = 404 if "not registered" in msg else 400 if refused else 502
+                return web.json_response({"error": {"message": msg, "type": "server_error", "index": i}},
+                                         status=status)
+            vec = out["embedding"]
+            tokens += int(out.get("prompt_tokens", 0))
+            emb = base64.b64encode(struct.pack(f"<{len(vec)}f", *vec)).decode() if b64 else vec
+            data.append({"object": "embedding", "index": i, "embedding": emb})
+        self.m_emb_items.labels(model).inc(len(data))
+        self.m_emb_tok.labels(model).inc(tokens)
+        self.m_emb_lat.labels(model).observe(time.perf_counter() - t0)
+        return web.json_response({"object": "list", "data": data, "model": model,
+                                  "usage": {"prompt_tokens": tokens, "total_tokens": tokens}})
 
     def _observe(self, model: str, out: Dict[str, Any], t0: float) -> None:
         self.m_lat.labels(model).observe(time.perf_counter() - t0)

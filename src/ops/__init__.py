@@ -307,6 +307,54 @@ def token_guide(logits: torch.Tensor, slot: torch.Tensor, desc: torch.Tensor, ro
     return logits
 
 
+# embedding pooling (launchers.h): a segment descriptor's flag bits, and the row split of long mean segments
+POOL_MEAN, POOL_FIRST, POOL_FINAL = 1, 2, 4
+POOL_MAX_PARTS = 64    # workgroups per segment
+POOL_PART_ROWS = 256   # rows per part (bench/micro_pool_embed.py: one workgroup alone reads ~90 GB/s)
+
+
+def pool_parts(rows: int) -> int:
+    """Into how many parts (workgroups) a mean segment of ``rows`` rows is split: POOL_PART_ROWS rows each, at most
+    POOL_MAX_PARTS. 1: one workgroup, no scratch needed."""
+    return max(1, min(POOL_MAX_PARTS, -(-int(rows) // POOL_PART_ROWS)))
+
+
+def pool_segment(first: int, rows: int, slot: int = 0, total: int = 0, mean: bool = False, first_chunk: bool = True,
+                 final: bool = True, part_base: int = 0, parts: int = 0) -> tuple:
+    """One row of :func:`pool_embed`'s ``segs``. ``parts`` > 1 (mean only): the segment's rows are split over that
+    many workgroups whose partial sums lie at rows [part_base, part_base + parts) of ``part``."""
+    flags = (POOL_MEAN if mean else 0) | (POOL_FIRST if first_chunk else 0) | (POOL_FINAL if final else 0)
+    return (int(first), int(rows), int(slot), int(total), flags, int(part_base), int(parts), 0)
+
+
+def pool_embed(hidden: torch.Tensor, segs: torch.Tensor, acc: Optional[torch.Tensor] = None,
+               out: Optional[torch.Tensor] = None, dims: int = 0, normalize: bool = True, scratch=None,
+               max_parts: int = 1) -> torch.Tensor:
+    """Pool the final-norm rows ``hidden`` bf16 [T, H] (row stride allowed) of a prefill step into one fp32 vector
+    per segment, all segments in one launch -> ``out`` fp32 [S, H]. ``segs`` int32 [S, 8] on ``hidden``'s device,
+    rows as :func:`pool_segment` builds them: (first row, rows, acc slot, total prompt length, flags, part base,
+    parts). Without ``POOL_MEAN`` the vector is the segment's last row. With it, it is (``POOL_FIRST`` ? 0 :
+    ``acc[slot]``) + the fp32 sum of the rows; a segment without ``POOL_FINAL`` stores that to ``acc[slot]`` (fp32
+    [slots, H]) and leaves its row of ``out`` alone, one with it divides by ``total``. The vector is cut to its
+    first ``dims`` components (0: all H; else a multiple of 8; the columns of ``out`` beyond stay as they are) and,
+    with ``normalize``, divided by max(its L2 norm, 1e-12) as ``torch.nn.functional.normalize`` does. Rows outside
+    every segment are never read. A descriptor that does not fit the tensors writes nothing.
+    ``scratch`` = (part fp32 [P, H], tickets int32 [>= S], zero, re-armed by the kernel) and ``max_parts`` (>= the
+    largest ``parts`` of a segment, <= POOL_MAX_PARTS) are needed when a segment has ``parts`` > 1; the result does
+    not depend on which workgroup finishes last (the partials are combined in part order)."""
+    dims = int(dims)
+    s, (t, h) = segs.shape[0], hidden.shape
+    if out is None:
+        out = torch.zeros(s, h, dtype=torch.float32, device=hidden.device)
+    if not hidden.is_cuda:
+        if h % 8 or dims % 8 or not 0 <= dims <= h:
+            raise RuntimeError("pool_embed: H and dims must be multiples of 8, dims <= H")
+        return ref.pool_embed_rows(hidden, segs, acc, out, dims, normalize)
+    part, tickets = scratch if scratch is not None else (None, None)
+    _kern().pool_embed(out, acc, hidden, segs, dims, bool(normalize), part, tickets, int(max_parts))
+    return out
+
+
 def sample_advance(logits, temperature, top_k, top_p, seeds, steps, out, lm_part, ids, pos, ctx, slots, bt, tokens,
                    cnt, n_real, block_size: int, ticket, embed=None) -> torch.Tensor:
     """:func:`sample` from the LM head's candidates (``lm_part``) fused with :func:`decode_advance`: every row's

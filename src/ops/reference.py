@@ -289,6 +289,39 @@ def token_guide_rows(logits, slot, desc, rowptr, edges, cur, err, advance_ids=No
     return logits
 
 
+POOL_MEAN, POOL_FIRST, POOL_FINAL = 1, 2, 4  # flag bits of a pool_embed segment descriptor
+
+
+def pool_embed_rows(hidden, segs, acc, out, dims: int = 0, normalize: bool = True):
+    """ops.pool_embed on host tensors (the contract of csrc/kernels/pooling.hip), fp32 throughout: per segment
+    (first row, rows, slot, total, flags): the last row, or (FIRST ? 0 : acc[slot]) + the rows' sum, stored to
+    acc[slot] unless FINAL, else divided by total; cut to the first dims components; divided by max(norm, 1e-12).
+    A descriptor that does not fit the tensors writes nothing."""
+    t, h = hidden.shape
+    d = dims if dims else h
+    for i in range(segs.shape[0]):
+        first, rows, slot, total, flags = (int(v) for v in segs[i, :5])
+        mean = bool(flags & POOL_MEAN)
+        if first < 0 or rows < 1 or first + rows > t:
+            continue
+        if mean and (acc is None or not 0 <= slot < acc.shape[0] or total < 1):
+            continue
+        if not mean:
+            v = hidden[first + rows - 1, :d].float()
+        else:
+            v = hidden[first:first + rows, :d].float().sum(0)
+            if not flags & POOL_FIRST:
+                v = acc[slot, :d] + v
+            if not flags & POOL_FINAL:
+                acc[slot, :d] = v
+                continue
+            v = v / torch.tensor(float(total), dtype=torch.float32)
+        if normalize:
+            v = v / torch.clamp(torch.sqrt((v * v).sum()), min=1e-12)
+        out[i, :d] = v
+    return out
+
+
 def topk_softmax(gating: torch.Tensor, k: int, renorm: bool = True):
     p = torch.softmax(gating.float(), dim=-1)
     w, ids = torch.topk(p, k, dim=-1)

@@ -62,6 +62,7 @@ def load_tokenizer(path: Optional[str] = None, vocab_size: int = 128256):
 
 
 MAX_LOGPROBS = 20  # the OpenAI chat API's cap on top_logprobs
+POOLING_MODES = ("last", "mean")  # SamplingParams.pooling
 MAX_LOGIT_BIAS = 300  # the OpenAI API's cap on logit_bias entries (launchers.h LOGIT_BIAS_MAX)
 
 
@@ -101,6 +102,13 @@ class SamplingParams:
     allowed_token_ids: Optional[List[int]] = None
     guided_choice: Optional[List[List[int]]] = None
     guided_regex: Optional[str] = None
+    # embeddings: with pooling set the request generates nothing. It ends when its prompt does, and its result is
+    # the pooled final-norm hidden state of the prompt (ops.pool_embed): "last" = the last prompt token's row,
+    # "mean" = the mean over all prompt rows; cut to its first embed_dimensions components (None: all; a multiple
+    # of 8), then L2-normalised unless embed_normalize is off. max_tokens is ignored.
+    pooling: Optional[str] = None
+    embed_normalize: bool = True
+    embed_dimensions: Optional[int] = None
 
     def __post_init__(self):
         if self.max_tokens < 1:
@@ -147,6 +155,26 @@ class SamplingParams:
                 bias[k] = v
             self.logit_bias = bias or None
         self._check_guided()
+        self._check_pooling()
+
+    def _check_pooling(self) -> None:
+        if self.pooling is None:
+            if self.embed_dimensions is not None:
+                raise ValueError("embed_dimensions needs pooling")
+            return
+        if self.pooling not in POOLING_MODES:
+            raise ValueError(f"pooling must be one of {', '.join(POOLING_MODES)}")
+        if not isinstance(self.embed_normalize, bool):
+            raise ValueError("embed_normalize must be a boolean")
+        d = self.embed_dimensions
+        if d is not None and (isinstance(d, bool) or not isinstance(d, int) or d < 8 or d % 8):
+            raise ValueError("embed_dimensions must be a positive multiple of 8")
+        if self.logprobs is not None or self.prompt_logprobs is not None:
+            raise ValueError("pooling cannot be combined with logprobs / prompt_logprobs")
+        if self.processes_logits:
+            raise ValueError("pooling cannot be combined with penalties or logit_bias")
+        if self.guided:
+            raise ValueError("pooling cannot be combined with allowed_token_ids / guided_choice / guided_regex")
 
     def _check_guided(self) -> None:
         if sum(v is not None for v in (self.allowed_token_ids, self.guided_choice, self.guided_regex)) > 1:
@@ -212,7 +240,8 @@ class GenerationInputs:
 
 _SAMPLING_KEYS = ("max_tokens", "temperature", "top_k", "top_p", "seed", "ignore_eos", "stop_token_ids",
                   "logprobs", "prompt_logprobs", "presence_penalty", "frequency_penalty", "repetition_penalty",
-                  "logit_bias", "allowed_token_ids", "guided_choice", "guided_regex")
+                  "logit_bias", "allowed_token_ids", "guided_choice", "guided_regex", "pooling", "embed_normalize",
+                  "embed_dimensions")
 
 
 def normalize_request(inputs: Any, tokenizer=None, max_model_len: Optional[int] = None) -> GenerationInputs:
@@ -249,7 +278,12 @@ def normalize_request(inputs: Any, tokenizer=None, max_model_len: Optional[int] 
         named = sp.allowed_token_ids or [t for c in sp.guided_choice or () for t in c]
         if named and max(named) >= vs:
             raise ValueError("allowed_token_ids / guided_choice token id out of vocabulary range")
-    if max_model_len is not None and len(ids) + sp.max_tokens > max_model_len:
+    if sp.pooling is not None:  # nothing is generated: only the prompt has to fit
+        if inputs.get("stream"):
+            raise ValueError("pooling cannot be combined with stream")
+        if max_model_len is not None and len(ids) > max_model_len:
+            raise ValueError(f"prompt ({len(ids)}) exceeds max_model_len {max_model_len}")
+    elif max_model_len is not None and len(ids) + sp.max_tokens > max_model_len:
         raise ValueError(f"prompt ({len(ids)}) + max_tokens ({sp.max_tokens}) exceeds max_model_len {max_model_len}")
     return GenerationInputs(prompt_token_ids=ids, sampling=sp, prompt=prompt,
                             return_text=bool(inputs.get("return_text", True)))
@@ -401,6 +435,8 @@ def request_cost(inputs: Any) -> Optional[Tuple[int, int]]:
         p = len(inputs["prompt"].encode()) // 4 + 1
     else:
         return None
+    if inputs.get("pooling") is not None:  # an embedding request generates nothing
+        return p, 0
     try:
         g = int(inputs.get("max_tokens", SamplingParams.max_tokens))
     except (TypeError, ValueError):
