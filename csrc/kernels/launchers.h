@@ -139,6 +139,23 @@ hipError_t launch_token_guide(bf16_t* logits, int64_t stride, int rows, int voca
                               int64_t edges_len, int* cur, int* err, const int64_t* advance_ids, uint32_t* lm_part,
                               int lm_parts, hipStream_t s);
 
+// constrained decoding over a multi-byte vocabulary (byte_guide.hip): as launch_token_guide, but the slot's guide is
+// a byte DFA, desc [num_slots, 4] = (state_base, n_states, eos, 0) into the arenas trans int16 [trans_states, 256]
+// (-1: no transition) and accept uint8 [accept_len], and every token's bytes (tok_off int32 [n_tok + 1] into
+// tok_bytes uint8 [bytes_len]) are walked through it on the device; state n_states is the sink (EOS only). cur / err
+// are token_guide's arrays. hipErrorInvalidValue for what launch_token_guide refuses, a null or misaligned table
+// a byte table of fewer than 8 bytes (the kernel fetches eight at a time) and a table above the sizes below.
+constexpr int GUIDE_MAX_TOKEN_BYTES = 32;          // a longer token is never allowed (its bytes can still be spelled)
+constexpr int GUIDE_BYTE_STATE_ARENA = 65536;      // states: trans 32 MiB, accept 64 KiB
+constexpr int GUIDE_BYTE_LDS_STATES = 208;         // a guide of up to this many states is walked from LDS (104 KiB)
+constexpr int GUIDE_TOK_TABLE_MAX = 1 << 20;       // tokens in the vocabulary's byte table
+constexpr int GUIDE_TOK_BYTES_MAX = 1 << 25;       // bytes in it
+hipError_t launch_byte_guide(bf16_t* logits, int64_t stride, int rows, int vocab, const int* slot, int num_slots,
+                             const int* desc, const int16_t* trans, int64_t trans_states, const uint8_t* accept,
+                             int64_t accept_len, const int* tok_off, int64_t n_tok, const uint8_t* tok_bytes,
+                             int64_t bytes_len, int* cur, int* err, const int64_t* advance_ids, uint32_t* lm_part,
+                             int lm_parts, hipStream_t s);
+
 // embedding pooling of a prefill step's final-norm rows (pooling.hip): hidden bf16 [T, stride >= H]; segs int32
 // [num_segs, 8] = (first row, rows, acc slot, total prompt length, flags, part base, parts, 0); acc fp32 [slots, H]
 // (mean pooling's partial sums across chunks); out fp32 [num_segs, H], of which a FINAL (or last-pooling) segment

@@ -74,8 +74,11 @@ class LLMBackend:
         self.tokenizer = load_tokenizer(config.model_path or None, engine.arch.vocab_size)
         if not isinstance(self.tokenizer, ByteTokenizer):
             engine.eos_token_id = getattr(self.tokenizer, "eos_token_id", engine.eos_token_id)
-            # no byte table for a multi-byte vocabulary yet: the engine refuses guided_regex
-            engine.token_bytes = None
+            # the tokenizer's byte table (ByteLevel BPE, or byte-fallback pieces): guided_regex walks every token's
+            # bytes on the device (ops.byte_guide). None for a layout that is not recognised: guided_regex is refused
+            from src.guided import hf_token_bytes
+
+            engine.token_bytes = hf_token_bytes(self.tokenizer, engine.arch.vocab_size)
         self.async_engine = AsyncLLMEngine(engine, name=config.model_name)
         self.role = config.role
         self._decode_link = None

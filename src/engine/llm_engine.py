@@ -759,6 +759,7 @@ class LLMEngine:
         s["logprob_launches"] = getattr(self.runner, "logprob_launches", 0)  # ops.token_logprobs launches
         s["logit_process_launches"] = getattr(self.runner, "logit_process_launches", 0)  # ops.logit_process
         s["token_guide_launches"] = getattr(self.runner, "token_guide_launches", 0)  # ops.token_guide
+        s["byte_guide_launches"] = getattr(self.runner, "byte_guide_launches", 0)  # ops.byte_guide
         s["pool_embed_launches"] = getattr(self.runner, "pool_embed_launches", 0)  # ops.pool_embed
         used = getattr(self.runner, "guide_arena_edges_used", None)
         s["guide_arena_edges_used"] = used() if used is not None else 0  # edges of the automata held on the device

@@ -30,7 +30,7 @@ from src.config import EngineConfig
 from src.engine.block_manager import native_runtime
 from src.engine.scheduler import PrefillChunk
 from src.engine.sequence import Sequence
-from src.guided import Automaton, FirstFit, walk
+from src.guided import GUIDE_MAX_TOKEN_BYTES, Automaton, ByteGuide, FirstFit, table_of, walk
 from src.models.llama import AttnMetadata, CausalLM
 
 logger = logging.getLogger(__name__)
@@ -171,6 +171,15 @@ class ModelRunner:
         self.h_guide_slot = torch.full((self.max_seqs,), -1, dtype=i32, pin_memory=pin)
         self.d_guide_slot = torch.full((self.max_seqs,), -1, dtype=i32, device=dev)
         self.d_guide = None                     # (desc, rowptr, edges, cur, err)
+        # guided_regex over a multi-byte vocabulary (ops.byte_guide, launched directly behind ops.token_guide): the
+        # byte DFA's rows live in a second pair of arenas, the vocabulary's bytes in one table per runner; slots,
+        # descriptors, cur and err are the ones above. A row is in at most one of the two slot vectors.
+        self.h_bguide_slot = torch.full((self.max_seqs,), -1, dtype=i32, pin_memory=pin)
+        self.d_bguide_slot = torch.full((self.max_seqs,), -1, dtype=i32, device=dev)
+        self.d_bguide = None                    # (trans, accept, tok_off, tok_bytes)
+        self._bguide_st: Optional[FirstFit] = None
+        self._bguide_table: Optional[int] = None  # guided.id_of the byte table that is on the device
+        self.byte_guide_launches = 0            # eager launches and guided graph replays
         self._guide_slots: Dict[int, int] = {}  # seq_id -> slot
         self._guide_free: List[int] = []
         self._guide_refs: Dict[int, tuple] = {}  # seq_id -> the spec key of the region it references
@@ -179,7 +188,7 @@ class ModelRunner:
         self._guide_rp: Optional[FirstFit] = None
         self._guide_ed: Optional[FirstFit] = None
         self._guide_ev = None
-        self.graphs_guided: Dict[int, torch.cuda.CUDAGraph] = {}  # LM head -> logit_process -> token_guide -> tail
+        self.graphs_guided: Dict[int, torch.cuda.CUDAGraph] = {}  # LM head -> logit_process -> token_guide -> byte_guide -> tail
         self.graph_logits_guided: Dict[int, torch.Tensor] = {}
         self.token_guide_launches = 0           # eager launches and guided graph replays
         self._guided = False                    # the step being assembled has a guided row (_fill_sampling)
@@ -335,6 +344,14 @@ class ModelRunner:
         self.h_guide_err = torch.zeros(m, dtype=i32, pin_memory=self.is_cuda)  # err, read back with the tokens
         self._guide_free = list(range(m - 1, -1, -1))
         self._guide_rp, self._guide_ed = FirstFit(ops.GUIDE_ROWPTR_ARENA), FirstFit(ops.GUIDE_EDGE_ARENA)
+        # ops.byte_guide: the state arenas, and room for the vocabulary's bytes (a token over the cap is stored cut
+        # to one byte more than the cap, which bars it just the same)
+        v = self.model.arch.vocab_size
+        self.d_bguide = (torch.full((ops.GUIDE_BYTE_STATE_ARENA, 256), -1, dtype=torch.int16, device=dev),
+                         torch.zeros(ops.GUIDE_BYTE_STATE_ARENA, dtype=torch.uint8, device=dev),
+                         torch.zeros(v + 1, dtype=i32, device=dev),
+                         torch.zeros(v * (GUIDE_MAX_TOKEN_BYTES + 1), dtype=torch.uint8, device=dev))
+        self._bguide_st = FirstFit(ops.GUIDE_BYTE_STATE_ARENA)
 
     @staticmethod
     def _guides(seqs) -> bool:
@@ -347,13 +364,31 @@ class ModelRunner:
         return 2 if self._guides(seqs) else 1 if self._asks(seqs) else 0
 
     @torch.inference_mode()
-    def guide_admit(self, seq: Sequence, auto: Automaton) -> None:
-        """Reference the arena region of the sequence's automaton (LLMEngine.add_request: a ValueError here
-        refuses the request). Sequences with the same spec share one region; a new one is uploaded first-fit,
-        evicting unreferenced regions, least recently used first, until it fits."""
+    def guide_admit(self, seq: Sequence, auto) -> None:
+        """Reference the arena region of the sequence's automaton, an Automaton or a ByteGuide
+        (LLMEngine.add_request: a ValueError here refuses the request). Sequences with the same spec share one
+        region; a new one is uploaded first-fit, evicting unreferenced regions, least recently used first, until
+        it fits."""
         self._guide_alloc()
         reg = self._guide_regions.get(auto.key)
-        if reg is None:
+        if isinstance(auto, ByteGuide):
+            self._bguide_vocab(auto)
+        if reg is None and isinstance(auto, ByteGuide):
+            n = auto.n_states
+            while True:
+                st = self._bguide_st.alloc(n)
+                if st is not None:
+                    break
+                old = next((k for k in self._guide_lru if "st" in self._guide_regions[k]), None)
+                if old is None:
+                    raise ValueError("no room for the request's guide: the constrained-decoding arena is full")
+                del self._guide_lru[old]
+                self._guide_drop(old)
+            d_tr, d_ac, _, _ = self.d_bguide
+            d_tr[st:st + n].copy_(torch.from_numpy(auto.trans))
+            d_ac[st:st + n].copy_(torch.from_numpy(auto.accept))
+            reg = self._guide_regions[auto.key] = {"auto": auto, "st": st, "refs": 0}
+        elif reg is None:
             n_rp, n_ed = auto.n_states + 1, auto.n_edges
             while True:
                 rp = self._guide_rp.alloc(n_rp)
@@ -362,9 +397,10 @@ class ModelRunner:
                     break
                 if rp is not None:
                     self._guide_rp.release(rp, n_rp)
-                if not self._guide_lru:
+                old = next((k for k in self._guide_lru if "rp" in self._guide_regions[k]), None)
+                if old is None:
                     raise ValueError("no room for the request's guide: the constrained-decoding arena is full")
-                old, _ = self._guide_lru.popitem(last=False)
+                del self._guide_lru[old]
                 self._guide_drop(old)
             _, d_rp, d_ed, _, _ = self.d_guide
             # on the compute stream: behind every queued window that may still read what lay here
@@ -375,8 +411,32 @@ class ModelRunner:
         reg["refs"] += 1
         self._guide_refs[seq.seq_id] = auto.key
 
+    def _bguide_vocab(self, guide: ByteGuide) -> None:
+        """The vocabulary's bytes on the device: uploaded (on the compute stream, behind every queued window) when
+        the first ByteGuide arrives, and again only if the engine was paired with another byte table since — which
+        is refused while a sequence still walks the old one."""
+        tid = guide.key[-1]
+        if tid == self._bguide_table:
+            return
+        if any("st" in self._guide_regions[k] for k in self._guide_refs.values()):
+            raise ValueError("guided_regex: the tokenizer's byte table changed while guided requests are running")
+        _, _, d_off, d_by = self.d_bguide
+        v = d_off.shape[0] - 1
+        table = table_of(tid)
+        cut = [(table[t] or b"")[:GUIDE_MAX_TOKEN_BYTES + 1] if t < len(table) else b"" for t in range(v)]
+        off = np.zeros(v + 1, dtype=np.int32)
+        np.cumsum([len(b) for b in cut], out=off[1:])
+        data = np.frombuffer(b"".join(cut), dtype=np.uint8)
+        d_off.copy_(torch.from_numpy(off))
+        if len(data):
+            d_by[:len(data)].copy_(torch.from_numpy(data.copy()))
+        self._bguide_table = tid
+
     def _guide_drop(self, key: tuple) -> None:
         reg = self._guide_regions.pop(key)
+        if "st" in reg:
+            self._bguide_st.release(reg["st"], reg["auto"].n_states)
+            return
         self._guide_rp.release(reg["rp"], reg["auto"].n_states + 1)
         self._guide_ed.release(reg["ed"], reg["auto"].n_edges)
 
@@ -398,7 +458,10 @@ class ModelRunner:
         auto = reg["auto"]
         pre = list(getattr(seq, "_preempted_outputs", None) or ())
         state = walk(auto, 0, pre + (seq.output_ids if all_outputs else seq.output_ids[:-1]))
-        self.h_guide.numpy()[:] = (reg["rp"], auto.n_states, reg["ed"], auto.n_edges, state, 0)
+        if "st" in reg:
+            self.h_guide.numpy()[:] = (reg["st"], auto.n_states, auto.eos, 0, state, 0)
+        else:
+            self.h_guide.numpy()[:] = (reg["rp"], auto.n_states, reg["ed"], auto.n_edges, state, 0)
         d_desc, _, _, d_cur, d_err = self.d_guide
         nb = self.is_cuda
         d_desc[slot].copy_(self.h_guide[0:4], non_blocking=nb)
@@ -429,21 +492,37 @@ class ModelRunner:
     def guide_arena_edges_used(self) -> int:
         return self._guide_ed.used if self._guide_ed is not None else 0
 
+    def guide_arena_states_used(self) -> int:
+        """States of the byte guides held on the device (ops.byte_guide's arenas)."""
+        return self._bguide_st.used if self._bguide_st is not None else 0
+
     def _fill_guide(self, seqs: Seq[Sequence], n_pad: int, all_outputs: bool) -> bool:
-        """d_guide_slot[:n_pad] for the step (-1: padding, and rows that are not guided); False and nothing
-        written when no row is guided — only the guided graphs read it."""
+        """d_guide_slot[:n_pad] and d_bguide_slot[:n_pad] for the step (-1: padding, rows that are not guided, and
+        in each vector the rows the other kernel guides); False and nothing written when no row is guided — only
+        the guided graphs read them."""
         if not self._guides(seqs):
             return False
         n = len(seqs)
-        ns = self.h_guide_slot.numpy()
-        ns[:n] = [self._guide_build(s, all_outputs) if s.sampling.guided else -1 for s in seqs]
+        ns, nb = self.h_guide_slot.numpy(), self.h_bguide_slot.numpy()
+        for i, s in enumerate(seqs):
+            slot = self._guide_build(s, all_outputs) if s.sampling.guided else -1
+            byte = slot >= 0 and "st" in self._guide_regions[self._guide_refs[s.seq_id]]
+            ns[i], nb[i] = (-1, slot) if byte else (slot, -1)
         ns[n:n_pad] = -1
+        nb[n:n_pad] = -1
         self.d_guide_slot[:n_pad].copy_(self.h_guide_slot[:n_pad], non_blocking=self.is_cuda)
+        self.d_bguide_slot[:n_pad].copy_(self.h_bguide_slot[:n_pad], non_blocking=self.is_cuda)
         return True
 
     def _launch_token_guide(self, logits: torch.Tensor, n: int, advance_ids=None, lm_part=None) -> None:
+        """ops.token_guide for the rows a CSR automaton guides and, directly behind it, ops.byte_guide for the rows
+        a ByteGuide does; the workgroups of every other row exit at once in each."""
+        desc, _, _, cur, err = self.d_guide
         ops.token_guide(logits, self.d_guide_slot[:n], *self.d_guide, advance_ids=advance_ids, lm_part=lm_part)
         self.token_guide_launches += 1
+        ops.byte_guide(logits, self.d_bguide_slot[:n], desc, *self.d_bguide, cur, err, advance_ids=advance_ids,
+                       lm_part=lm_part)
+        self.byte_guide_launches += 1
 
     def _guide_err_to_host(self) -> None:
         """Queue the sticky error words behind a guided step: they come back with its tokens."""
@@ -919,12 +998,13 @@ class ModelRunner:
             torch.cuda.synchronize(self.device)
             self.logit_process_launches = 0  # warm-up and capture served no request
         if self.supports_logit_processing and self.supports_token_guide:
-            # a third set, LM head -> ops.logit_process -> ops.token_guide -> the unchanged tail, for batches with a
-            # guided row (_guides); rows that did not ask have slot -1 in both kernels. The two sets above stay
-            # exactly what they were.
+            # a third set, LM head -> ops.logit_process -> ops.token_guide -> ops.byte_guide -> the unchanged tail,
+            # for batches with a guided row (_guides); rows that did not ask have slot -1 in all three kernels.
+            # The two sets above stay exactly what they were.
             self._guide_alloc()
             self.d_pen_slot.fill_(-1)
             self.d_guide_slot.fill_(-1)
+            self.d_bguide_slot.fill_(-1)
             for b in sizes:
                 self._decode_forward(b, process=True, guide=True)
             torch.cuda.synchronize(self.device)
@@ -935,7 +1015,7 @@ class ModelRunner:
                 self.graphs_guided[b] = g
                 self.graph_logits_guided[b] = self._last_logits
             torch.cuda.synchronize(self.device)
-            self.logit_process_launches = self.token_guide_launches = 0
+            self.logit_process_launches = self.token_guide_launches = self.byte_guide_launches = 0
         self.graph_sizes = sizes
         logger.info("captured decode hipGraphs for batch sizes %s", sizes)
 
@@ -1034,6 +1114,7 @@ class ModelRunner:
             self.logit_process_launches += k
         if mode == 2:
             self.token_guide_launches += k
+            self.byte_guide_launches += k
         if top < 0:
             for _ in range(k):
                 g.replay()
@@ -1103,6 +1184,7 @@ class ModelRunner:
                 g = (self.graphs_proc, self.graphs_guided)[mode - 1][pad]
                 self.logit_process_launches += 1
                 self.token_guide_launches += mode == 2
+                self.byte_guide_launches += mode == 2
             g.replay()
             return self.d_out
         # eager: a guided step launches ops.logit_process only when a row asks for it

@@ -1,6 +1,7 @@
 """
 Constrained decoding on the host: three front ends (``allowed_token_ids``, ``guided_choice``, ``guided_regex``)
-compile to ONE target form, a token automaton in CSR, which ``ops.token_guide`` walks on the device.
+compile to a token automaton in CSR, which ``ops.token_guide`` walks on the device; a ``guided_regex`` over a
+multi-byte vocabulary compiles to the second form below instead.
 
     row_ptr[S + 1]   edges of state s: [row_ptr[s], row_ptr[s + 1])
     edge_tok[E]      ascending and unique within a state
@@ -20,6 +21,17 @@ Invariant: every reachable state has at least one edge (no dead ends), so a step
   upper-case escapes range over ASCII bytes only (``.`` excludes ``\\n``). Anything else is a ValueError naming
   the position.
 
+The second form, ``ByteGuide``: the pruned byte DFA itself (``trans`` int16 [S, 256], ``accept`` uint8 [S]).
+``ops.byte_guide`` walks every token's bytes through it inside the decode step, so nothing is lifted on the host:
+compile time is ``regex_to_dfa`` alone, memory is S * 512 bytes and no edge cap applies. ``compile_guide`` picks it
+for a ``guided_regex`` whose byte table holds an entry longer than one byte (a BPE vocabulary); the single-byte
+table keeps the CSR form. State S is a virtual sink: entered by EOS from an accepting state, only EOS is legal in it
+and keeps it. A token longer than GUIDE_MAX_TOKEN_BYTES bytes is never allowed — that only narrows the set, and
+its bytes can still be spelled by shorter tokens. Every byte that labels a transition must have a single-byte token
+other than EOS (checked at compile time): then "no dead ends" carries over from the byte DFA to tokens.
+``hf_token_bytes`` derives the byte table of a HuggingFace tokenizer (ByteLevel BPE, or SentencePiece pieces with
+byte fallback).
+
 Pure numpy / Python: imported by ``src.preproc`` for early validation, never touches torch.
 """
 
@@ -37,6 +49,7 @@ GUIDE_MAX_STATES = 16384
 GUIDE_MAX_EDGES = 262144           # twice the largest vocabulary
 GUIDE_MAX_CHOICES = 1024
 GUIDE_MAX_CHOICE_TOKENS = 65536
+GUIDE_MAX_TOKEN_BYTES = 32         # ops.byte_guide never allows a longer token (launchers.h)
 _QUANT_MAX = 1024                  # {m,n} bound: larger counts only ever end at the state cap
 
 
@@ -60,9 +73,54 @@ class Automaton:
         return self.edge_tok[lo:hi], self.edge_next[lo:hi]
 
 
-def walk(automaton: Automaton, state: int, tokens: Iterable[int]) -> int:
+@dataclass(frozen=True, eq=False)
+class ByteGuide:
+    trans: np.ndarray      # int16 [S, 256], -1: no transition; start state 0
+    accept: np.ndarray     # uint8 [S]
+    eos: int
+    key: tuple             # the canonical spec; its last element names the byte table (id_of / table_of)
+
+    @property
+    def n_states(self) -> int:
+        return self.trans.shape[0]
+
+    @property
+    def sink(self) -> int:
+        return self.trans.shape[0]
+
+
+def walk_bytes(guide: ByteGuide, state: int, tokens: Iterable[int],
+               token_bytes: Optional[Sequence[Optional[bytes]]] = None) -> int:
+    """``walk`` for a ByteGuide, by the device's rules (csrc/kernels/byte_guide.hip): EOS from an accepting state
+    or in the sink gives the sink; any other token walks its bytes. A ValueError where the device would report
+    GUIDE_ERR_NO_EDGE."""
+    if token_bytes is None:
+        token_bytes = table_of(guide.key[-1])
+    n = guide.n_states
+    for t in tokens:
+        t = int(t)
+        if t == guide.eos:
+            if state != n and not guide.accept[state]:
+                raise ValueError(f"end of sequence in guide state {state}, which does not accept")
+            state = n
+            continue
+        bs = token_bytes[t] if 0 <= t < len(token_bytes) else None
+        if state == n or not bs or len(bs) > GUIDE_MAX_TOKEN_BYTES:
+            raise ValueError(f"token {t} has no edge in guide state {state}")
+        s = state
+        for b in bs:
+            s = int(guide.trans[s, b])
+            if s < 0:
+                raise ValueError(f"token {t} has no edge in guide state {state}")
+        state = s
+    return state
+
+
+def walk(automaton, state: int, tokens: Iterable[int]) -> int:
     """The state after ``tokens`` from ``state``. A token without an edge is a ValueError: the runner rebuilds
     device state from tokens the automaton itself allowed, so this never happens to a healthy sequence."""
+    if isinstance(automaton, ByteGuide):
+        return walk_bytes(automaton, state, tokens)
     for t in tokens:
         toks, nxt = automaton.edges(state)
         i = int(np.searchsorted(toks, t))
@@ -552,6 +610,8 @@ def compile_regex(pattern: str, token_bytes: Sequence[Optional[bytes]], eos: int
 
 
 _TABLE_IDS: Dict[int, tuple] = {}
+_TABLES: List[Sequence[Optional[bytes]]] = []   # by id_of
+_TABLE_FACTS: Dict[tuple, tuple] = {}
 
 
 def id_of(token_bytes) -> int:
@@ -560,7 +620,109 @@ def id_of(token_bytes) -> int:
     ent = _TABLE_IDS.get(id(token_bytes))
     if ent is None:
         ent = _TABLE_IDS[id(token_bytes)] = (token_bytes, len(_TABLE_IDS))
+        _TABLES.append(token_bytes)
     return ent[1]
+
+
+def table_of(table_id: int) -> Sequence[Optional[bytes]]:
+    """The byte table that id_of numbered ``table_id`` (a ByteGuide's key ends in it)."""
+    return _TABLES[table_id]
+
+
+def _table_facts(token_bytes, eos: int, vocab: int) -> tuple:
+    """(an entry is longer than one byte, the bytes that have a single-byte token other than EOS) of the table's
+    first ``vocab`` entries: one pass per table, kept."""
+    k = (id_of(token_bytes), int(eos), int(vocab))
+    f = _TABLE_FACTS.get(k)
+    if f is None:
+        multi, single = False, set()
+        for t in range(min(vocab, len(token_bytes))):
+            bs = token_bytes[t]
+            if not bs:
+                continue
+            if len(bs) > 1:
+                multi = True
+            elif t != eos:
+                single.add(bs[0])
+        f = _TABLE_FACTS[k] = (multi, frozenset(single))
+    return f
+
+
+def compile_byte_guide(pattern: str, token_bytes: Sequence[Optional[bytes]], eos: int,
+                       vocab: Optional[int] = None) -> ByteGuide:
+    """The ByteGuide of a pattern: regex_to_dfa and the soundness check, nothing per token. ValueError: what
+    regex_to_dfa refuses, and a byte on a transition that no single-byte token (other than EOS) spells — a state
+    could then be left without any legal token."""
+    trans, accept = regex_to_dfa(pattern)
+    vocab = len(token_bytes) if vocab is None else min(vocab, len(token_bytes))
+    _, single = _table_facts(token_bytes, eos, vocab)
+    used = np.nonzero((trans >= 0).any(axis=0))[0]
+    for b in used:
+        if int(b) not in single:
+            raise ValueError(f"guided_regex needs byte 0x{int(b):02X}, which is not supported on this tokenizer: no "
+                             "single-byte token spells it")
+    return ByteGuide(np.ascontiguousarray(trans, dtype=np.int16), np.ascontiguousarray(accept, dtype=np.uint8),
+                     int(eos), ("regex", pattern, int(eos), id_of(token_bytes)))
+
+
+# ------------------------------------------------------------------ byte tables of HuggingFace tokenizers
+def _bytelevel_alphabet() -> Dict[str, int]:
+    """The inverse of GPT-2's bytes-to-unicode map: printable Latin-1 stands for itself, the other 68 bytes for
+    U+0100 onwards in ascending byte order."""
+    keep = list(range(0x21, 0x7F)) + list(range(0xA1, 0xAD)) + list(range(0xAE, 0x100))
+    inv = {chr(b): b for b in keep}
+    n = 0
+    for b in range(256):
+        if b not in keep:
+            inv[chr(256 + n)] = b
+            n += 1
+    return inv
+
+
+_HF_CHECK_TEXTS = ("Hello, world! 123", " two  spaces\nand a line", "café ☃ {\"k\": [1, 2]}")
+
+
+def hf_token_bytes(tokenizer, vocab: int) -> Optional[List[Optional[bytes]]]:
+    """id -> bytes | None for a HuggingFace tokenizer, ``vocab`` entries (the model's vocabulary; ids beyond the
+    tokenizer's are None, and so are special and added tokens). Two layouts are recognised: ByteLevel BPE (every
+    piece is spelled in the bytes-to-unicode alphabet) and SentencePiece-style pieces with byte fallback (``<0xXX>``
+    is that byte, ``▁`` a space, anything else its UTF-8 bytes). None when neither fits or when a few strings do
+    not round-trip (the bytes of ``encode(text)`` must spell ``text``): guided_regex is then refused."""
+    try:
+        pieces = dict(tokenizer.get_vocab())
+        special = set(int(i) for i in getattr(tokenizer, "all_special_ids", ()) or ())
+        added = getattr(tokenizer, "get_added_vocab", None)
+        special |= set(int(i) for i in (added() if added is not None else {}).values())
+    except Exception:
+        return None
+    if not pieces:
+        return None
+    plain = [(p, int(i)) for p, i in pieces.items() if int(i) not in special and 0 <= int(i) < vocab]
+    alpha = _bytelevel_alphabet()
+    table: List[Optional[bytes]] = [None] * vocab
+    if all(all(ch in alpha for ch in p) for p, _ in plain):
+        for p, i in plain:
+            table[i] = bytes(alpha[ch] for ch in p)
+    elif any(len(p) == 6 and p.startswith("<0x") and p.endswith(">") for p, _ in plain):
+        for p, i in plain:
+            if len(p) == 6 and p.startswith("<0x") and p.endswith(">"):
+                try:
+                    table[i] = bytes([int(p[3:5], 16)])
+                    continue
+                except ValueError:
+                    pass
+            table[i] = p.replace("▁", " ").encode("utf-8")
+    else:
+        return None
+    try:
+        for text in _HF_CHECK_TEXTS:
+            ids = tokenizer.encode(text, add_special_tokens=False)
+            got = b"".join(table[i] or b"" for i in ids if 0 <= i < vocab)
+            if got != text.encode("utf-8") or any(not 0 <= i < vocab or table[i] is None for i in ids):
+                return None
+    except Exception:
+        return None
+    return table
 
 
 # ------------------------------------------------------------------ the one entry point, cached
@@ -569,10 +731,9 @@ _CACHE_MAX = 64
 _LOCK = threading.Lock()
 
 
-def compile_guide(sampling, vocab: int, eos: Optional[int], token_bytes: Optional[Sequence[Optional[bytes]]] = None
-                  ) -> Automaton:
+def compile_guide(sampling, vocab: int, eos: Optional[int], token_bytes: Optional[Sequence[Optional[bytes]]] = None):
     """The automaton of a request's guide (SamplingParams.guided is true), from a small LRU keyed by the
-    canonical spec. ValueError for everything the engine must refuse."""
+    canonical spec: an Automaton, or a ByteGuide for a guided_regex over a multi-byte vocabulary. ValueError for everything the engine must refuse."""
     if sampling.allowed_token_ids is not None:
         spec = ("allowed", tuple(sorted(sampling.allowed_token_ids)), vocab)
     else:
@@ -586,7 +747,8 @@ def compile_guide(sampling, vocab: int, eos: Optional[int], token_bytes: Optiona
         else:
             if token_bytes is None:
                 raise ValueError("guided_regex is not supported on an engine without a byte table of its "
-                                 "tokenizer (only the byte-level tokenizer provides one)")
+                                 "tokenizer (the byte-level tokenizer, ByteLevel BPE and byte-fallback "
+                                 "vocabularies provide one)")
             spec = ("regex", sampling.guided_regex, vocab, eos, id_of(token_bytes))
     with _LOCK:
         a = _CACHE.get(spec)
@@ -597,9 +759,15 @@ def compile_guide(sampling, vocab: int, eos: Optional[int], token_bytes: Optiona
         a = compile_allowed(spec[1], vocab)
     elif spec[0] == "choice":
         a = compile_choice(spec[1], eos, vocab)
+    elif _table_facts(token_bytes, eos, min(vocab, len(token_bytes)))[0]:
+        # a multi-byte vocabulary: the byte DFA itself, walked per token on the device (ops.byte_guide)
+        a = compile_byte_guide(spec[1], token_bytes, eos, vocab)
     else:
         a = compile_regex(spec[1], token_bytes, eos, vocab)
-    a = Automaton(a.row_ptr, a.edge_tok, a.edge_next, spec)
+    if isinstance(a, ByteGuide):
+        a = ByteGuide(a.trans, a.accept, a.eos, spec)
+    else:
+        a = Automaton(a.row_ptr, a.edge_tok, a.edge_next, spec)
     with _LOCK:
         _CACHE[spec] = a
         while len(_CACHE) > _CACHE_MAX:

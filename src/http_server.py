@@ -30,9 +30,12 @@ coordinator's framed-RPC API. It holds no model state — every request becomes 
     of the processed distribution (before temperature / top-k / top-p); without them nothing changes.
     Constrained decoding (both endpoints): allowed_token_ids bars every other token at every step, guided_choice
     yields exactly one of its choices and then EOS, guided_regex an output that fully matches the pattern (the
-    byte-level subset of src/guided.py) and then EOS. Barred tokens have logprob -inf (-9999.0 here). A malformed
-    value, two of the three at once, unsupported regex syntax, ignore_eos with a choice or a pattern, or any of
-    them on a model served tensor-parallel is a 400.
+    byte-level subset of src/guided.py) and then EOS — on the byte-level tokenizer and on HuggingFace BPE
+    vocabularies alike (ByteLevel BPE, or pieces with byte fallback: every token's bytes are walked through the
+    pattern's automaton on the GPU). Barred tokens have logprob -inf (-9999.0 here). A malformed value, two of the
+    three at once, unsupported regex syntax, ignore_eos with a choice or a pattern, or any of them on a model
+    served tensor-parallel is a 400; so is guided_regex with a tokenizer whose layout is not recognised, or with a
+    pattern that needs a byte no single-byte token of the vocabulary spells.
     POST /v1/embeddings    {"model", "input": str | [str] | [token ids] | [[token ids]] (<= 2048 items),
                             "encoding_format": "float" | "base64", "dimensions": multiple of 8,
                             "pooling": "last" | "mean", "normalize": bool}

@@ -307,6 +307,35 @@ def token_guide(logits: torch.Tensor, slot: torch.Tensor, desc: torch.Tensor, ro
     return logits
 
 
+# constrained decoding over a multi-byte vocabulary (launchers.h)
+GUIDE_MAX_TOKEN_BYTES = ref.GUIDE_MAX_TOKEN_BYTES  # a longer token is never allowed: its bytes can still be spelled
+GUIDE_BYTE_STATE_ARENA = 65536   # states shared by all slots: trans int16 [., 256] 32 MiB, accept uint8 64 KiB
+GUIDE_BYTE_LDS_STATES = 208      # a guide of up to this many states is walked from LDS, a larger one through L2
+GUIDE_TOK_TABLE_MAX = 1 << 20    # tokens in the vocabulary's byte table
+GUIDE_TOK_BYTES_MAX = 1 << 25    # bytes in it
+
+
+def byte_guide(logits: torch.Tensor, slot: torch.Tensor, desc: torch.Tensor, trans: torch.Tensor,
+               accept: torch.Tensor, tok_off: torch.Tensor, tok_bytes: torch.Tensor, cur: torch.Tensor,
+               err: torch.Tensor, advance_ids: Optional[torch.Tensor] = None,
+               lm_part: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Constrained decoding on ``logits`` [rows, vocab] bf16 IN PLACE for vocabularies with multi-byte tokens: every
+    token whose BYTES the row's byte DFA cannot read from its current state becomes ``-inf``, an allowed entry keeps
+    its exact bits (:func:`reference.byte_guide_rows` is the contract). Row r uses the tables of ``slot[r]`` (int32;
+    < 0: the row is left untouched): ``desc`` int32 [slots, 4] = (state_base, n_states, eos, 0) into the arenas
+    ``trans`` int16 [A, 256] (-1: no transition) and ``accept`` uint8 [A]; state ``n_states`` is the sink, entered
+    by EOS from an accepting state, where only EOS is allowed. ``tok_off`` int32 [n_tok + 1] / ``tok_bytes`` uint8
+    [B]: the vocabulary's bytes (length 0: never allowed; longer than GUIDE_MAX_TOKEN_BYTES: never allowed either;
+    the kernel fetches eight bytes at a time and refuses a table with B < 8).
+    ``cur`` / ``err`` int32 [slots], ``advance_ids`` and ``lm_part`` as in :func:`token_guide` (the same arrays: a
+    slot belongs to one of the two ops)."""
+    if not logits.is_cuda:
+        return ref.byte_guide_rows(logits, slot, desc, trans, accept, tok_off, tok_bytes, cur, err, advance_ids,
+                                   lm_part)
+    _kern().byte_guide(logits, slot, desc, trans, accept, tok_off, tok_bytes, cur, err, advance_ids, lm_part)
+    return logits
+
+
 # embedding pooling (launchers.h): a segment descriptor's flag bits, and the row split of long mean segments
 POOL_MEAN, POOL_FIRST, POOL_FINAL = 1, 2, 4
 POOL_MAX_PARTS = 64    # workgroups per segment

@@ -289,6 +289,103 @@ def token_guide_rows(logits, slot, desc, rowptr, edges, cur, err, advance_ids=No
     return logits
 
 
+GUIDE_MAX_TOKEN_BYTES = 32  # byte_guide never allows a longer token
+
+
+def byte_guide_rows(logits, slot, desc, trans, accept, tok_off, tok_bytes, cur, err, advance_ids=None, lm_part=None):
+    """ops.byte_guide on host tensors (the contract of csrc/kernels/byte_guide.hip): row r -> slot[r] -> desc
+    (state_base, n_states, eos, 0) into trans int16 [A, 256] / accept uint8 [A]; state n_states is the sink. The
+    state advances over advance_ids[r] first (EOS from an accepting state or the sink: the sink; a token whose
+    bytes die, without bytes, over the length cap, beyond the table, or any token but EOS in the sink: err |= 1,
+    state kept). Allowed next: in the sink EOS alone; else EOS iff the state accepts, and every token of 1..32
+    bytes whose walk never dies. Barred entries become -inf, the others keep their bits; lm_part candidates are
+    overwritten with the best allowed entry. Anything out of bounds: err |= 2 and row, candidates and state stay
+    untouched."""
+    import numpy as np
+
+    vocab = logits.shape[1]
+    tr_all, ac_all = trans.numpy(), accept.numpy()
+    off, by = tok_off.numpy().astype(np.int64), tok_bytes.numpy()
+    arena, n_tok, blen = min(tr_all.shape[0], ac_all.shape[0]), len(off) - 1, len(by)
+    lim = min(vocab, n_tok)
+    for r in range(logits.shape[0]):
+        s = int(slot[r])
+        if s < 0 or s >= desc.shape[0]:
+            continue
+        sb, ns, eos = (int(v) for v in desc[s, :3])
+        c = int(cur[s])
+        if sb < 0 or ns < 1 or sb + ns > arena or not 0 <= c <= ns or not 0 <= eos < vocab:
+            err[s] |= GUIDE_ERR_TABLE
+            continue
+        tr, ac = tr_all[sb:sb + ns], ac_all[sb:sb + ns]
+        flags, bad = 0, False
+        if advance_ids is not None:
+            tok = int(advance_ids[r])
+            if tok == eos:
+                if c == ns or ac[c]:
+                    c = ns
+                else:
+                    flags = GUIDE_ERR_NO_EDGE
+            elif c == ns or not 0 <= tok < lim:
+                flags = GUIDE_ERR_NO_EDGE
+            else:
+                lo, hi = int(off[tok]), int(off[tok + 1])
+                if not 0 <= lo <= hi <= blen:
+                    bad = True
+                elif hi == lo or hi - lo > GUIDE_MAX_TOKEN_BYTES:
+                    flags = GUIDE_ERR_NO_EDGE
+                else:
+                    st = c
+                    for p in range(lo, hi):
+                        st = int(tr[st, by[p]])
+                        if st < -1 or st >= ns:
+                            bad = True
+                        if st < 0 or bad:
+                            break
+                    if st < 0:
+                        flags = GUIDE_ERR_NO_EDGE
+                    elif not bad:
+                        c = st
+        allowed = np.zeros(vocab, dtype=bool)
+        if not bad and c < ns:
+            lo, hi = off[:lim], off[1:lim + 1]
+            bad = bool(((lo < 0) | (hi < lo) | (hi > blen)).any())
+            if not bad:
+                ln = hi - lo
+                st = np.where((ln >= 1) & (ln <= GUIDE_MAX_TOKEN_BYTES), c, -1).astype(np.int64)
+                for level in range(GUIDE_MAX_TOKEN_BYTES):
+                    idx = np.nonzero((st >= 0) & (level < ln))[0]
+                    if not len(idx):
+                        break
+                    v = tr[st[idx], by[lo[idx] + level]].astype(np.int64)
+                    bad = bad or bool(((v < -1) | (v >= ns)).any())
+                    st[idx] = np.where((v < -1) | (v >= ns), -1, v)
+                allowed[:lim] = st >= 0
+                allowed[eos] = bool(ac[c])
+        elif not bad:
+            allowed[eos] = True
+        if bad:
+            err[s] |= GUIDE_ERR_TABLE
+            continue
+        cur[s] = c
+        err[s] |= flags
+        allowed = torch.from_numpy(allowed)
+        logits[r, :vocab] = torch.where(allowed, logits[r, :vocab],
+                                        torch.tensor(float("-inf"), dtype=logits.dtype))
+        if lm_part is not None:
+            x = logits[r, :vocab].float()
+            ok = allowed & ~torch.isnan(x)  # a NaN never wins a comparison (sampling.hip's better())
+            x = torch.where(ok, x, torch.tensor(float("-inf")))
+            v = x.max()
+            first = ((x == v) & ok).nonzero()  # lowest allowed index holding the maximum
+            lm_part[r, :, 0] = torch.tensor(float("-inf")).view(torch.int32)
+            lm_part[r, :, 1] = 0x7fffffff
+            if first.numel():
+                lm_part[r, 0, 0] = x[int(first[0])].view(torch.int32)  # that entry's own bits (-0.0 equals +0.0)
+                lm_part[r, 0, 1] = int(first[0])
+    return logits
+
+
 POOL_MEAN, POOL_FIRST, POOL_FINAL = 1, 2, 4  # flag bits of a pool_embed segment descriptor
 
 
