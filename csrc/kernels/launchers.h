@@ -156,6 +156,18 @@ hipError_t launch_byte_guide(bf16_t* logits, int64_t stride, int rows, int vocab
                              int64_t bytes_len, int* cur, int* err, const int64_t* advance_ids, uint32_t* lm_part,
                              int lm_parts, hipStream_t s);
 
+// JSON mode (json_guide.hip): as launch_byte_guide, but the guide is one byte PUSHDOWN table for all slots, trans int16
+// [table_states, 256] (-1, or next state | action << 8: 0 none, 1 push-object, 2 push-array, 3 pop), desc
+// [num_slots, 4] = (n_states, done, eos, 0), and a slot's configuration is cur[slot] with jstk int32 [num_slots, 2] =
+// (depth, stack bits). tok_off / tok_bytes are byte_guide's tables, cur / err token_guide's arrays. hipErrorInvalidValue
+// for what launch_byte_guide refuses, a table above GUIDE_JSON_MAX_STATES and a jstk that is not 8-byte aligned.
+constexpr int GUIDE_JSON_MAX_DEPTH = 32;           // containers open at once: the stack is one 32-bit word
+constexpr int GUIDE_JSON_MAX_STATES = 92;          // the table's LDS copy: 46 KiB behind the 48 KiB bitmap
+hipError_t launch_json_guide(bf16_t* logits, int64_t stride, int rows, int vocab, const int* slot, int num_slots,
+                             const int* desc, const int16_t* trans, int64_t table_states, const int* tok_off,
+                             int64_t n_tok, const uint8_t* tok_bytes, int64_t bytes_len, int* cur, int* jstk, int* err,
+                             const int64_t* advance_ids, uint32_t* lm_part, int lm_parts, hipStream_t s);
+
 // embedding pooling of a prefill step's final-norm rows (pooling.hip): hidden bf16 [T, stride >= H]; segs int32
 // [num_segs, 8] = (first row, rows, acc slot, total prompt length, flags, part base, parts, 0); acc fp32 [slots, H]
 // (mean pooling's partial sums across chunks); out fp32 [num_segs, H], of which a FINAL (or last-pooling) segment

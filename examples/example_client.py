@@ -9,6 +9,7 @@
     python examples/example_client.py --model llama --prompt "Hello" --repetition-penalty 1.2 --logit-bias '{"50256": -100}'
     python examples/example_client.py --model llama --prompt "Is water wet? " --guided-choice yes no
     python examples/example_client.py --model llama --prompt "A date: " --guided-regex '\d{4}-\d{2}-\d{2}'
+    python examples/example_client.py --model llama --prompt "A JSON record: " --max-tokens 64 --json   # JSON mode
     python examples/example_client.py --model llama --prompt "a sentence to embed" --embed mean   # the prompt's vector
 """
 
@@ -41,6 +42,9 @@ async def main():
                     help="the output is exactly one of these strings, then EOS")
     ap.add_argument("--guided-regex", default=None, metavar="PATTERN",
                     help="the output fully matches this pattern (the byte-level subset of src/guided.py), then EOS")
+    ap.add_argument("--json", action="store_true", dest="json_object",
+                    help="JSON mode: the output is one JSON object, then EOS (a request cut off by --max-tokens "
+                         "returns an incomplete document with finish_reason length)")
     ap.add_argument("--embed", nargs="?", const="last", default=None, choices=["last", "mean"], metavar="POOLING",
                     help="return the prompt's embedding (last-token or mean pooling, L2-normalised) instead of text")
     ap.add_argument("--request-key", default=None, help="session key for shard affinity")
@@ -61,6 +65,8 @@ async def main():
             inputs["guided_choice"] = a.guided_choice
         if a.guided_regex is not None:
             inputs["guided_regex"] = a.guided_regex
+        if a.json_object:
+            inputs["guided_json_object"] = True
         if a.embed is not None:
             inputs = {"prompt": a.prompt, "pooling": a.embed}
     else:

@@ -294,7 +294,7 @@ def sampling_to_dict(sp: SamplingParams) -> Dict[str, Any]:
             "logit_bias": None if not sp.logit_bias else {str(k): v for k, v in sp.logit_bias.items()},
             "allowed_token_ids": None if sp.allowed_token_ids is None else list(sp.allowed_token_ids),
             "guided_choice": None if sp.guided_choice is None else [list(c) for c in sp.guided_choice],
-            "guided_regex": sp.guided_regex}
+            "guided_regex": sp.guided_regex, "guided_json_object": sp.guided_json_object}
 
 
 def packet_for_import(d: Dict[str, Any], device) -> KVPacket:

@@ -30,7 +30,7 @@ from src.config import EngineConfig
 from src.engine.block_manager import native_runtime
 from src.engine.scheduler import PrefillChunk
 from src.engine.sequence import Sequence
-from src.guided import GUIDE_MAX_TOKEN_BYTES, Automaton, ByteGuide, FirstFit, table_of, walk
+from src.guided import GUIDE_MAX_TOKEN_BYTES, Automaton, ByteGuide, FirstFit, JsonGuide, table_of, walk
 from src.models.llama import AttnMetadata, CausalLM
 
 logger = logging.getLogger(__name__)
@@ -180,6 +180,14 @@ class ModelRunner:
         self._bguide_st: Optional[FirstFit] = None
         self._bguide_table: Optional[int] = None  # guided.id_of the byte table that is on the device
         self.byte_guide_launches = 0            # eager launches and guided graph replays
+        # JSON mode (ops.json_guide, launched directly behind ops.byte_guide): one pushdown table for all slots,
+        # uploaded at the first such request, and a (depth, stack bits) pair per slot next to cur. The byte table,
+        # slots, descriptors, cur and err are the ones above. A row is in at most one of the three slot vectors.
+        self.h_jguide_slot = torch.full((self.max_seqs,), -1, dtype=i32, pin_memory=pin)
+        self.d_jguide_slot = torch.full((self.max_seqs,), -1, dtype=i32, device=dev)
+        self.d_jguide = None                    # (trans, jstk)
+        self._jguide_up = False                 # the table is on the device
+        self.json_guide_launches = 0            # eager launches and replays of the JSON graph set
         self._guide_slots: Dict[int, int] = {}  # seq_id -> slot
         self._guide_free: List[int] = []
         self._guide_refs: Dict[int, tuple] = {}  # seq_id -> the spec key of the region it references
@@ -190,6 +198,11 @@ class ModelRunner:
         self._guide_ev = None
         self.graphs_guided: Dict[int, torch.cuda.CUDAGraph] = {}  # LM head -> logit_process -> token_guide -> byte_guide -> tail
         self.graph_logits_guided: Dict[int, torch.Tensor] = {}
+        # a fourth set for batches with a JSON row: ... -> byte_guide -> json_guide -> tail (the guided set above stays
+        # launch for launch what it was before JSON mode)
+        self.graphs_json: Dict[int, torch.cuda.CUDAGraph] = {}
+        self.graph_logits_json: Dict[int, torch.Tensor] = {}
+        self._json = False                      # the step being assembled has a JSON row (_fill_guide)
         self.token_guide_launches = 0           # eager launches and guided graph replays
         self._guided = False                    # the step being assembled has a guided row (_fill_sampling)
         # embeddings (ops.pool_embed): requests with SamplingParams.pooling end with their prompt and return its
@@ -352,6 +365,10 @@ class ModelRunner:
                          torch.zeros(v + 1, dtype=i32, device=dev),
                          torch.zeros(v * (GUIDE_MAX_TOKEN_BYTES + 1), dtype=torch.uint8, device=dev))
         self._bguide_st = FirstFit(ops.GUIDE_BYTE_STATE_ARENA)
+        # ops.json_guide: the table, a slot's (depth, stack bits), and the pinned staging row of one slot's pair
+        self.d_jguide = (torch.full((ops.GUIDE_JSON_MAX_STATES, 256), -1, dtype=torch.int16, device=dev),
+                         torch.zeros(m, 2, dtype=i32, device=dev))
+        self.h_jguide = torch.zeros(2, dtype=i32, pin_memory=self.is_cuda)
 
     @staticmethod
     def _guides(seqs) -> bool:
@@ -359,21 +376,30 @@ class ModelRunner:
         return any(s.sampling.guided for s in seqs)
 
     def _mode(self, seqs) -> int:
-        """Which graph set a decode batch replays: 2 guided (a row is guided), 1 processed (a row set a penalty or
-        a bias), 0 raw."""
+        """Which graph set a decode batch replays: 3 guided with a row in JSON mode, 2 guided (a row is guided), 1
+        processed (a row set a penalty or a bias), 0 raw."""
+        if any(s.sampling.guided_json_object for s in seqs):
+            return 3
         return 2 if self._guides(seqs) else 1 if self._asks(seqs) else 0
 
     @torch.inference_mode()
     def guide_admit(self, seq: Sequence, auto) -> None:
-        """Reference the arena region of the sequence's automaton, an Automaton or a ByteGuide
+        """Reference the arena region of the sequence's automaton, an Automaton, a ByteGuide or a JsonGuide
         (LLMEngine.add_request: a ValueError here refuses the request). Sequences with the same spec share one
         region; a new one is uploaded first-fit, evicting unreferenced regions, least recently used first, until
         it fits."""
         self._guide_alloc()
         reg = self._guide_regions.get(auto.key)
-        if isinstance(auto, ByteGuide):
+        if isinstance(auto, (ByteGuide, JsonGuide)):
             self._bguide_vocab(auto)
-        if reg is None and isinstance(auto, ByteGuide):
+        if reg is None and isinstance(auto, JsonGuide):
+            # one table for every JSON request, uploaded once; the region entry takes no room in any arena (its key
+            # "js" is neither "st" nor "rp": the eviction loops below never pick it)
+            if not self._jguide_up:
+                self.d_jguide[0][:auto.n_states].copy_(torch.from_numpy(auto.trans))
+                self._jguide_up = True
+            reg = self._guide_regions[auto.key] = {"auto": auto, "js": 0, "refs": 0}
+        elif reg is None and isinstance(auto, ByteGuide):
             n = auto.n_states
             while True:
                 st = self._bguide_st.alloc(n)
@@ -411,15 +437,15 @@ class ModelRunner:
         reg["refs"] += 1
         self._guide_refs[seq.seq_id] = auto.key
 
-    def _bguide_vocab(self, guide: ByteGuide) -> None:
+    def _bguide_vocab(self, guide) -> None:
         """The vocabulary's bytes on the device: uploaded (on the compute stream, behind every queued window) when
-        the first ByteGuide arrives, and again only if the engine was paired with another byte table since — which
+        the first ByteGuide or JsonGuide arrives, and again only if the engine was paired with another byte table since — which
         is refused while a sequence still walks the old one."""
         tid = guide.key[-1]
         if tid == self._bguide_table:
             return
-        if any("st" in self._guide_regions[k] for k in self._guide_refs.values()):
-            raise ValueError("guided_regex: the tokenizer's byte table changed while guided requests are running")
+        if any("st" in self._guide_regions[k] or "js" in self._guide_regions[k] for k in self._guide_refs.values()):
+            raise ValueError("guided_regex / guided_json_object: the tokenizer's byte table changed while guided requests are running")
         _, _, d_off, d_by = self.d_bguide
         v = d_off.shape[0] - 1
         table = table_of(tid)
@@ -434,6 +460,8 @@ class ModelRunner:
 
     def _guide_drop(self, key: tuple) -> None:
         reg = self._guide_regions.pop(key)
+        if "js" in reg:  # the JSON table stays where it is
+            return
         if "st" in reg:
             self._bguide_st.release(reg["st"], reg["auto"].n_states)
             return
@@ -458,7 +486,12 @@ class ModelRunner:
         auto = reg["auto"]
         pre = list(getattr(seq, "_preempted_outputs", None) or ())
         state = walk(auto, 0, pre + (seq.output_ids if all_outputs else seq.output_ids[:-1]))
-        if "st" in reg:
+        if "js" in reg:  # the configuration (state, depth, stack bits), by the device's rules (guided.walk_json)
+            state, depth, bits = state
+            self.h_guide.numpy()[:] = (auto.n_states, auto.done, auto.eos, 0, state, 0)
+            self.h_jguide.numpy()[:] = (depth, bits - (1 << 32) if bits >= 1 << 31 else bits)
+            self.d_jguide[1][slot].copy_(self.h_jguide, non_blocking=self.is_cuda)
+        elif "st" in reg:
             self.h_guide.numpy()[:] = (reg["st"], auto.n_states, auto.eos, 0, state, 0)
         else:
             self.h_guide.numpy()[:] = (reg["rp"], auto.n_states, reg["ed"], auto.n_edges, state, 0)
@@ -497,32 +530,45 @@ class ModelRunner:
         return self._bguide_st.used if self._bguide_st is not None else 0
 
     def _fill_guide(self, seqs: Seq[Sequence], n_pad: int, all_outputs: bool) -> bool:
-        """d_guide_slot[:n_pad] and d_bguide_slot[:n_pad] for the step (-1: padding, rows that are not guided, and
-        in each vector the rows the other kernel guides); False and nothing written when no row is guided — only
+        """d_guide_slot[:n_pad], d_bguide_slot[:n_pad] and d_jguide_slot[:n_pad] for the step (-1: padding, rows that
+        are not guided, and in each vector the rows another kernel guides); False and nothing written when no row is guided — only
         the guided graphs read them."""
+        self._json = False
         if not self._guides(seqs):
             return False
         n = len(seqs)
-        ns, nb = self.h_guide_slot.numpy(), self.h_bguide_slot.numpy()
+        ns, nb, nj = self.h_guide_slot.numpy(), self.h_bguide_slot.numpy(), self.h_jguide_slot.numpy()
         for i, s in enumerate(seqs):
             slot = self._guide_build(s, all_outputs) if s.sampling.guided else -1
-            byte = slot >= 0 and "st" in self._guide_regions[self._guide_refs[s.seq_id]]
-            ns[i], nb[i] = (-1, slot) if byte else (slot, -1)
+            reg = self._guide_regions[self._guide_refs[s.seq_id]] if slot >= 0 else ()
+            ns[i], nb[i], nj[i] = (-1, -1, slot) if "js" in reg else (-1, slot, -1) if "st" in reg else (slot, -1, -1)
         ns[n:n_pad] = -1
         nb[n:n_pad] = -1
+        nj[n:n_pad] = -1
+        self._json = bool((nj[:n] >= 0).any())
         self.d_guide_slot[:n_pad].copy_(self.h_guide_slot[:n_pad], non_blocking=self.is_cuda)
         self.d_bguide_slot[:n_pad].copy_(self.h_bguide_slot[:n_pad], non_blocking=self.is_cuda)
+        self.d_jguide_slot[:n_pad].copy_(self.h_jguide_slot[:n_pad], non_blocking=self.is_cuda)
         return True
 
-    def _launch_token_guide(self, logits: torch.Tensor, n: int, advance_ids=None, lm_part=None) -> None:
+    def _launch_token_guide(self, logits: torch.Tensor, n: int, advance_ids=None, lm_part=None,
+                            json: Optional[bool] = None) -> None:
         """ops.token_guide for the rows a CSR automaton guides and, directly behind it, ops.byte_guide for the rows
-        a ByteGuide does; the workgroups of every other row exit at once in each."""
+        a ByteGuide does and — json (default: the step has a JSON row, _fill_guide) — ops.json_guide for those in
+        JSON mode; the workgroups of every other row exit at once in each."""
         desc, _, _, cur, err = self.d_guide
         ops.token_guide(logits, self.d_guide_slot[:n], *self.d_guide, advance_ids=advance_ids, lm_part=lm_part)
         self.token_guide_launches += 1
         ops.byte_guide(logits, self.d_bguide_slot[:n], desc, *self.d_bguide, cur, err, advance_ids=advance_ids,
                        lm_part=lm_part)
         self.byte_guide_launches += 1
+        if not (self._json if json is None else json):
+            return
+        _, _, tok_off, tok_bytes = self.d_bguide
+        d_jtr, d_jstk = self.d_jguide
+        ops.json_guide(logits, self.d_jguide_slot[:n], desc, d_jtr, tok_off, tok_bytes, cur, d_jstk, err,
+                       advance_ids=advance_ids, lm_part=lm_part)
+        self.json_guide_launches += 1
 
     def _guide_err_to_host(self) -> None:
         """Queue the sticky error words behind a guided step: they come back with its tokens."""
@@ -920,7 +966,7 @@ class ModelRunner:
             sc = self.dec_scratch
             ops.embed_sumsq(self.d_ids[:pad], self.model.embed, sc["ssp0"], out=sc["h_in"][:pad])
 
-    def _decode_forward(self, n: int, process: bool = False, guide: bool = False) -> torch.Tensor:
+    def _decode_forward(self, n: int, process: bool = False, guide: bool = False, json: bool = False) -> torch.Tensor:
         tail = self._fused_tail(n)
         meta = AttnMetadata(is_prefill=False, slot_mapping=self.d_slots[:n], block_tables=self.d_bt[:n],
                             ctx_lens=self.d_ctx[:n], max_ctx=self.max_model_len, part_o=self.part_o,
@@ -939,7 +985,8 @@ class ModelRunner:
         if guide:
             # after the penalties and biases, so that no bias can lift a barred token: advances the guided rows'
             # automata over this step's input ids, masks the rows and makes their greedy candidates agree
-            self._launch_token_guide(logits, n, advance_ids=self.d_ids[:n], lm_part=amax[:n] if amax is not None else None)
+            self._launch_token_guide(logits, n, advance_ids=self.d_ids[:n],
+                                     lm_part=amax[:n] if amax is not None else None, json=json)
         if not self.is_cuda:
             return ops.sample(logits, self.d_temp[:n], self.d_topk[:n], self.d_topp[:n], self.d_seed[:n],
                               self.d_step[:n])
@@ -1000,11 +1047,14 @@ class ModelRunner:
         if self.supports_logit_processing and self.supports_token_guide:
             # a third set, LM head -> ops.logit_process -> ops.token_guide -> ops.byte_guide -> the unchanged tail,
             # for batches with a guided row (_guides); rows that did not ask have slot -1 in all three kernels.
-            # The two sets above stay exactly what they were.
+            # The two sets above stay exactly what they were. Behind it a fourth set with ops.json_guide behind
+            # ops.byte_guide, replayed only by batches with a row in JSON mode: a guided batch without one pays
+            # nothing for JSON mode (the idle launch measured +2 to +3 us per step in the third set).
             self._guide_alloc()
             self.d_pen_slot.fill_(-1)
             self.d_guide_slot.fill_(-1)
             self.d_bguide_slot.fill_(-1)
+            self.d_jguide_slot.fill_(-1)
             for b in sizes:
                 self._decode_forward(b, process=True, guide=True)
             torch.cuda.synchronize(self.device)
@@ -1015,7 +1065,18 @@ class ModelRunner:
                 self.graphs_guided[b] = g
                 self.graph_logits_guided[b] = self._last_logits
             torch.cuda.synchronize(self.device)
+            for b in sizes:
+                self._decode_forward(b, process=True, guide=True, json=True)
+            torch.cuda.synchronize(self.device)
+            for b in reversed(sizes):
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, pool=self._graph_pool):
+                    self._decode_forward(b, process=True, guide=True, json=True)
+                self.graphs_json[b] = g
+                self.graph_logits_json[b] = self._last_logits
+            torch.cuda.synchronize(self.device)
             self.logit_process_launches = self.token_guide_launches = self.byte_guide_launches = 0
+            self.json_guide_launches = 0
         self.graph_sizes = sizes
         logger.info("captured decode hipGraphs for batch sizes %s", sizes)
 
@@ -1043,15 +1104,15 @@ class ModelRunner:
             self.h_ctl[1] = n
             self.d_ctl.copy_(self.h_ctl, non_blocking=True)
         self._sync_step(self.KIND_DECODE, n, pad)
-        mode = 2 if self._guided else int(self._proc)
+        mode = (3 if self._json else 2) if self._guided else int(self._proc)
         ids = self._exec_decode(n, pad, mode)
-        if mode == 2:
+        if mode >= 2:
             self._guide_err_to_host()
         top = self._lp_top(seqs)
         self.last_logprobs = None
         if top < 0:
             return self._to_host(ids, n)
-        glog = (self.graph_logits, self.graph_logits_proc, self.graph_logits_guided)[mode]
+        glog = (self.graph_logits, self.graph_logits_proc, self.graph_logits_guided, self.graph_logits_json)[mode]
         self._launch_logprobs(glog[pad] if pad in self.graphs else self._last_logits, ids, n, 0, top)
         self._lp_to_host(0, 1)
         toks = self._to_host(ids, n)
@@ -1089,7 +1150,7 @@ class ModelRunner:
         self.d_ctl.copy_(self.h_ctl, non_blocking=True)
         self._sync_window(n, pad, k)
         top = self._lp_top(seqs)
-        self._replay_window(pad, n, k, 0, top, 2 if self._guided else int(self._proc))
+        self._replay_window(pad, n, k, 0, top, (3 if self._json else 2) if self._guided else int(self._proc))
         self._queue_fault_readback()
         if k_next > 1:
             ev = torch.cuda.Event()
@@ -1108,27 +1169,30 @@ class ModelRunner:
         before the next replay overwrites them (stream order) — and the logprob rows come back with the tokens.
         mode (_mode) 1, a row asks for logit processing: the graphs with the ops.logit_process launch and their
         logits; 2, a row is guided: the graphs with the ops.token_guide launch behind it, and the slots' error
-        words come back with the tokens; 0: the raw graphs, launch for launch as without either feature."""
-        g = (self.graphs, self.graphs_proc, self.graphs_guided)[mode][pad]
+        words come back with the tokens; 3, a row is in JSON mode: the same with the ops.json_guide launch too; 0: the
+        raw graphs, launch for launch as without any of the features."""
+        g = (self.graphs, self.graphs_proc, self.graphs_guided, self.graphs_json)[mode][pad]
         if mode:
             self.logit_process_launches += k
-        if mode == 2:
+        if mode >= 2:
             self.token_guide_launches += k
             self.byte_guide_launches += k
+        if mode == 3:
+            self.json_guide_launches += k
         if top < 0:
             for _ in range(k):
                 g.replay()
             self.h_tokens[base:base + k].copy_(self.d_tokens[base:base + k], non_blocking=True)
-            if mode == 2:
+            if mode >= 2:
                 self._guide_err_to_host()
             return
-        logits = (self.graph_logits, self.graph_logits_proc, self.graph_logits_guided)[mode][pad]
+        logits = (self.graph_logits, self.graph_logits_proc, self.graph_logits_guided, self.graph_logits_json)[mode][pad]
         for i in range(k):
             g.replay()
             self._launch_logprobs(logits, self.d_out, n, base + i, top)
         self.h_tokens[base:base + k].copy_(self.d_tokens[base:base + k], non_blocking=True)
         self._lp_to_host(base, base + k)
-        if mode == 2:
+        if mode >= 2:
             self._guide_err_to_host()
 
     def _queue_continuation(self, seqs: List[Sequence], pending: int, k: int, base: int) -> None:
@@ -1181,11 +1245,12 @@ class ModelRunner:
         g = self.graphs.get(pad)
         if g is not None:
             if mode:
-                g = (self.graphs_proc, self.graphs_guided)[mode - 1][pad]
+                g = (self.graphs_proc, self.graphs_guided, self.graphs_json)[mode - 1][pad]
                 self.logit_process_launches += 1
-                self.token_guide_launches += mode == 2
-                self.byte_guide_launches += mode == 2
+                self.token_guide_launches += mode >= 2
+                self.byte_guide_launches += mode >= 2
+                self.json_guide_launches += mode == 3
             g.replay()
             return self.d_out
         # eager: a guided step launches ops.logit_process only when a row asks for it
-        return self._decode_forward(n, self._proc if mode == 2 else bool(mode), mode == 2)
+        return self._decode_forward(n, self._proc if mode >= 2 else bool(mode), mode >= 2, mode == 3)

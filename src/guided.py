@@ -1,5 +1,6 @@
 """
 Constrained decoding on the host: three front ends (``allowed_token_ids``, ``guided_choice``, ``guided_regex``)
+and ``guided_json_object`` (the third form below). The first three
 compile to a token automaton in CSR, which ``ops.token_guide`` walks on the device; a ``guided_regex`` over a
 multi-byte vocabulary compiles to the second form below instead.
 
@@ -32,6 +33,27 @@ other than EOS (checked at compile time): then "no dead ends" carries over from 
 ``hf_token_bytes`` derives the byte table of a HuggingFace tokenizer (ByteLevel BPE, or SentencePiece pieces with
 byte fallback).
 
+The third form, ``JsonGuide`` (``guided_json_object``, the gateway's ``response_format: {"type": "json_object"}``):
+JSON nests, so a byte DFA cannot hold it; the guide is a byte PUSHDOWN automaton, ``trans`` int16 [S, 256] whose
+entries carry the next state in bits 0..7 and an action in bits 8..9 (``JSON_ACT_*``: none, push-object, push-array,
+pop), -1 for no transition. The configuration is (state, depth, stack bits): bit d - 1 of the stack word is the kind
+(0 object, 1 array) of the container at depth d, at most GUIDE_JSON_MAX_DEPTH = 32 open at once. The control
+automaton keeps one copy of its value / string / literal / number states per enclosing kind, so the stack is read
+only on a pop: a pop entry's state field names the "after a value in an object" state, directly followed by "after a
+value in an array" and DONE, and the pop lands on the one the new top (or depth 0) selects. ``ops.json_guide`` walks
+every token's bytes through it inside the decode step. The language (``build_json_table``): one object, compact or
+with a single space after ``,`` and ``:``, well-formed UTF-8 strings, then only EOS.
+
+No dead ends, from bytes to tokens: (a) every state but DONE has a byte transition that is legal at every depth —
+a ``{`` or ``[`` at the cap has no transition, but wherever a value may start, ``"``, a digit, ``t`` ... start one too,
+and every other state's transitions do not push; a pop is only reachable with depth >= 1, since the only state at
+depth 0 besides DONE is the start state, which pushes; (b) from every configuration DONE is reachable (close what is
+open: a string by ``"``, a number by its terminator, a literal by its remaining letters, a container by ``}`` /
+``]``, which the per-kind copies make legal exactly in the matching kind); (c) every byte that labels a transition
+must have a single-byte token other than EOS (checked at compile time, the ValueError names the byte), so the byte
+of (a) is a token the device allows; in DONE, EOS is allowed. Hence every configuration a sequence can reach allows
+at least one token, and a finite continuation to DONE then EOS exists.
+
 Pure numpy / Python: imported by ``src.preproc`` for early validation, never touches torch.
 """
 
@@ -50,6 +72,9 @@ GUIDE_MAX_EDGES = 262144           # twice the largest vocabulary
 GUIDE_MAX_CHOICES = 1024
 GUIDE_MAX_CHOICE_TOKENS = 65536
 GUIDE_MAX_TOKEN_BYTES = 32         # ops.byte_guide never allows a longer token (launchers.h)
+GUIDE_JSON_MAX_DEPTH = 32          # containers open at once, the top-level object included (launchers.h)
+GUIDE_JSON_MAX_STATES = 92         # ops.json_guide keeps the whole table in LDS (launchers.h)
+JSON_ACT_NONE, JSON_ACT_PUSH_OBJECT, JSON_ACT_PUSH_ARRAY, JSON_ACT_POP = 0, 1, 2, 3   # bits 8..9 of a trans entry
 _QUANT_MAX = 1024                  # {m,n} bound: larger counts only ever end at the state cap
 
 
@@ -116,9 +141,77 @@ def walk_bytes(guide: ByteGuide, state: int, tokens: Iterable[int],
     return state
 
 
-def walk(automaton, state: int, tokens: Iterable[int]) -> int:
-    """The state after ``tokens`` from ``state``. A token without an edge is a ValueError: the runner rebuilds
+@dataclass(frozen=True, eq=False)
+class JsonGuide:
+    trans: np.ndarray      # int16 [S, 256]: -1, or next state | action << 8 (module docstring); start state 0
+    done: int              # the only accepting state
+    eos: int
+    key: tuple             # the canonical spec; its last element names the byte table (id_of / table_of)
+
+    @property
+    def n_states(self) -> int:
+        return self.trans.shape[0]
+
+    @property
+    def sink(self) -> int:
+        return self.trans.shape[0]
+
+
+def json_step(trans: np.ndarray, config: Tuple[int, int, int], byte: int) -> Optional[Tuple[int, int, int]]:
+    """One byte from (state, depth, stack bits) by the device's rules; None: no transition, or a push at the cap."""
+    s, d, k = config
+    v = int(trans[s, byte])
+    if v < 0:
+        return None
+    nxt, act = v & 0xFF, v >> 8
+    if act == JSON_ACT_PUSH_OBJECT or act == JSON_ACT_PUSH_ARRAY:
+        if d >= GUIDE_JSON_MAX_DEPTH:
+            return None
+        if act == JSON_ACT_PUSH_ARRAY:
+            k |= 1 << d
+        d += 1
+    elif act == JSON_ACT_POP:
+        if d < 1:
+            raise ValueError("the JSON guide pops an empty stack")
+        d -= 1
+        k &= ~(1 << d)
+        nxt += 2 if d == 0 else (k >> (d - 1)) & 1
+    return nxt, d, k
+
+
+def walk_json(guide: JsonGuide, config: Tuple[int, int, int], tokens: Iterable[int],
+              token_bytes: Optional[Sequence[Optional[bytes]]] = None) -> Tuple[int, int, int]:
+    """``walk`` for a JsonGuide over (state, depth, stack bits), by the device's rules
+    (csrc/kernels/json_guide.hip): EOS from DONE or in the sink gives the sink; any other token walks its bytes,
+    pushes and pops applied. A ValueError where the device would report GUIDE_ERR_NO_EDGE."""
+    if token_bytes is None:
+        token_bytes = table_of(guide.key[-1])
+    n = guide.n_states
+    for t in tokens:
+        t = int(t)
+        if t == guide.eos:
+            if config[0] != n and config[0] != guide.done:
+                raise ValueError(f"end of sequence in guide state {config[0]}, which does not accept")
+            config = (n, config[1], config[2])
+            continue
+        bs = token_bytes[t] if 0 <= t < len(token_bytes) else None
+        if config[0] == n or not bs or len(bs) > GUIDE_MAX_TOKEN_BYTES:
+            raise ValueError(f"token {t} has no edge in guide state {config[0]}")
+        c = config
+        for b in bs:
+            c = json_step(guide.trans, c, b)
+            if c is None:
+                raise ValueError(f"token {t} has no edge in guide state {config[0]}")
+        config = c
+    return config
+
+
+def walk(automaton, state, tokens: Iterable[int]):
+    """The state after ``tokens`` from ``state`` (a JsonGuide: the configuration (state, depth, stack bits); start
+    state 0 stands for (0, 0, 0)). A token without an edge is a ValueError: the runner rebuilds
     device state from tokens the automaton itself allowed, so this never happens to a healthy sequence."""
+    if isinstance(automaton, JsonGuide):
+        return walk_json(automaton, (0, 0, 0) if isinstance(state, int) and state == 0 else state, tokens)
     if isinstance(automaton, ByteGuide):
         return walk_bytes(automaton, state, tokens)
     for t in tokens:
@@ -665,6 +758,146 @@ def compile_byte_guide(pattern: str, token_bytes: Sequence[Optional[bytes]], eos
                      int(eos), ("regex", pattern, int(eos), id_of(token_bytes)))
 
 
+# ------------------------------------------------------------------ guided_json_object: the pushdown table
+def build_json_table() -> Tuple[np.ndarray, int]:
+    """(trans int16 [S, 256], DONE) of the JSON-object pushdown automaton described in the module docstring; start
+    state 0. Value, string, literal and number states exist once per enclosing kind ("o": in an object, "a": in an
+    array); the key string is a third copy. States after_o, after_a and DONE are consecutive: a pop lands on
+    after_o + (0: the new top is an object, 1: an array, 2: depth 0)."""
+    names: List[str] = []
+    rows: List[List[int]] = []
+
+    def st(name: str) -> int:
+        names.append(name)
+        rows.append([-1] * 256)
+        return len(rows) - 1
+
+    def edge(a: int, bs, b: int, act: int = JSON_ACT_NONE) -> None:
+        for x in (bs if not isinstance(bs, int) else [bs]):
+            x = x if isinstance(x, int) else ord(x)
+            assert rows[a][x] == -1, (names[a], x)
+            rows[a][x] = b | (act << 8)
+
+    start = st("start")
+    after = {"o": st("after_o"), "a": st("after_a")}
+    done = st("done")
+    assert (after["o"], after["a"], done) == (1, 2, 3)
+    obj_open, key_end, colon, colon_sp = st("obj_open"), st("key_end"), st("colon"), st("colon_sp")
+    comma_o, comma_o_sp = st("comma_o"), st("comma_o_sp")
+    arr_open, comma_a, comma_a_sp = st("arr_open"), st("comma_a"), st("comma_a_sp")
+    hexd = "0123456789abcdefABCDEF"
+
+    def string(tag: str, end: int) -> int:
+        """The states of a string whose opening quote was read; `end` follows the closing one. Returns the body."""
+        body, esc = st("str_" + tag), st("esc_" + tag)
+        u = [st(f"u{i}_{tag}") for i in range(4)]
+        c1, c2, c3 = st("c1_" + tag), st("c2_" + tag), st("c3_" + tag)   # 1, 2, 3 continuation bytes to go
+        e0, ed, f0, f4 = st("e0_" + tag), st("ed_" + tag), st("f0_" + tag), st("f4_" + tag)
+        edge(body, [b for b in range(0x20, 0x80) if b not in (0x22, 0x5C)], body)
+        edge(body, '"', end)
+        edge(body, "\\", esc)
+        edge(esc, '"\\/bfnrt', body)
+        edge(esc, "u", u[0])
+        for i in range(4):
+            edge(u[i], hexd, u[i + 1] if i < 3 else body)
+        cont = range(0x80, 0xC0)
+        edge(body, range(0xC2, 0xE0), c1)                       # C0, C1: overlong
+        edge(body, 0xE0, e0)
+        edge(body, [b for b in range(0xE1, 0xF0) if b != 0xED], c2)
+        edge(body, 0xED, ed)
+        edge(body, 0xF0, f0)
+        edge(body, range(0xF1, 0xF4), c3)
+        edge(body, 0xF4, f4)                                    # F5..: above U+10FFFF
+        edge(c1, cont, body)
+        edge(c2, cont, c1)
+        edge(c3, cont, c2)
+        edge(e0, range(0xA0, 0xC0), c1)                         # E0 80..9F: overlong
+        edge(ed, range(0x80, 0xA0), c1)                         # ED A0..BF: surrogates
+        edge(f0, range(0x90, 0xC0), c2)                         # F0 80..8F: overlong
+        edge(f4, range(0x80, 0x90), c2)                         # F4 90..: above U+10FFFF
+        return body
+
+    key = string("k", key_end)
+    edge(start, "{", obj_open, JSON_ACT_PUSH_OBJECT)
+    edge(obj_open, '"', key)
+    edge(obj_open, "}", after["o"], JSON_ACT_POP)
+    edge(key_end, ":", colon)
+    edge(colon, " ", colon_sp)
+    edge(after["o"], ",", comma_o)
+    edge(after["o"], "}", after["o"], JSON_ACT_POP)
+    edge(comma_o, " ", comma_o_sp)
+    edge(comma_o, '"', key)
+    edge(comma_o_sp, '"', key)
+    edge(arr_open, "]", after["o"], JSON_ACT_POP)
+    edge(after["a"], ",", comma_a)
+    edge(after["a"], "]", after["o"], JSON_ACT_POP)
+    edge(comma_a, " ", comma_a_sp)
+    digits = "0123456789"
+    for kind, value_starts in (("o", (colon, colon_sp)), ("a", (arr_open, comma_a, comma_a_sp))):
+        aft = after[kind]
+        sbody = string(kind, aft)
+        lits = {}
+        for word in ("true", "false", "null"):
+            prev = None
+            for i in range(1, len(word)):
+                cur_ = st(f"{word[:i]}_{kind}")
+                if prev is None:
+                    lits[word] = cur_
+                else:
+                    edge(prev, word[i - 1], cur_)
+                prev = cur_
+            edge(prev, word[-1], aft)
+        minus, zero, int_, dot = st("minus_" + kind), st("zero_" + kind), st("int_" + kind), st("dot_" + kind)
+        frac, e_, esign, exp = st("frac_" + kind), st("e_" + kind), st("esign_" + kind), st("exp_" + kind)
+        edge(minus, "0", zero)
+        edge(minus, "123456789", int_)
+        edge(int_, digits, int_)
+        for s_ in (zero, int_):
+            edge(s_, ".", dot)
+        edge(dot, digits, frac)
+        edge(frac, digits, frac)
+        for s_ in (zero, int_, frac):
+            edge(s_, "eE", e_)
+        edge(e_, "+-", esign)
+        edge(e_, digits, exp)
+        edge(esign, digits, exp)
+        edge(exp, digits, exp)
+        for s_ in (zero, int_, frac, exp):      # a number's terminators act as they do after a value
+            for b in range(256):
+                if rows[aft][b] != -1:
+                    edge(s_, b, rows[aft][b] & 0xFF, rows[aft][b] >> 8)
+        for v in value_starts:
+            edge(v, "{", obj_open, JSON_ACT_PUSH_OBJECT)
+            edge(v, "[", arr_open, JSON_ACT_PUSH_ARRAY)
+            edge(v, '"', sbody)
+            edge(v, "-", minus)
+            edge(v, "0", zero)
+            edge(v, "123456789", int_)
+            for word in ("true", "false", "null"):
+                edge(v, word[0], lits[word])
+    assert len(rows) <= GUIDE_JSON_MAX_STATES
+    return np.asarray(rows, dtype=np.int16), done
+
+
+_JSON_TABLE: Optional[Tuple[np.ndarray, int]] = None
+
+
+def compile_json_guide(token_bytes: Sequence[Optional[bytes]], eos: int, vocab: Optional[int] = None) -> JsonGuide:
+    """The JsonGuide of ``guided_json_object`` on a byte table: the fixed table and compile_byte_guide's soundness
+    check (ValueError naming a byte on a transition that no single-byte token other than EOS spells)."""
+    global _JSON_TABLE
+    if _JSON_TABLE is None:
+        _JSON_TABLE = build_json_table()
+    trans, done = _JSON_TABLE
+    vocab = len(token_bytes) if vocab is None else min(vocab, len(token_bytes))
+    _, single = _table_facts(token_bytes, eos, vocab)
+    for b in np.nonzero((trans >= 0).any(axis=0))[0]:
+        if int(b) not in single:
+            raise ValueError(f"guided_json_object needs byte 0x{int(b):02X}, which is not supported on this tokenizer: "
+                             "no single-byte token spells it")
+    return JsonGuide(trans, done, int(eos), ("json_object", int(eos), id_of(token_bytes)))
+
+
 # ------------------------------------------------------------------ byte tables of HuggingFace tokenizers
 def _bytelevel_alphabet() -> Dict[str, int]:
     """The inverse of GPT-2's bytes-to-unicode map: printable Latin-1 stands for itself, the other 68 bytes for
@@ -733,16 +966,23 @@ _LOCK = threading.Lock()
 
 def compile_guide(sampling, vocab: int, eos: Optional[int], token_bytes: Optional[Sequence[Optional[bytes]]] = None):
     """The automaton of a request's guide (SamplingParams.guided is true), from a small LRU keyed by the
-    canonical spec: an Automaton, or a ByteGuide for a guided_regex over a multi-byte vocabulary. ValueError for everything the engine must refuse."""
+    canonical spec: an Automaton, a ByteGuide for a guided_regex over a multi-byte vocabulary, or a JsonGuide for
+    guided_json_object. ValueError for everything the engine must refuse."""
     if sampling.allowed_token_ids is not None:
         spec = ("allowed", tuple(sorted(sampling.allowed_token_ids)), vocab)
     else:
         if eos is None:
-            raise ValueError("guided_choice / guided_regex are not supported on an engine without an "
-                             "end-of-sequence token")
+            raise ValueError("guided_choice / guided_regex / guided_json_object are not supported on an engine "
+                             "without an end-of-sequence token")
         if sampling.ignore_eos:
-            raise ValueError("guided_choice / guided_regex cannot be combined with ignore_eos")
-        if sampling.guided_choice is not None:
+            raise ValueError("guided_choice / guided_regex / guided_json_object cannot be combined with ignore_eos")
+        if getattr(sampling, "guided_json_object", False):
+            if token_bytes is None:
+                raise ValueError("guided_json_object is not supported on an engine without a byte table of its "
+                                 "tokenizer (the byte-level tokenizer, ByteLevel BPE and byte-fallback "
+                                 "vocabularies provide one)")
+            spec = ("json_object", vocab, eos, id_of(token_bytes))
+        elif sampling.guided_choice is not None:
             spec = ("choice", tuple(sorted(set(tuple(c) for c in sampling.guided_choice))), vocab, eos)
         else:
             if token_bytes is None:
@@ -759,12 +999,16 @@ def compile_guide(sampling, vocab: int, eos: Optional[int], token_bytes: Optiona
         a = compile_allowed(spec[1], vocab)
     elif spec[0] == "choice":
         a = compile_choice(spec[1], eos, vocab)
+    elif spec[0] == "json_object":
+        a = compile_json_guide(token_bytes, eos, vocab)
     elif _table_facts(token_bytes, eos, min(vocab, len(token_bytes)))[0]:
         # a multi-byte vocabulary: the byte DFA itself, walked per token on the device (ops.byte_guide)
         a = compile_byte_guide(spec[1], token_bytes, eos, vocab)
     else:
         a = compile_regex(spec[1], token_bytes, eos, vocab)
-    if isinstance(a, ByteGuide):
+    if isinstance(a, JsonGuide):
+        a = JsonGuide(a.trans, a.done, a.eos, spec)
+    elif isinstance(a, ByteGuide):
         a = ByteGuide(a.trans, a.accept, a.eos, spec)
     else:
         a = Automaton(a.row_ptr, a.edge_tok, a.edge_next, spec)

@@ -10,7 +10,8 @@ coordinator's framed-RPC API. It holds no model state — every request becomes 
                             "logprobs": 0..20, "echo", "presence_penalty", "frequency_penalty" (-2..2),
                             "repetition_penalty" (> 0), "logit_bias": {token id: -100..100}, <= 300 entries,
                             at most one of "allowed_token_ids": [ids], "guided_choice": [str | [ids]],
-                            "guided_regex": str}
+                            "guided_regex": str, "response_format": {"type": "json_object"} (or
+                            "guided_json_object": true)}
                            stream=true answers with server-sent events ("data: {...}" chunks,
                            then "data: [DONE]"), text and token ids per chunk.
                            logprobs=N: choice.logprobs = {"tokens", "token_logprobs", "top_logprobs":
@@ -36,6 +37,13 @@ coordinator's framed-RPC API. It holds no model state — every request becomes 
     three at once, unsupported regex syntax, ignore_eos with a choice or a pattern, or any of them on a model
     served tensor-parallel is a 400; so is guided_regex with a tokenizer whose layout is not recognised, or with a
     pattern that needs a byte no single-byte token of the vocabulary spells.
+    JSON mode (both endpoints): response_format {"type": "json_object"}, or the plain field guided_json_object:
+    true, constrains the output to one JSON object (compact, or with a single space after ',' and ':'; at most 32
+    containers deep) followed by EOS: a byte pushdown automaton walked over every token's bytes on the GPU. A
+    request cut off by max_tokens returns an incomplete document with finish_reason "length", as OpenAI documents.
+    {"type": "text"} does nothing. Any other type (json_schema included) is a 400 naming it; so are a malformed
+    response_format, json_object next to allowed_token_ids / guided_choice / guided_regex or with ignore_eos, and
+    JSON mode on a model served tensor-parallel or with a tokenizer that has no byte table.
     POST /v1/embeddings    {"model", "input": str | [str] | [token ids] | [[token ids]] (<= 2048 items),
                             "encoding_format": "float" | "base64", "dimensions": multiple of 8,
                             "pooling": "last" | "mean", "normalize": bool}
@@ -72,7 +80,7 @@ from src.preproc import SamplingParams
 from src.utils import setup_logging
 
 _LOGIT_PROCESSING = ("presence_penalty", "frequency_penalty", "repetition_penalty", "logit_bias")
-_GUIDED = ("allowed_token_ids", "guided_choice", "guided_regex")
+_GUIDED = ("allowed_token_ids", "guided_choice", "guided_regex", "guided_json_object")
 _SAMPLING = ("max_tokens", "temperature", "top_p", "top_k", "seed", "stop_token_ids", "ignore_eos") + \
     _LOGIT_PROCESSING + _GUIDED
 _ROLES = ("system", "user", "assistant", "tool")
@@ -189,6 +197,14 @@ class Gateway:
             raise ValueError("prompt must be a string or a list of token ids")
         inp.update({k: body[k] for k in _SAMPLING if k in body and body[k] is not None})
         inp.setdefault("max_tokens", 16)
+        fmt = body.get("response_format")
+        if fmt is not None:  # OpenAI's JSON mode; "text" is the default and does nothing
+            if not isinstance(fmt, dict) or not isinstance(fmt.get("type"), str):
+                raise ValueError('response_format must be an object {"type": "text" | "json_object"}')
+            if fmt["type"] == "json_object":
+                inp["guided_json_object"] = True
+            elif fmt["type"] != "text":
+                raise ValueError(f"response_format type {fmt['type']!r} is not supported (text, json_object)")
         # ranges and types of the penalties / bias: refused here with a 400, not by a worker after routing
         SamplingParams(**{k: inp[k] for k in _LOGIT_PROCESSING if k in inp})
         # the same for constrained decoding (shapes, "at most one", the regex subset, ignore_eos); a text choice

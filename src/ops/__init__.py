@@ -336,6 +336,31 @@ def byte_guide(logits: torch.Tensor, slot: torch.Tensor, desc: torch.Tensor, tra
     return logits
 
 
+# JSON mode (launchers.h)
+GUIDE_JSON_MAX_DEPTH = ref.GUIDE_JSON_MAX_DEPTH    # containers open at once: the stack is one 32-bit word
+GUIDE_JSON_MAX_STATES = ref.GUIDE_JSON_MAX_STATES  # the pushdown table is always walked from LDS
+
+
+def json_guide(logits: torch.Tensor, slot: torch.Tensor, desc: torch.Tensor, trans: torch.Tensor,
+               tok_off: torch.Tensor, tok_bytes: torch.Tensor, cur: torch.Tensor, jstk: torch.Tensor,
+               err: torch.Tensor, advance_ids: Optional[torch.Tensor] = None,
+               lm_part: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """JSON mode on ``logits`` [rows, vocab] bf16 IN PLACE: every token whose BYTES the byte pushdown automaton
+    ``trans`` int16 [S, 256] cannot read from the row's configuration becomes ``-inf``, an allowed entry keeps its
+    exact bits (:func:`reference.json_guide_rows` is the contract). An entry of ``trans`` is -1 or next state |
+    action << 8 (0 none, 1 push-object, 2 push-array, 3 pop; a pop lands on its state field + 0 / 1 / 2 for an
+    object on top / an array / depth 0). Row r uses ``slot[r]`` (int32; < 0: the row is left untouched): ``desc``
+    int32 [slots, 4] = (n_states, done, eos, 0), the configuration is ``cur[slot]`` (``n_states``: the sink, entered
+    by EOS from ``done``) with ``jstk`` int32 [slots, 2] = (depth, stack bits). ``tok_off`` / ``tok_bytes``,
+    ``cur`` / ``err``, ``advance_ids`` and ``lm_part`` as in :func:`byte_guide` (the same arrays: a slot belongs to
+    one of the three ops)."""
+    if not logits.is_cuda:
+        return ref.json_guide_rows(logits, slot, desc, trans, tok_off, tok_bytes, cur, jstk, err, advance_ids,
+                                   lm_part)
+    _kern().json_guide(logits, slot, desc, trans, tok_off, tok_bytes, cur, jstk, err, advance_ids, lm_part)
+    return logits
+
+
 # embedding pooling (launchers.h): a segment descriptor's flag bits, and the row split of long mean segments
 POOL_MEAN, POOL_FIRST, POOL_FINAL = 1, 2, 4
 POOL_MAX_PARTS = 64    # workgroups per segment

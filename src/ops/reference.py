@@ -386,6 +386,131 @@ def byte_guide_rows(logits, slot, desc, trans, accept, tok_off, tok_bytes, cur, 
     return logits
 
 
+GUIDE_JSON_MAX_DEPTH = 32   # json_guide: containers open at once
+GUIDE_JSON_MAX_STATES = 92  # json_guide: states of the pushdown table
+
+
+def json_guide_rows(logits, slot, desc, trans, tok_off, tok_bytes, cur, jstk, err, advance_ids=None, lm_part=None):
+    """ops.json_guide on host tensors (the contract of csrc/kernels/json_guide.hip): row r -> slot[r] -> desc
+    (n_states, done, eos, 0); trans int16 [S, 256] holds -1 or next state | action << 8 (1 push-object, 2
+    push-array, 3 pop: the landing state is the field + 0 / 1 / 2 for an object on top / an array / depth 0). The
+    configuration (cur, jstk = (depth, stack bits)) advances over advance_ids[r] first (EOS from done or the sink:
+    the sink; a token whose walk dies or pushes at the cap, without bytes, over the length cap, beyond the table,
+    or any token but EOS in the sink: err |= 1, configuration kept). Allowed next: in the sink EOS alone; else EOS
+    iff the state is done, and every token of 1..32 bytes whose walk never dies. Barred entries become -inf, the
+    others keep their bits; lm_part candidates are overwritten with the best allowed entry. Anything out of bounds
+    (any entry of the table's first n_states rows, a pop at depth 0): err |= 2 and row, candidates and configuration stay untouched."""
+    import numpy as np
+
+    vocab = logits.shape[1]
+    tr = trans.numpy()
+    off, by = tok_off.numpy().astype(np.int64), tok_bytes.numpy()
+    n_tok, blen = len(off) - 1, len(by)
+    lim = min(vocab, n_tok)
+    cap = GUIDE_JSON_MAX_DEPTH
+
+    def step(ns, st, dp, kb, b):
+        """The chains (int64 arrays) over bytes b: (states or -1, depths, bits, a value was out of bounds)."""
+        v = tr[st, b].astype(np.int64)
+        none = v == -1
+        nxt, act = v & 0xFF, (v >> 8) & 3
+        push, pop = (act == 1) | (act == 2), act == 3
+        oob = ~none & ((v < 0) | (v >= 1024) | (nxt + np.where(pop, 2, 0) >= ns) | (pop & (dp < 1)))
+        dead = none | oob | (push & (dp >= cap))
+        dpop = dp - 1
+        k_push = kb | (np.where(act == 2, 1, 0) << np.minimum(dp, 31))
+        k_pop = kb & ~(np.int64(1) << np.maximum(dpop, 0))
+        top = np.where(dpop <= 0, 2, (k_pop >> np.maximum(dpop - 1, 0)) & 1)
+        s_new = np.where(pop, nxt + top, nxt)
+        kb = np.where(dead, kb, np.where(push, k_push, np.where(pop, k_pop, kb)))
+        dp = np.where(dead, dp, np.where(push, dp + 1, np.where(pop, dpop, dp)))
+        return np.where(dead, -1, s_new), dp, kb, bool(oob.any())
+
+    for r in range(logits.shape[0]):
+        s = int(slot[r])
+        if s < 0 or s >= desc.shape[0]:
+            continue
+        ns, done, eos = (int(v) for v in desc[s, :3])
+        c, d, k = int(cur[s]), int(jstk[s, 0]), int(jstk[s, 1]) & 0xFFFFFFFF
+        if (ns < 3 or ns > tr.shape[0] or ns > GUIDE_JSON_MAX_STATES or not 0 <= done < ns or not 0 <= c <= ns
+                or not 0 <= d <= cap or (k >> d) != 0 or not 0 <= eos < vocab):
+            err[s] |= GUIDE_ERR_TABLE
+            continue
+        t = tr[:ns].astype(np.int64)  # the whole table is validated at every launch
+        if ((t != -1) & ((t < 0) | (t >= 1024) | ((t & 0xFF) + np.where(t >> 8 == 3, 2, 0) >= ns))).any():
+            err[s] |= GUIDE_ERR_TABLE
+            continue
+        flags, bad = 0, False
+        if advance_ids is not None:
+            tok = int(advance_ids[r])
+            if tok == eos:
+                if c == ns or c == done:
+                    c = ns
+                else:
+                    flags = GUIDE_ERR_NO_EDGE
+            elif c == ns or not 0 <= tok < lim:
+                flags = GUIDE_ERR_NO_EDGE
+            else:
+                lo, hi = int(off[tok]), int(off[tok + 1])
+                if not 0 <= lo <= hi <= blen:
+                    bad = True
+                elif hi == lo or hi - lo > GUIDE_MAX_TOKEN_BYTES:
+                    flags = GUIDE_ERR_NO_EDGE
+                else:
+                    st, dp, kb = np.array([c]), np.array([d]), np.array([k])
+                    for p in range(lo, hi):
+                        st, dp, kb, oob = step(ns, st, dp, kb, by[p:p + 1])
+                        bad = bad or oob
+                        if st[0] < 0:
+                            break
+                    if bad:
+                        pass
+                    elif st[0] < 0:
+                        flags = GUIDE_ERR_NO_EDGE
+                    else:
+                        c, d, k = int(st[0]), int(dp[0]), int(kb[0])
+        allowed = np.zeros(vocab, dtype=bool)
+        if not bad and c < ns:
+            lo, hi = off[:lim], off[1:lim + 1]
+            bad = bool(((lo < 0) | (hi < lo) | (hi > blen)).any())
+            if not bad:
+                ln = hi - lo
+                st = np.where((ln >= 1) & (ln <= GUIDE_MAX_TOKEN_BYTES), c, -1).astype(np.int64)
+                dp, kb = np.full(lim, d, dtype=np.int64), np.full(lim, k, dtype=np.int64)
+                for level in range(GUIDE_MAX_TOKEN_BYTES):
+                    idx = np.nonzero((st >= 0) & (level < ln))[0]
+                    if not len(idx):
+                        break
+                    st[idx], dp[idx], kb[idx], oob = step(ns, st[idx], dp[idx], kb[idx], by[lo[idx] + level])
+                    bad = bad or oob
+                allowed[:lim] = st >= 0
+                allowed[eos] = c == done
+        elif not bad:
+            allowed[eos] = True
+        if bad:
+            err[s] |= GUIDE_ERR_TABLE
+            continue
+        cur[s] = c
+        jstk[s, 0] = d
+        jstk[s, 1] = k - (1 << 32) if k >= 1 << 31 else k
+        err[s] |= flags
+        allowed = torch.from_numpy(allowed)
+        logits[r, :vocab] = torch.where(allowed, logits[r, :vocab],
+                                        torch.tensor(float("-inf"), dtype=logits.dtype))
+        if lm_part is not None:
+            x = logits[r, :vocab].float()
+            ok = allowed & ~torch.isnan(x)  # a NaN never wins a comparison (sampling.hip's better())
+            x = torch.where(ok, x, torch.tensor(float("-inf")))
+            v = x.max()
+            first = ((x == v) & ok).nonzero()  # lowest allowed index holding the maximum
+            lm_part[r, :, 0] = torch.tensor(float("-inf")).view(torch.int32)
+            lm_part[r, :, 1] = 0x7fffffff
+            if first.numel():
+                lm_part[r, 0, 0] = x[int(first[0])].view(torch.int32)  # that entry's own bits (-0.0 equals +0.0)
+                lm_part[r, 0, 1] = int(first[0])
+    return logits
+
+
 POOL_MEAN, POOL_FIRST, POOL_FINAL = 1, 2, 4  # flag bits of a pool_embed segment descriptor
 
 

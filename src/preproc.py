@@ -102,6 +102,10 @@ class SamplingParams:
     allowed_token_ids: Optional[List[int]] = None
     guided_choice: Optional[List[List[int]]] = None
     guided_regex: Optional[str] = None
+    # JSON mode (the gateway's response_format {"type": "json_object"}): the output is one JSON object, compact or
+    # with a single space after ',' and ':', then EOS (src/guided.py: a byte pushdown automaton that ops.json_guide
+    # walks on the device). One of the "at most one" fields above.
+    guided_json_object: bool = False
     # embeddings: with pooling set the request generates nothing. It ends when its prompt does, and its result is
     # the pooled final-norm hidden state of the prompt (ops.pool_embed): "last" = the last prompt token's row,
     # "mean" = the mean over all prompt rows; cut to its first embed_dimensions components (None: all; a multiple
@@ -174,11 +178,16 @@ class SamplingParams:
         if self.processes_logits:
             raise ValueError("pooling cannot be combined with penalties or logit_bias")
         if self.guided:
-            raise ValueError("pooling cannot be combined with allowed_token_ids / guided_choice / guided_regex")
+            raise ValueError("pooling cannot be combined with allowed_token_ids / guided_choice / guided_regex / "
+                             "guided_json_object")
 
     def _check_guided(self) -> None:
-        if sum(v is not None for v in (self.allowed_token_ids, self.guided_choice, self.guided_regex)) > 1:
-            raise ValueError("at most one of allowed_token_ids, guided_choice and guided_regex may be set")
+        if not isinstance(self.guided_json_object, bool):
+            raise ValueError("guided_json_object must be a boolean")
+        if sum(v is not None for v in (self.allowed_token_ids, self.guided_choice, self.guided_regex)) + \
+                self.guided_json_object > 1:
+            raise ValueError("at most one of allowed_token_ids, guided_choice, guided_regex and guided_json_object "
+                             "may be set")
 
         def ids_of(v, name):
             if not isinstance(v, (list, tuple)) or not v:
@@ -213,6 +222,8 @@ class SamplingParams:
             parse_regex(self.guided_regex)  # ValueError naming the position for anything outside the subset
         if self.ignore_eos and (self.guided_choice is not None or self.guided_regex is not None):
             raise ValueError("guided_choice / guided_regex cannot be combined with ignore_eos")
+        if self.ignore_eos and self.guided_json_object:
+            raise ValueError("guided_json_object cannot be combined with ignore_eos")
 
     @property
     def greedy(self) -> bool:
@@ -227,7 +238,8 @@ class SamplingParams:
     @property
     def guided(self) -> bool:
         """Constrained decoding asked for: the request's rows go through ops.token_guide before sampling."""
-        return self.allowed_token_ids is not None or self.guided_choice is not None or self.guided_regex is not None
+        return (self.allowed_token_ids is not None or self.guided_choice is not None or self.guided_regex is not None
+                or self.guided_json_object)
 
 
 @dataclass
@@ -240,8 +252,8 @@ class GenerationInputs:
 
 _SAMPLING_KEYS = ("max_tokens", "temperature", "top_k", "top_p", "seed", "ignore_eos", "stop_token_ids",
                   "logprobs", "prompt_logprobs", "presence_penalty", "frequency_penalty", "repetition_penalty",
-                  "logit_bias", "allowed_token_ids", "guided_choice", "guided_regex", "pooling", "embed_normalize",
-                  "embed_dimensions")
+                  "logit_bias", "allowed_token_ids", "guided_choice", "guided_regex", "guided_json_object", "pooling",
+                  "embed_normalize", "embed_dimensions")
 
 
 def normalize_request(inputs: Any, tokenizer=None, max_model_len: Optional[int] = None) -> GenerationInputs:
