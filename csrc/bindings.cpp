@@ -567,6 +567,64 @@ void json_guide(Tensor logits, Tensor slot, Tensor desc, Tensor trans, Tensor to
                                  lp, lparts, cur_stream()));
 }
 
+// Structured outputs on logits [rows, vocab] in place (schema_guide.hip). slot int32 [>= rows]; desc int32 [slots, 4]
+// = (state_base, n_states, eos, 0); trans int32 [A, 256] and accept uint8 [A], the pushdown arenas; tok_off / tok_bytes:
+// byte_guide's tables; cur / err int32 [slots] (token_guide's); sdep int32 [slots] and sstk int16 [slots, 32], the
+// depth and the return states; advance_ids and lm_part optional. The launcher itself refuses vocab % 8 != 0, a bad
+// stride, null tables and an oversized arena.
+void schema_guide(Tensor logits, Tensor slot, Tensor desc, Tensor trans, Tensor accept, Tensor tok_off,
+                  Tensor tok_bytes, Tensor cur, Tensor sdep, Tensor sstk, Tensor err,
+                  c10::optional<Tensor> advance_ids, c10::optional<Tensor> lm_part) {
+  CHK_CUDA(logits);
+  CHK_BF16(logits);
+  check_rows(logits, "logits");
+  const int64_t rows = logits.size(0), vocab = logits.size(1);
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0, "schema_guide: logits must be 16-B aligned");
+  TORCH_CHECK(slot.is_cuda() && slot.scalar_type() == at::kInt && slot.is_contiguous() && slot.numel() >= rows,
+              "schema_guide: slot int32 [rows]");
+  TORCH_CHECK(desc.is_cuda() && desc.scalar_type() == at::kInt && desc.is_contiguous() && desc.dim() == 2 &&
+                  desc.size(1) == 4 && reinterpret_cast<uintptr_t>(desc.data_ptr()) % 16 == 0,
+              "schema_guide: desc int32 [slots, 4]");
+  const int64_t slots = desc.size(0);
+  TORCH_CHECK(trans.is_cuda() && trans.scalar_type() == at::kInt && trans.is_contiguous() && trans.dim() == 2 &&
+                  trans.size(1) == 256, "schema_guide: trans int32 [A, 256]");
+  TORCH_CHECK(accept.is_cuda() && accept.scalar_type() == at::kByte && accept.is_contiguous() && accept.dim() == 1,
+              "schema_guide: accept uint8 [A]");
+  TORCH_CHECK(tok_off.is_cuda() && tok_off.scalar_type() == at::kInt && tok_off.is_contiguous() && tok_off.dim() == 1,
+              "schema_guide: tok_off int32 [n_tok + 1]");
+  TORCH_CHECK(tok_bytes.is_cuda() && tok_bytes.scalar_type() == at::kByte && tok_bytes.is_contiguous() &&
+                  tok_bytes.dim() == 1, "schema_guide: tok_bytes uint8 [B]");
+  TORCH_CHECK(cur.is_cuda() && cur.scalar_type() == at::kInt && cur.is_contiguous() && cur.numel() >= slots &&
+                  err.is_cuda() && err.scalar_type() == at::kInt && err.is_contiguous() && err.numel() >= slots,
+              "schema_guide: cur / err int32 [slots]");
+  TORCH_CHECK(sdep.is_cuda() && sdep.scalar_type() == at::kInt && sdep.is_contiguous() && sdep.numel() >= slots,
+              "schema_guide: sdep int32 [slots]");
+  TORCH_CHECK(sstk.is_cuda() && sstk.scalar_type() == at::kShort && sstk.is_contiguous() && sstk.dim() == 2 &&
+                  sstk.size(0) >= slots && sstk.size(1) == die::GUIDE_SCHEMA_MAX_DEPTH,
+              "schema_guide: sstk int16 [slots, 32]");
+  const int64_t* ap = nullptr;
+  if (advance_ids.has_value()) {
+    TORCH_CHECK(advance_ids->is_cuda() && advance_ids->scalar_type() == at::kLong && advance_ids->is_contiguous() &&
+                    advance_ids->numel() >= rows, "schema_guide: advance_ids int64 [rows]");
+    ap = advance_ids->data_ptr<int64_t>();
+  }
+  uint32_t* lp = nullptr;
+  int lparts = 0;
+  if (lm_part.has_value()) {
+    TORCH_CHECK(lm_part->is_cuda() && lm_part->scalar_type() == at::kInt && lm_part->dim() == 3 &&
+                    lm_part->size(0) >= rows && lm_part->size(2) == 2 && lm_part->is_contiguous(),
+                "schema_guide: lm_part [rows, parts, 2] int32");
+    lp = reinterpret_cast<uint32_t*>(lm_part->data_ptr<int>());
+    lparts = (int)lm_part->size(1);
+  }
+  HIP_OK(die::launch_schema_guide(bf(logits), logits.stride(0), (int)rows, (int)vocab, slot.data_ptr<int>(),
+                                   (int)slots, desc.data_ptr<int>(), trans.data_ptr<int>(), trans.size(0),
+                                   accept.data_ptr<uint8_t>(), accept.numel(), tok_off.data_ptr<int>(),
+                                   tok_off.numel() - 1, tok_bytes.data_ptr<uint8_t>(), tok_bytes.numel(),
+                                   cur.data_ptr<int>(), sdep.data_ptr<int>(), sstk.data_ptr<int16_t>(),
+                                   err.data_ptr<int>(), ap, lp, lparts, cur_stream()));
+}
+
 // Embedding pooling (pooling.hip): hidden bf16 [T, H] (row stride allowed); segs int32 [S, 8]; acc fp32 [slots, H]
 // (optional: only mean pooling reads or writes it); out fp32 [S, H]; part fp32 [P, H] and tickets int32 [>= S]
 // (optional, both or neither: the scratch of segments split over max_parts > 1 workgroups). The launcher itself
@@ -1305,6 +1363,7 @@ PYBIND11_MODULE(_C, m) {
   m.def("token_guide", &token_guide);
   m.def("byte_guide", &byte_guide);
   m.def("json_guide", &json_guide);
+  m.def("schema_guide", &schema_guide);
   m.def("pool_embed", &pool_embed);
   m.def("sample_advance", &sample_advance);
   m.def("move_blocks", &move_blocks);

@@ -168,6 +168,22 @@ hipError_t launch_json_guide(bf16_t* logits, int64_t stride, int rows, int vocab
                              int64_t n_tok, const uint8_t* tok_bytes, int64_t bytes_len, int* cur, int* jstk, int* err,
                              const int64_t* advance_ids, uint32_t* lm_part, int lm_parts, hipStream_t s);
 
+// structured outputs (schema_guide.hip): as launch_byte_guide, but the slot's guide is a byte PUSHDOWN automaton with a
+// stack of return states, desc [num_slots, 4] = (state_base, n_states, eos, 0) into the arenas trans int32
+// [trans_states, 256] (-1, or next state | return state << 14 | action << 28: 0 none, 1 push, 2 pop) and accept uint8
+// [accept_len]; a slot's configuration is cur[slot] with sdep int32 [num_slots] (the depth) and sstk int16
+// [num_slots, GUIDE_SCHEMA_MAX_DEPTH] (the return states, the oldest first). tok_off / tok_bytes are byte_guide's
+// tables, cur / err token_guide's arrays. hipErrorInvalidValue for what launch_byte_guide refuses and an arena above
+// GUIDE_SCHEMA_STATE_ARENA.
+constexpr int GUIDE_SCHEMA_MAX_DEPTH = 32;         // return states live at once
+constexpr int GUIDE_SCHEMA_TOKEN_PUSHES = 4;       // a token's own not-yet-popped pushes: one 64-bit register per chain
+constexpr int GUIDE_SCHEMA_STATE_ARENA = 16384;    // states: trans 16 MiB, accept 16 KiB
+hipError_t launch_schema_guide(bf16_t* logits, int64_t stride, int rows, int vocab, const int* slot, int num_slots,
+                               const int* desc, const int* trans, int64_t trans_states, const uint8_t* accept,
+                               int64_t accept_len, const int* tok_off, int64_t n_tok, const uint8_t* tok_bytes,
+                               int64_t bytes_len, int* cur, int* sdep, int16_t* sstk, int* err,
+                               const int64_t* advance_ids, uint32_t* lm_part, int lm_parts, hipStream_t s);
+
 // embedding pooling of a prefill step's final-norm rows (pooling.hip): hidden bf16 [T, stride >= H]; segs int32
 // [num_segs, 8] = (first row, rows, acc slot, total prompt length, flags, part base, parts, 0); acc fp32 [slots, H]
 // (mean pooling's partial sums across chunks); out fp32 [num_segs, H], of which a FINAL (or last-pooling) segment

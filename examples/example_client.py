@@ -10,6 +10,8 @@
     python examples/example_client.py --model llama --prompt "Is water wet? " --guided-choice yes no
     python examples/example_client.py --model llama --prompt "A date: " --guided-regex '\d{4}-\d{2}-\d{2}'
     python examples/example_client.py --model llama --prompt "A JSON record: " --max-tokens 64 --json   # JSON mode
+    python examples/example_client.py --model llama --prompt "A point: " --max-tokens 64 \
+        --guided-json '{"type": "object", "properties": {"x": {"type": "integer"}, "y": {"type": "integer"}}, "required": ["x", "y"]}'
     python examples/example_client.py --model llama --prompt "a sentence to embed" --embed mean   # the prompt's vector
 """
 
@@ -45,6 +47,9 @@ async def main():
     ap.add_argument("--json", action="store_true", dest="json_object",
                     help="JSON mode: the output is one JSON object, then EOS (a request cut off by --max-tokens "
                          "returns an incomplete document with finish_reason length)")
+    ap.add_argument("--guided-json", default=None, metavar="FILE_OR_JSON",
+                    help="structured output: a JSON Schema (a file name or the JSON text itself); the output is one "
+                         "document valid against it, then EOS")
     ap.add_argument("--embed", nargs="?", const="last", default=None, choices=["last", "mean"], metavar="POOLING",
                     help="return the prompt's embedding (last-token or mean pooling, L2-normalised) instead of text")
     ap.add_argument("--request-key", default=None, help="session key for shard affinity")
@@ -67,6 +72,12 @@ async def main():
             inputs["guided_regex"] = a.guided_regex
         if a.json_object:
             inputs["guided_json_object"] = True
+        if a.guided_json is not None:
+            text = a.guided_json
+            if not text.lstrip().startswith("{"):
+                with open(text, "r", encoding="utf-8") as f:
+                    text = f.read()
+            inputs["guided_json"] = json.loads(text)
         if a.embed is not None:
             inputs = {"prompt": a.prompt, "pooling": a.embed}
     else:

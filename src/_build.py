@@ -27,7 +27,7 @@ ARCH = os.environ.get("DIE_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 KERNELS = ["norm_act", "rope_cache", "attention", "sampling", "logit_process", "token_guide", "byte_guide", "json_guide",
-           "pooling", "moe", "gemm_decode", "decode_step", "allreduce"]
+           "schema_guide", "pooling", "moe", "gemm_decode", "decode_step", "allreduce"]
 CONTRACT_ON = {"attention", "gemm_decode"}
 # the decode step's kernels get the head of their argument list in SGPRs at wave launch (gfx950 kernarg preload:
 # 16 user SGPRs, 14 of them argument dwords); their signatures are ordered for it

@@ -17,6 +17,7 @@ control-plane RPC (``op: kv_import``).
 from __future__ import annotations
 
 import asyncio
+import json
 import logging
 import os
 import time
@@ -294,7 +295,9 @@ def sampling_to_dict(sp: SamplingParams) -> Dict[str, Any]:
             "logit_bias": None if not sp.logit_bias else {str(k): v for k, v in sp.logit_bias.items()},
             "allowed_token_ids": None if sp.allowed_token_ids is None else list(sp.allowed_token_ids),
             "guided_choice": None if sp.guided_choice is None else [list(c) for c in sp.guided_choice],
-            "guided_regex": sp.guided_regex, "guided_json_object": sp.guided_json_object}
+            "guided_regex": sp.guided_regex, "guided_json_object": sp.guided_json_object,
+            # as text: SamplingParams parses it back, and the members keep their declared order on every wire format
+            "guided_json": None if sp.guided_json is None else json.dumps(sp.guided_json)}
 
 
 def packet_for_import(d: Dict[str, Any], device) -> KVPacket:

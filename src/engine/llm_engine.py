@@ -259,14 +259,14 @@ class LLMEngine:
     def _compile_guide(self, sampling: SamplingParams):
         """The token automaton of a guided request (None: not guided), or the ValueError that refuses it: a runner
         without the device state, an id beyond the vocabulary, guided_choice / guided_regex without an
-        end-of-sequence token or with ignore_eos, guided_regex / guided_json_object without a byte table (or with one
+        end-of-sequence token or with ignore_eos, guided_regex / guided_json_object / guided_json without a byte table (or with one
         that lacks a needed single-byte token), an automaton over the caps,
         a pattern that matches nothing."""
         if not getattr(sampling, "guided", False):
             return None
         if not getattr(self.runner, "supports_token_guide", False):
-            raise ValueError("allowed_token_ids / guided_choice / guided_regex / guided_json_object are not "
-                             "supported on a tensor-parallel engine")
+            raise ValueError("allowed_token_ids / guided_choice / guided_regex / guided_json / guided_json_object "
+                             "are not supported on a tensor-parallel engine")
         return compile_guide(sampling, self.arch.vocab_size, self.eos_token_id, self.token_bytes)
 
     def _release_logit_state(self, seq: Sequence, preempted: bool = False) -> None:
@@ -762,6 +762,7 @@ class LLMEngine:
         s["token_guide_launches"] = getattr(self.runner, "token_guide_launches", 0)  # ops.token_guide
         s["byte_guide_launches"] = getattr(self.runner, "byte_guide_launches", 0)  # ops.byte_guide
         s["json_guide_launches"] = getattr(self.runner, "json_guide_launches", 0)  # ops.json_guide
+        s["schema_guide_launches"] = getattr(self.runner, "schema_guide_launches", 0)  # ops.schema_guide
         s["pool_embed_launches"] = getattr(self.runner, "pool_embed_launches", 0)  # ops.pool_embed
         used = getattr(self.runner, "guide_arena_edges_used", None)
         s["guide_arena_edges_used"] = used() if used is not None else 0  # edges of the automata held on the device

@@ -30,7 +30,8 @@ from src.config import EngineConfig
 from src.engine.block_manager import native_runtime
 from src.engine.scheduler import PrefillChunk
 from src.engine.sequence import Sequence
-from src.guided import GUIDE_MAX_TOKEN_BYTES, Automaton, ByteGuide, FirstFit, JsonGuide, table_of, walk
+from src.guided import (GUIDE_MAX_TOKEN_BYTES, Automaton, ByteGuide, FirstFit, JsonGuide, SchemaGuide, table_of,
+                        walk)
 from src.models.llama import AttnMetadata, CausalLM
 
 logger = logging.getLogger(__name__)
@@ -188,6 +189,15 @@ class ModelRunner:
         self.d_jguide = None                    # (trans, jstk)
         self._jguide_up = False                 # the table is on the device
         self.json_guide_launches = 0            # eager launches and replays of the JSON graph set
+        # structured outputs (ops.schema_guide, launched directly behind ops.json_guide): a schema's pushdown table
+        # lives in a third pair of arenas (first fit, one region per distinct spec), a slot's depth and stack of
+        # return states next to cur. The byte table, slots, descriptors, cur and err are the ones above. A row is in
+        # at most one of the four slot vectors.
+        self.h_sguide_slot = torch.full((self.max_seqs,), -1, dtype=i32, pin_memory=pin)
+        self.d_sguide_slot = torch.full((self.max_seqs,), -1, dtype=i32, device=dev)
+        self.d_sguide = None                    # (trans, accept, sdep, sstk)
+        self._sguide_st: Optional[FirstFit] = None
+        self.schema_guide_launches = 0          # eager launches and replays of the schema graph set
         self._guide_slots: Dict[int, int] = {}  # seq_id -> slot
         self._guide_free: List[int] = []
         self._guide_refs: Dict[int, tuple] = {}  # seq_id -> the spec key of the region it references
@@ -203,6 +213,11 @@ class ModelRunner:
         self.graphs_json: Dict[int, torch.cuda.CUDAGraph] = {}
         self.graph_logits_json: Dict[int, torch.Tensor] = {}
         self._json = False                      # the step being assembled has a JSON row (_fill_guide)
+        # a fifth set for batches with a schema row: ... -> byte_guide -> json_guide -> schema_guide -> tail (the four
+        # sets above stay launch for launch what they were)
+        self.graphs_schema: Dict[int, torch.cuda.CUDAGraph] = {}
+        self.graph_logits_schema: Dict[int, torch.Tensor] = {}
+        self._schema = False                    # the step being assembled has a schema row (_fill_guide)
         self.token_guide_launches = 0           # eager launches and guided graph replays
         self._guided = False                    # the step being assembled has a guided row (_fill_sampling)
         # embeddings (ops.pool_embed): requests with SamplingParams.pooling end with their prompt and return its
@@ -369,6 +384,14 @@ class ModelRunner:
         self.d_jguide = (torch.full((ops.GUIDE_JSON_MAX_STATES, 256), -1, dtype=torch.int16, device=dev),
                          torch.zeros(m, 2, dtype=i32, device=dev))
         self.h_jguide = torch.zeros(2, dtype=i32, pin_memory=self.is_cuda)
+        # ops.schema_guide: the arenas, a slot's depth and return states, and the pinned staging of one slot's
+        self.d_sguide = (torch.full((ops.GUIDE_SCHEMA_STATE_ARENA, 256), -1, dtype=i32, device=dev),
+                         torch.zeros(ops.GUIDE_SCHEMA_STATE_ARENA, dtype=torch.uint8, device=dev),
+                         torch.zeros(m, dtype=i32, device=dev),
+                         torch.zeros(m, ops.GUIDE_SCHEMA_MAX_DEPTH, dtype=torch.int16, device=dev))
+        self._sguide_st = FirstFit(ops.GUIDE_SCHEMA_STATE_ARENA)
+        self.h_sguide = (torch.zeros(1, dtype=i32, pin_memory=self.is_cuda),
+                         torch.zeros(ops.GUIDE_SCHEMA_MAX_DEPTH, dtype=torch.int16, pin_memory=self.is_cuda))
 
     @staticmethod
     def _guides(seqs) -> bool:
@@ -376,21 +399,23 @@ class ModelRunner:
         return any(s.sampling.guided for s in seqs)
 
     def _mode(self, seqs) -> int:
-        """Which graph set a decode batch replays: 3 guided with a row in JSON mode, 2 guided (a row is guided), 1
-        processed (a row set a penalty or a bias), 0 raw."""
+        """Which graph set a decode batch replays: 4 guided with a schema row, 3 guided with a row in JSON mode, 2
+        guided (a row is guided), 1 processed (a row set a penalty or a bias), 0 raw."""
+        if any(s.sampling.guided_json is not None for s in seqs):
+            return 4
         if any(s.sampling.guided_json_object for s in seqs):
             return 3
         return 2 if self._guides(seqs) else 1 if self._asks(seqs) else 0
 
     @torch.inference_mode()
     def guide_admit(self, seq: Sequence, auto) -> None:
-        """Reference the arena region of the sequence's automaton, an Automaton, a ByteGuide or a JsonGuide
+        """Reference the arena region of the sequence's automaton, an Automaton, a ByteGuide, a JsonGuide or a SchemaGuide
         (LLMEngine.add_request: a ValueError here refuses the request). Sequences with the same spec share one
         region; a new one is uploaded first-fit, evicting unreferenced regions, least recently used first, until
         it fits."""
         self._guide_alloc()
         reg = self._guide_regions.get(auto.key)
-        if isinstance(auto, (ByteGuide, JsonGuide)):
+        if isinstance(auto, (ByteGuide, JsonGuide, SchemaGuide)):
             self._bguide_vocab(auto)
         if reg is None and isinstance(auto, JsonGuide):
             # one table for every JSON request, uploaded once; the region entry takes no room in any arena (its key
@@ -399,6 +424,22 @@ class ModelRunner:
                 self.d_jguide[0][:auto.n_states].copy_(torch.from_numpy(auto.trans))
                 self._jguide_up = True
             reg = self._guide_regions[auto.key] = {"auto": auto, "js": 0, "refs": 0}
+        elif reg is None and isinstance(auto, SchemaGuide):
+            n = auto.n_states
+            while True:
+                st = self._sguide_st.alloc(n)
+                if st is not None:
+                    break
+                old = next((k for k in self._guide_lru if "sg" in self._guide_regions[k]), None)
+                if old is None:
+                    raise ValueError("no room for the request's guide: the constrained-decoding arena is full")
+                del self._guide_lru[old]
+                self._guide_drop(old)
+            d_tr, d_ac, _, _ = self.d_sguide
+            # on the compute stream: behind every queued window that may still read what lay here
+            d_tr[st:st + n].copy_(torch.from_numpy(auto.trans))
+            d_ac[st:st + n].copy_(torch.from_numpy(auto.accept))
+            reg = self._guide_regions[auto.key] = {"auto": auto, "sg": st, "refs": 0}
         elif reg is None and isinstance(auto, ByteGuide):
             n = auto.n_states
             while True:
@@ -439,13 +480,15 @@ class ModelRunner:
 
     def _bguide_vocab(self, guide) -> None:
         """The vocabulary's bytes on the device: uploaded (on the compute stream, behind every queued window) when
-        the first ByteGuide or JsonGuide arrives, and again only if the engine was paired with another byte table since — which
+        the first ByteGuide, JsonGuide or SchemaGuide arrives, and again only if the engine was paired with another byte table since — which
         is refused while a sequence still walks the old one."""
         tid = guide.key[-1]
         if tid == self._bguide_table:
             return
-        if any("st" in self._guide_regions[k] or "js" in self._guide_regions[k] for k in self._guide_refs.values()):
-            raise ValueError("guided_regex / guided_json_object: the tokenizer's byte table changed while guided requests are running")
+        if any("st" in self._guide_regions[k] or "js" in self._guide_regions[k] or "sg" in self._guide_regions[k]
+               for k in self._guide_refs.values()):
+            raise ValueError("guided_regex / guided_json_object / guided_json: the tokenizer's byte table changed "
+                             "while guided requests are running")
         _, _, d_off, d_by = self.d_bguide
         v = d_off.shape[0] - 1
         table = table_of(tid)
@@ -464,6 +507,9 @@ class ModelRunner:
             return
         if "st" in reg:
             self._bguide_st.release(reg["st"], reg["auto"].n_states)
+            return
+        if "sg" in reg:
+            self._sguide_st.release(reg["sg"], reg["auto"].n_states)
             return
         self._guide_rp.release(reg["rp"], reg["auto"].n_states + 1)
         self._guide_ed.release(reg["ed"], reg["auto"].n_edges)
@@ -491,6 +537,14 @@ class ModelRunner:
             self.h_guide.numpy()[:] = (auto.n_states, auto.done, auto.eos, 0, state, 0)
             self.h_jguide.numpy()[:] = (depth, bits - (1 << 32) if bits >= 1 << 31 else bits)
             self.d_jguide[1][slot].copy_(self.h_jguide, non_blocking=self.is_cuda)
+        elif "sg" in reg:  # (state, depth, return states), by the device's rules (guided.walk_schema)
+            state, depth, stack = state
+            self.h_guide.numpy()[:] = (reg["sg"], auto.n_states, auto.eos, 0, state, 0)
+            h_dep, h_stk = self.h_sguide
+            h_dep[0] = depth
+            h_stk.numpy()[:depth] = stack
+            self.d_sguide[2][slot:slot + 1].copy_(h_dep, non_blocking=self.is_cuda)
+            self.d_sguide[3][slot].copy_(h_stk, non_blocking=self.is_cuda)
         elif "st" in reg:
             self.h_guide.numpy()[:] = (reg["st"], auto.n_states, auto.eos, 0, state, 0)
         else:
@@ -530,45 +584,67 @@ class ModelRunner:
         return self._bguide_st.used if self._bguide_st is not None else 0
 
     def _fill_guide(self, seqs: Seq[Sequence], n_pad: int, all_outputs: bool) -> bool:
-        """d_guide_slot[:n_pad], d_bguide_slot[:n_pad] and d_jguide_slot[:n_pad] for the step (-1: padding, rows that
+        """d_guide_slot[:n_pad], d_bguide_slot[:n_pad], d_jguide_slot[:n_pad] and d_sguide_slot[:n_pad] for the step (-1: padding, rows that
         are not guided, and in each vector the rows another kernel guides); False and nothing written when no row is guided — only
         the guided graphs read them."""
-        self._json = False
+        self._json = self._schema = False
         if not self._guides(seqs):
             return False
         n = len(seqs)
         ns, nb, nj = self.h_guide_slot.numpy(), self.h_bguide_slot.numpy(), self.h_jguide_slot.numpy()
+        nsg = self.h_sguide_slot.numpy()
         for i, s in enumerate(seqs):
             slot = self._guide_build(s, all_outputs) if s.sampling.guided else -1
             reg = self._guide_regions[self._guide_refs[s.seq_id]] if slot >= 0 else ()
             ns[i], nb[i], nj[i] = (-1, -1, slot) if "js" in reg else (-1, slot, -1) if "st" in reg else (slot, -1, -1)
+            if "sg" in reg:
+                ns[i], nsg[i] = -1, slot
+            else:
+                nsg[i] = -1
         ns[n:n_pad] = -1
         nb[n:n_pad] = -1
         nj[n:n_pad] = -1
+        nsg[n:n_pad] = -1
         self._json = bool((nj[:n] >= 0).any())
+        self._schema = bool((nsg[:n] >= 0).any())
+        if self._schema:  # only the schema graphs read it: a batch without a schema row copies nothing more
+            self.d_sguide_slot[:n_pad].copy_(self.h_sguide_slot[:n_pad], non_blocking=self.is_cuda)
         self.d_guide_slot[:n_pad].copy_(self.h_guide_slot[:n_pad], non_blocking=self.is_cuda)
         self.d_bguide_slot[:n_pad].copy_(self.h_bguide_slot[:n_pad], non_blocking=self.is_cuda)
         self.d_jguide_slot[:n_pad].copy_(self.h_jguide_slot[:n_pad], non_blocking=self.is_cuda)
         return True
 
     def _launch_token_guide(self, logits: torch.Tensor, n: int, advance_ids=None, lm_part=None,
-                            json: Optional[bool] = None) -> None:
+                            json: Optional[bool] = None, schema: Optional[bool] = None) -> None:
         """ops.token_guide for the rows a CSR automaton guides and, directly behind it, ops.byte_guide for the rows
         a ByteGuide does and — json (default: the step has a JSON row, _fill_guide) — ops.json_guide for those in
-        JSON mode; the workgroups of every other row exit at once in each."""
+        JSON mode and — schema (default: the step has a schema row) — ops.schema_guide for those a SchemaGuide
+        guides; the workgroups of every other row exit at once in each."""
         desc, _, _, cur, err = self.d_guide
         ops.token_guide(logits, self.d_guide_slot[:n], *self.d_guide, advance_ids=advance_ids, lm_part=lm_part)
         self.token_guide_launches += 1
         ops.byte_guide(logits, self.d_bguide_slot[:n], desc, *self.d_bguide, cur, err, advance_ids=advance_ids,
                        lm_part=lm_part)
         self.byte_guide_launches += 1
-        if not (self._json if json is None else json):
-            return
+        schema = self._schema if schema is None else schema
         _, _, tok_off, tok_bytes = self.d_bguide
-        d_jtr, d_jstk = self.d_jguide
-        ops.json_guide(logits, self.d_jguide_slot[:n], desc, d_jtr, tok_off, tok_bytes, cur, d_jstk, err,
-                       advance_ids=advance_ids, lm_part=lm_part)
-        self.json_guide_launches += 1
+        if self._json if json is None else json:  # (the schema graph set holds the JSON launch too: json = True)
+            d_jtr, d_jstk = self.d_jguide
+            ops.json_guide(logits, self.d_jguide_slot[:n], desc, d_jtr, tok_off, tok_bytes, cur, d_jstk, err,
+                           advance_ids=advance_ids, lm_part=lm_part)
+            self.json_guide_launches += 1
+        if not schema:
+            return
+        d_str, d_sac, d_sdep, d_sstk = self.d_sguide
+        ops.schema_guide(logits, self.d_sguide_slot[:n], desc, d_str, d_sac, tok_off, tok_bytes, cur, d_sdep, d_sstk,
+                         err, advance_ids=advance_ids, lm_part=lm_part)
+        self.schema_guide_launches += 1
+
+    def _step_mode(self) -> int:
+        """_mode of the step being assembled, from the flags _fill_sampling / _fill_guide left."""
+        if not self._guided:
+            return int(self._proc)
+        return 4 if self._schema else 3 if self._json else 2
 
     def _guide_err_to_host(self) -> None:
         """Queue the sticky error words behind a guided step: they come back with its tokens."""
@@ -966,7 +1042,8 @@ class ModelRunner:
             sc = self.dec_scratch
             ops.embed_sumsq(self.d_ids[:pad], self.model.embed, sc["ssp0"], out=sc["h_in"][:pad])
 
-    def _decode_forward(self, n: int, process: bool = False, guide: bool = False, json: bool = False) -> torch.Tensor:
+    def _decode_forward(self, n: int, process: bool = False, guide: bool = False, json: bool = False,
+                        schema: bool = False) -> torch.Tensor:
         tail = self._fused_tail(n)
         meta = AttnMetadata(is_prefill=False, slot_mapping=self.d_slots[:n], block_tables=self.d_bt[:n],
                             ctx_lens=self.d_ctx[:n], max_ctx=self.max_model_len, part_o=self.part_o,
@@ -986,7 +1063,7 @@ class ModelRunner:
             # after the penalties and biases, so that no bias can lift a barred token: advances the guided rows'
             # automata over this step's input ids, masks the rows and makes their greedy candidates agree
             self._launch_token_guide(logits, n, advance_ids=self.d_ids[:n],
-                                     lm_part=amax[:n] if amax is not None else None, json=json)
+                                     lm_part=amax[:n] if amax is not None else None, json=json, schema=schema)
         if not self.is_cuda:
             return ops.sample(logits, self.d_temp[:n], self.d_topk[:n], self.d_topp[:n], self.d_seed[:n],
                               self.d_step[:n])
@@ -1075,8 +1152,20 @@ class ModelRunner:
                 self.graphs_json[b] = g
                 self.graph_logits_json[b] = self._last_logits
             torch.cuda.synchronize(self.device)
+            # a fifth set with ops.schema_guide behind ops.json_guide, replayed only by batches with a schema row
+            self.d_sguide_slot.fill_(-1)
+            for b in sizes:
+                self._decode_forward(b, process=True, guide=True, json=True, schema=True)
+            torch.cuda.synchronize(self.device)
+            for b in reversed(sizes):
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, pool=self._graph_pool):
+                    self._decode_forward(b, process=True, guide=True, json=True, schema=True)
+                self.graphs_schema[b] = g
+                self.graph_logits_schema[b] = self._last_logits
+            torch.cuda.synchronize(self.device)
             self.logit_process_launches = self.token_guide_launches = self.byte_guide_launches = 0
-            self.json_guide_launches = 0
+            self.json_guide_launches = self.schema_guide_launches = 0
         self.graph_sizes = sizes
         logger.info("captured decode hipGraphs for batch sizes %s", sizes)
 
@@ -1104,7 +1193,7 @@ class ModelRunner:
             self.h_ctl[1] = n
             self.d_ctl.copy_(self.h_ctl, non_blocking=True)
         self._sync_step(self.KIND_DECODE, n, pad)
-        mode = (3 if self._json else 2) if self._guided else int(self._proc)
+        mode = self._step_mode()
         ids = self._exec_decode(n, pad, mode)
         if mode >= 2:
             self._guide_err_to_host()
@@ -1112,7 +1201,8 @@ class ModelRunner:
         self.last_logprobs = None
         if top < 0:
             return self._to_host(ids, n)
-        glog = (self.graph_logits, self.graph_logits_proc, self.graph_logits_guided, self.graph_logits_json)[mode]
+        glog = (self.graph_logits, self.graph_logits_proc, self.graph_logits_guided, self.graph_logits_json,
+                self.graph_logits_schema)[mode]
         self._launch_logprobs(glog[pad] if pad in self.graphs else self._last_logits, ids, n, 0, top)
         self._lp_to_host(0, 1)
         toks = self._to_host(ids, n)
@@ -1150,7 +1240,7 @@ class ModelRunner:
         self.d_ctl.copy_(self.h_ctl, non_blocking=True)
         self._sync_window(n, pad, k)
         top = self._lp_top(seqs)
-        self._replay_window(pad, n, k, 0, top, (3 if self._json else 2) if self._guided else int(self._proc))
+        self._replay_window(pad, n, k, 0, top, self._step_mode())
         self._queue_fault_readback()
         if k_next > 1:
             ev = torch.cuda.Event()
@@ -1169,16 +1259,19 @@ class ModelRunner:
         before the next replay overwrites them (stream order) — and the logprob rows come back with the tokens.
         mode (_mode) 1, a row asks for logit processing: the graphs with the ops.logit_process launch and their
         logits; 2, a row is guided: the graphs with the ops.token_guide launch behind it, and the slots' error
-        words come back with the tokens; 3, a row is in JSON mode: the same with the ops.json_guide launch too; 0: the
-        raw graphs, launch for launch as without any of the features."""
-        g = (self.graphs, self.graphs_proc, self.graphs_guided, self.graphs_json)[mode][pad]
+        words come back with the tokens; 3, a row is in JSON mode: the same with the ops.json_guide launch too; 4, a
+        row has a schema: the same with the ops.schema_guide launch behind that; 0: the raw graphs, launch for launch
+        as without any of the features."""
+        g = (self.graphs, self.graphs_proc, self.graphs_guided, self.graphs_json, self.graphs_schema)[mode][pad]
         if mode:
             self.logit_process_launches += k
         if mode >= 2:
             self.token_guide_launches += k
             self.byte_guide_launches += k
-        if mode == 3:
+        if mode >= 3:
             self.json_guide_launches += k
+        if mode == 4:
+            self.schema_guide_launches += k
         if top < 0:
             for _ in range(k):
                 g.replay()
@@ -1186,7 +1279,8 @@ class ModelRunner:
             if mode >= 2:
                 self._guide_err_to_host()
             return
-        logits = (self.graph_logits, self.graph_logits_proc, self.graph_logits_guided, self.graph_logits_json)[mode][pad]
+        logits = (self.graph_logits, self.graph_logits_proc, self.graph_logits_guided, self.graph_logits_json,
+                  self.graph_logits_schema)[mode][pad]
         for i in range(k):
             g.replay()
             self._launch_logprobs(logits, self.d_out, n, base + i, top)
@@ -1245,12 +1339,13 @@ class ModelRunner:
         g = self.graphs.get(pad)
         if g is not None:
             if mode:
-                g = (self.graphs_proc, self.graphs_guided, self.graphs_json)[mode - 1][pad]
+                g = (self.graphs_proc, self.graphs_guided, self.graphs_json, self.graphs_schema)[mode - 1][pad]
                 self.logit_process_launches += 1
                 self.token_guide_launches += mode >= 2
                 self.byte_guide_launches += mode >= 2
-                self.json_guide_launches += mode == 3
+                self.json_guide_launches += mode >= 3
+                self.schema_guide_launches += mode == 4
             g.replay()
             return self.d_out
         # eager: a guided step launches ops.logit_process only when a row asks for it
-        return self._decode_forward(n, self._proc if mode >= 2 else bool(mode), mode >= 2, mode == 3)
+        return self._decode_forward(n, self._proc if mode >= 2 else bool(mode), mode >= 2, mode >= 3, mode == 4)

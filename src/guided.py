@@ -54,6 +54,17 @@ must have a single-byte token other than EOS (checked at compile time, the Value
 of (a) is a token the device allows; in DONE, EOS is allowed. Hence every configuration a sequence can reach allows
 at least one token, and a finite continuation to DONE then EOS exists.
 
+The fourth form, ``SchemaGuide`` (``guided_json``, the gateway's ``response_format: {"type": "json_schema"}``): a
+general byte pushdown automaton whose stack holds RETURN STATES, compiled from a JSON Schema by
+src/guided_schema.py (its docstring has the construction, the refusals and the no-dead-end proof). ``trans`` int32
+[S, 256]: -1, or the next state in bits 0..13, the return state in bits 14..27 (push only) and the action in bits
+28..29 (``SCHEMA_ACT_*``: none, push, pop); ``accept`` uint8 [S]. The configuration is (state, depth, stack): at
+most GUIDE_SCHEMA_MAX_DEPTH entries, a push at the cap is no transition, a pop goes to the popped return state. EOS
+is legal when the state accepts and the depth is 0. A token that would hold more than GUIDE_SCHEMA_TOKEN_PUSHES of
+its own not-yet-popped pushes at once is never allowed: like the byte cap this only narrows the set (its bytes can
+be spelled by shorter tokens, and a single-byte token pushes at most once), and it lets the device keep a chain's
+pushes in one 64-bit register. ``ops.schema_guide`` walks every token's bytes through it inside the decode step.
+
 Pure numpy / Python: imported by ``src.preproc`` for early validation, never touches torch.
 """
 
@@ -75,6 +86,12 @@ GUIDE_MAX_TOKEN_BYTES = 32         # ops.byte_guide never allows a longer token 
 GUIDE_JSON_MAX_DEPTH = 32          # containers open at once, the top-level object included (launchers.h)
 GUIDE_JSON_MAX_STATES = 92         # ops.json_guide keeps the whole table in LDS (launchers.h)
 JSON_ACT_NONE, JSON_ACT_PUSH_OBJECT, JSON_ACT_PUSH_ARRAY, JSON_ACT_POP = 0, 1, 2, 3   # bits 8..9 of a trans entry
+GUIDE_SCHEMA_MAX_DEPTH = 32        # return states live at once in a SchemaGuide's stack (launchers.h)
+GUIDE_SCHEMA_TOKEN_PUSHES = 4      # a token never holds more of its own not-yet-popped pushes (launchers.h)
+SCHEMA_ACT_NONE, SCHEMA_ACT_PUSH, SCHEMA_ACT_POP = 0, 1, 2   # bits 28..29 of a SchemaGuide's trans entry
+_SCHEMA_STATE_BITS = 14            # next state in bits 0..13, return state in bits 14..27
+_SCHEMA_STATE_MASK = (1 << _SCHEMA_STATE_BITS) - 1
+_SCHEMA_BOUND_MAX = 256            # minItems / maxItems / minLength / maxLength
 _QUANT_MAX = 1024                  # {m,n} bound: larger counts only ever end at the state cap
 
 
@@ -206,10 +223,79 @@ def walk_json(guide: JsonGuide, config: Tuple[int, int, int], tokens: Iterable[i
     return config
 
 
+@dataclass(frozen=True, eq=False)
+class SchemaGuide:
+    trans: np.ndarray      # int32 [S, 256]: -1, or next | return state << 14 | action << 28; start state 0
+    accept: np.ndarray     # uint8 [S]
+    eos: int
+    key: tuple             # the canonical spec; its last element names the byte table (id_of / table_of)
+
+    @property
+    def n_states(self) -> int:
+        return self.trans.shape[0]
+
+    @property
+    def sink(self) -> int:
+        return self.trans.shape[0]
+
+
+def schema_step(trans: np.ndarray, config: Tuple[int, int, tuple], byte: int,
+                held: int = 0) -> Optional[Tuple[Tuple[int, int, tuple], int]]:
+    """One byte from (state, depth, stack of return states) by the device's rules; ``held``: the pushes of the
+    running token that are still on the stack. ((state, depth, stack), held), or None: no transition, a push at the
+    depth cap or beyond the token's push cap."""
+    s, d, stk = config
+    v = int(trans[s, byte])
+    if v < 0:
+        return None
+    act = v >> 28
+    if act == SCHEMA_ACT_PUSH:
+        if d >= GUIDE_SCHEMA_MAX_DEPTH or held >= GUIDE_SCHEMA_TOKEN_PUSHES:
+            return None
+        return (v & _SCHEMA_STATE_MASK, d + 1, stk + ((v >> _SCHEMA_STATE_BITS) & _SCHEMA_STATE_MASK,)), held + 1
+    if act == SCHEMA_ACT_POP:
+        if d < 1:
+            raise ValueError("the schema guide pops an empty stack")
+        return (stk[-1], d - 1, stk[:-1]), max(held - 1, 0)
+    return (v & _SCHEMA_STATE_MASK, d, stk), held
+
+
+def walk_schema(guide: SchemaGuide, config: Tuple[int, int, tuple], tokens: Iterable[int],
+                token_bytes: Optional[Sequence[Optional[bytes]]] = None) -> Tuple[int, int, tuple]:
+    """``walk`` for a SchemaGuide over (state, depth, stack of return states), by the device's rules
+    (csrc/kernels/schema_guide.hip): EOS from an accepting state at depth 0 or in the sink gives the sink; any other
+    token walks its bytes, pushes and pops applied, never more than GUIDE_SCHEMA_TOKEN_PUSHES of its own pushes
+    held. A ValueError where the device would report GUIDE_ERR_NO_EDGE."""
+    if token_bytes is None:
+        token_bytes = table_of(guide.key[-1])
+    n = guide.n_states
+    for t in tokens:
+        t = int(t)
+        if t == guide.eos:
+            if config[0] != n and not (guide.accept[config[0]] and config[1] == 0):
+                raise ValueError(f"end of sequence in guide state {config[0]}, which does not accept")
+            config = (n, config[1], config[2])
+            continue
+        bs = token_bytes[t] if 0 <= t < len(token_bytes) else None
+        if config[0] == n or not bs or len(bs) > GUIDE_MAX_TOKEN_BYTES:
+            raise ValueError(f"token {t} has no edge in guide state {config[0]}")
+        c, held = config, 0
+        for b in bs:
+            r = schema_step(guide.trans, c, b, held)
+            if r is None:
+                raise ValueError(f"token {t} has no edge in guide state {config[0]}")
+            c, held = r
+        config = c
+    return config
+
+
 def walk(automaton, state, tokens: Iterable[int]):
     """The state after ``tokens`` from ``state`` (a JsonGuide: the configuration (state, depth, stack bits); start
-    state 0 stands for (0, 0, 0)). A token without an edge is a ValueError: the runner rebuilds
+    state 0 stands for (0, 0, 0); a SchemaGuide: (state, depth, stack of return states), 0 for (0, 0, ())). A token
+    without an edge is a ValueError: the runner rebuilds
     device state from tokens the automaton itself allowed, so this never happens to a healthy sequence."""
+    if isinstance(automaton, SchemaGuide):
+        return walk_schema(automaton, (0, 0, ()) if isinstance(state, int) and state == 0 else state, tokens)
     if isinstance(automaton, JsonGuide):
         return walk_json(automaton, (0, 0, 0) if isinstance(state, int) and state == 0 else state, tokens)
     if isinstance(automaton, ByteGuide):
@@ -966,17 +1052,27 @@ _LOCK = threading.Lock()
 
 def compile_guide(sampling, vocab: int, eos: Optional[int], token_bytes: Optional[Sequence[Optional[bytes]]] = None):
     """The automaton of a request's guide (SamplingParams.guided is true), from a small LRU keyed by the
-    canonical spec: an Automaton, a ByteGuide for a guided_regex over a multi-byte vocabulary, or a JsonGuide for
-    guided_json_object. ValueError for everything the engine must refuse."""
+    canonical spec: an Automaton, a ByteGuide for a guided_regex over a multi-byte vocabulary, a JsonGuide for
+    guided_json_object, or a SchemaGuide for guided_json (its key: the schema dumped with sorted keys). ValueError
+    for everything the engine must refuse."""
     if sampling.allowed_token_ids is not None:
         spec = ("allowed", tuple(sorted(sampling.allowed_token_ids)), vocab)
     else:
         if eos is None:
-            raise ValueError("guided_choice / guided_regex / guided_json_object are not supported on an engine "
-                             "without an end-of-sequence token")
+            raise ValueError("guided_choice / guided_regex / guided_json_object / guided_json are not supported on "
+                             "an engine without an end-of-sequence token")
         if sampling.ignore_eos:
-            raise ValueError("guided_choice / guided_regex / guided_json_object cannot be combined with ignore_eos")
-        if getattr(sampling, "guided_json_object", False):
+            raise ValueError("guided_choice / guided_regex / guided_json_object / guided_json cannot be combined "
+                             "with ignore_eos")
+        if getattr(sampling, "guided_json", None) is not None:
+            if token_bytes is None:
+                raise ValueError("guided_json is not supported on an engine without a byte table of its "
+                                 "tokenizer (the byte-level tokenizer, ByteLevel BPE and byte-fallback "
+                                 "vocabularies provide one)")
+            from src.guided_schema import canonical_schema
+
+            spec = ("json_schema", canonical_schema(sampling.guided_json), vocab, eos, id_of(token_bytes))
+        elif getattr(sampling, "guided_json_object", False):
             if token_bytes is None:
                 raise ValueError("guided_json_object is not supported on an engine without a byte table of its "
                                  "tokenizer (the byte-level tokenizer, ByteLevel BPE and byte-fallback "
@@ -1001,12 +1097,18 @@ def compile_guide(sampling, vocab: int, eos: Optional[int], token_bytes: Optiona
         a = compile_choice(spec[1], eos, vocab)
     elif spec[0] == "json_object":
         a = compile_json_guide(token_bytes, eos, vocab)
+    elif spec[0] == "json_schema":
+        from src.guided_schema import compile_schema_guide
+
+        a = compile_schema_guide(sampling.guided_json, token_bytes, eos, vocab)
     elif _table_facts(token_bytes, eos, min(vocab, len(token_bytes)))[0]:
         # a multi-byte vocabulary: the byte DFA itself, walked per token on the device (ops.byte_guide)
         a = compile_byte_guide(spec[1], token_bytes, eos, vocab)
     else:
         a = compile_regex(spec[1], token_bytes, eos, vocab)
-    if isinstance(a, JsonGuide):
+    if isinstance(a, SchemaGuide):
+        a = SchemaGuide(a.trans, a.accept, a.eos, spec)
+    elif isinstance(a, JsonGuide):
         a = JsonGuide(a.trans, a.done, a.eos, spec)
     elif isinstance(a, ByteGuide):
         a = ByteGuide(a.trans, a.accept, a.eos, spec)
@@ -1054,3 +1156,17 @@ class FirstFit:
     @property
     def used(self) -> int:
         return self.size - sum(ln for _, ln in self.free)
+
+
+# guided_json: the JSON Schema compiler of the fourth form lives in src/guided_schema.py, which imports this module's
+# pieces. Its names are served from here on first use, so either module can be imported first.
+_SCHEMA_EXPORTS = ("canonical_schema", "compile_schema_guide", "schema_check_closable", "schema_closable_sets",
+                   "schema_depth_sets", "schema_to_pda")
+
+
+def __getattr__(name: str):
+    if name in _SCHEMA_EXPORTS:
+        from src import guided_schema
+
+        return getattr(guided_schema, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -11,7 +11,8 @@ coordinator's framed-RPC API. It holds no model state — every request becomes 
                             "repetition_penalty" (> 0), "logit_bias": {token id: -100..100}, <= 300 entries,
                             at most one of "allowed_token_ids": [ids], "guided_choice": [str | [ids]],
                             "guided_regex": str, "response_format": {"type": "json_object"} (or
-                            "guided_json_object": true)}
+                            "guided_json_object": true), "response_format": {"type": "json_schema",
+                            "json_schema": {"name", "schema": {...}}} (or "guided_json": {...})}
                            stream=true answers with server-sent events ("data: {...}" chunks,
                            then "data: [DONE]"), text and token ids per chunk.
                            logprobs=N: choice.logprobs = {"tokens", "token_logprobs", "top_logprobs":
@@ -41,9 +42,17 @@ coordinator's framed-RPC API. It holds no model state — every request becomes 
     true, constrains the output to one JSON object (compact, or with a single space after ',' and ':'; at most 32
     containers deep) followed by EOS: a byte pushdown automaton walked over every token's bytes on the GPU. A
     request cut off by max_tokens returns an incomplete document with finish_reason "length", as OpenAI documents.
-    {"type": "text"} does nothing. Any other type (json_schema included) is a 400 naming it; so are a malformed
+    {"type": "text"} does nothing. Any other type is a 400 naming it; so are a malformed
     response_format, json_object next to allowed_token_ids / guided_choice / guided_regex or with ignore_eos, and
     JSON mode on a model served tensor-parallel or with a tokenizer that has no byte table.
+    Structured outputs (both endpoints): response_format {"type": "json_schema", "json_schema": {"name": ...,
+    "schema": {...}}} ("name" optional, "strict" and "description" accepted and ignored), or the plain field
+    guided_json: {...} (or its JSON text), constrains the output to one document valid against the schema, in JSON
+    mode's text conventions, followed by EOS: the schema is compiled to a byte pushdown automaton with a stack of
+    return states (src/guided_schema.py lists the supported keywords) that the GPU walks over every token's bytes.
+    A json_schema member that is missing, is not an object or lacks an object "schema", an unsupported keyword
+    (named with its JSON pointer), a schema with a dead end or over the state cap, a second guided field,
+    ignore_eos, a model served tensor-parallel or a tokenizer without a byte table is a 400.
     POST /v1/embeddings    {"model", "input": str | [str] | [token ids] | [[token ids]] (<= 2048 items),
                             "encoding_format": "float" | "base64", "dimensions": multiple of 8,
                             "pooling": "last" | "mean", "normalize": bool}
@@ -80,7 +89,7 @@ from src.preproc import SamplingParams
 from src.utils import setup_logging
 
 _LOGIT_PROCESSING = ("presence_penalty", "frequency_penalty", "repetition_penalty", "logit_bias")
-_GUIDED = ("allowed_token_ids", "guided_choice", "guided_regex", "guided_json_object")
+_GUIDED = ("allowed_token_ids", "guided_choice", "guided_regex", "guided_json_object", "guided_json")
 _SAMPLING = ("max_tokens", "temperature", "top_p", "top_k", "seed", "stop_token_ids", "ignore_eos") + \
     _LOGIT_PROCESSING + _GUIDED
 _ROLES = ("system", "user", "assistant", "tool")
@@ -200,11 +209,22 @@ class Gateway:
         fmt = body.get("response_format")
         if fmt is not None:  # OpenAI's JSON mode; "text" is the default and does nothing
             if not isinstance(fmt, dict) or not isinstance(fmt.get("type"), str):
-                raise ValueError('response_format must be an object {"type": "text" | "json_object"}')
+                raise ValueError('response_format must be an object {"type": "text" | "json_object" | "json_schema"}')
             if fmt["type"] == "json_object":
                 inp["guided_json_object"] = True
+            elif fmt["type"] == "json_schema":
+                js = fmt.get("json_schema")
+                if not isinstance(js, dict) or not isinstance(js.get("schema"), dict):
+                    raise ValueError('response_format type json_schema needs "json_schema": {"schema": {...}} '
+                                     '("name" optional; "strict" and "description" are accepted and ignored)')
+                if js.get("name") is not None and not isinstance(js["name"], str):
+                    raise ValueError("response_format json_schema: name must be a string")
+                if "guided_json" in inp:
+                    raise ValueError("response_format json_schema and guided_json name two schemas")
+                inp["guided_json"] = js["schema"]
             elif fmt["type"] != "text":
-                raise ValueError(f"response_format type {fmt['type']!r} is not supported (text, json_object)")
+                raise ValueError(f"response_format type {fmt['type']!r} is not supported (text, json_object, "
+                                 "json_schema)")
         # ranges and types of the penalties / bias: refused here with a 400, not by a worker after routing
         SamplingParams(**{k: inp[k] for k in _LOGIT_PROCESSING if k in inp})
         # the same for constrained decoding (shapes, "at most one", the regex subset, ignore_eos); a text choice

@@ -361,6 +361,34 @@ def json_guide(logits: torch.Tensor, slot: torch.Tensor, desc: torch.Tensor, tra
     return logits
 
 
+# structured outputs (launchers.h)
+GUIDE_SCHEMA_MAX_DEPTH = ref.GUIDE_SCHEMA_MAX_DEPTH        # return states live at once
+GUIDE_SCHEMA_TOKEN_PUSHES = ref.GUIDE_SCHEMA_TOKEN_PUSHES  # a token's own pushes held at once
+GUIDE_SCHEMA_STATE_ARENA = ref.GUIDE_SCHEMA_STATE_ARENA    # states shared by all slots: trans int32 [., 256] 16 MiB
+
+
+def schema_guide(logits: torch.Tensor, slot: torch.Tensor, desc: torch.Tensor, trans: torch.Tensor,
+                 accept: torch.Tensor, tok_off: torch.Tensor, tok_bytes: torch.Tensor, cur: torch.Tensor,
+                 sdep: torch.Tensor, sstk: torch.Tensor, err: torch.Tensor,
+                 advance_ids: Optional[torch.Tensor] = None, lm_part: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Structured outputs on ``logits`` [rows, vocab] bf16 IN PLACE: every token whose BYTES the row's byte pushdown
+    automaton cannot read from its configuration becomes ``-inf``, an allowed entry keeps its exact bits
+    (:func:`reference.schema_guide_rows` is the contract). Row r uses ``slot[r]`` (int32; < 0: the row is left
+    untouched): ``desc`` int32 [slots, 4] = (state_base, n_states, eos, 0) into the arenas ``trans`` int32 [A, 256]
+    (-1, or next state | return state << 14 | action << 28: 0 none, 1 push, 2 pop) and ``accept`` uint8 [A]. The
+    configuration is ``cur[slot]`` (``n_states``: the sink, entered by EOS from an accepting state at depth 0) with
+    ``sdep`` int32 [slots], the depth, and ``sstk`` int16 [slots, 32], the return states (the oldest first; entries
+    at or above the depth are never read). A push at depth 32, and a token's fifth own push that is still held, are
+    no transition. ``tok_off`` / ``tok_bytes``, ``cur`` / ``err``, ``advance_ids`` and ``lm_part`` as in
+    :func:`byte_guide` (the same arrays: a slot belongs to one of the four ops)."""
+    if not logits.is_cuda:
+        return ref.schema_guide_rows(logits, slot, desc, trans, accept, tok_off, tok_bytes, cur, sdep, sstk, err,
+                                     advance_ids, lm_part)
+    _kern().schema_guide(logits, slot, desc, trans, accept, tok_off, tok_bytes, cur, sdep, sstk, err, advance_ids,
+                         lm_part)
+    return logits
+
+
 # embedding pooling (launchers.h): a segment descriptor's flag bits, and the row split of long mean segments
 POOL_MEAN, POOL_FIRST, POOL_FINAL = 1, 2, 4
 POOL_MAX_PARTS = 64    # workgroups per segment

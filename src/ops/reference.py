@@ -511,6 +511,142 @@ def json_guide_rows(logits, slot, desc, trans, tok_off, tok_bytes, cur, jstk, er
     return logits
 
 
+GUIDE_SCHEMA_MAX_DEPTH = 32       # schema_guide: return states live at once
+GUIDE_SCHEMA_TOKEN_PUSHES = 4     # schema_guide: a token's own pushes held at once
+GUIDE_SCHEMA_STATE_ARENA = 16384  # schema_guide: states shared by all slots (trans int32 [., 256]: 16 MiB)
+
+
+def schema_guide_rows(logits, slot, desc, trans, accept, tok_off, tok_bytes, cur, sdep, sstk, err, advance_ids=None,
+                      lm_part=None):
+    """ops.schema_guide on host tensors (the contract of csrc/kernels/schema_guide.hip): row r -> slot[r] -> desc
+    (state_base, n_states, eos, 0) into trans int32 [A, 256] / accept uint8 [A]. An entry is -1 or next state |
+    return state << 14 | action << 28 (1 push, 2 pop). The configuration (cur, sdep, sstk[:sdep]) advances over
+    advance_ids[r] first (EOS from an accepting state at depth 0 or in the sink: the sink; a token whose walk dies,
+    pushes at the depth cap or holds more than four of its own pushes, without bytes, over the length cap, beyond
+    the table, or any token but EOS in the sink: err |= 1, configuration kept). Allowed next: in the sink EOS alone;
+    else EOS iff the state accepts at depth 0, and every token of 1..32 bytes whose walk never dies. Barred entries
+    become -inf, the others keep their bits; lm_part candidates are overwritten with the best allowed entry.
+    Anything out of bounds (the region, the state, the depth, a live stack entry, eos, an offset, an entry read
+    that is negative but not -1, has a bit above 29, action 3, a state field at or above n_states, or pops at depth
+    0): err |= 2 and row, candidates and configuration stay untouched."""
+    import numpy as np
+
+    vocab = logits.shape[1]
+    tr_all, ac_all = trans.numpy(), accept.numpy()
+    off, by = tok_off.numpy().astype(np.int64), tok_bytes.numpy()
+    arena, n_tok, blen = min(tr_all.shape[0], ac_all.shape[0]), len(off) - 1, len(by)
+    lim = min(vocab, n_tok)
+    cap, held_cap = GUIDE_SCHEMA_MAX_DEPTH, GUIDE_SCHEMA_TOKEN_PUSHES
+
+    def step(tr, ns, stack, st, dp, ov, cnt, b):
+        """The chains (int64 arrays; ov [N, 4]: a chain's own pushes, the latest first) over bytes b."""
+        v = tr[st, b].astype(np.int64)
+        none = v == -1
+        nxt, ret, act = v & 0x3FFF, (v >> 14) & 0x3FFF, (v >> 28) & 3
+        push, pop = act == 1, act == 2
+        oob = ~none & ((v < 0) | (v >= 1 << 30) | (act == 3) | (nxt >= ns) | (ret >= ns) | (pop & (dp < 1)))
+        dead = none | oob | (push & ((dp >= cap) | (cnt >= held_cap)))
+        own = cnt > 0
+        landed = np.where(own, ov[:, 0], stack[np.clip(dp - 1, 0, cap - 1)])
+        do_push, do_pop = push & ~dead, pop & ~dead & own
+        shifted_in = np.concatenate([ret[:, None], ov[:, :3]], axis=1)
+        shifted_out = np.concatenate([ov[:, 1:], np.zeros((len(v), 1), dtype=np.int64)], axis=1)
+        ov = np.where(do_push[:, None], shifted_in, np.where(do_pop[:, None], shifted_out, ov))
+        cnt = cnt + do_push - do_pop
+        dp = dp + do_push - (pop & ~dead)
+        return np.where(dead, -1, np.where(pop, landed, nxt)), dp, ov, cnt, bool(oob.any())
+
+    for r in range(logits.shape[0]):
+        s = int(slot[r])
+        if s < 0 or s >= desc.shape[0]:
+            continue
+        sb, ns, eos = (int(v) for v in desc[s, :3])
+        c, d = int(cur[s]), int(sdep[s])
+        if (sb < 0 or ns < 1 or sb + ns > arena or ns > 16384 or not 0 <= c <= ns or not 0 <= d <= cap
+                or not 0 <= eos < vocab):
+            err[s] |= GUIDE_ERR_TABLE
+            continue
+        stack = np.zeros(cap, dtype=np.int64)
+        stack[:d] = sstk[s, :d].numpy()
+        if ((stack[:d] < 0) | (stack[:d] >= ns)).any():
+            err[s] |= GUIDE_ERR_TABLE
+            continue
+        tr, ac = tr_all[sb:sb + ns], ac_all[sb:sb + ns]
+        flags, bad = 0, False
+        if advance_ids is not None:
+            tok = int(advance_ids[r])
+            if tok == eos:
+                if c == ns or (ac[c] and d == 0):
+                    c = ns
+                else:
+                    flags = GUIDE_ERR_NO_EDGE
+            elif c == ns or not 0 <= tok < lim:
+                flags = GUIDE_ERR_NO_EDGE
+            else:
+                lo, hi = int(off[tok]), int(off[tok + 1])
+                if not 0 <= lo <= hi <= blen:
+                    bad = True
+                elif hi == lo or hi - lo > GUIDE_MAX_TOKEN_BYTES:
+                    flags = GUIDE_ERR_NO_EDGE
+                else:
+                    st, dp, cnt = np.array([c]), np.array([d]), np.array([0])
+                    ov = np.zeros((1, 4), dtype=np.int64)
+                    for p in range(lo, hi):
+                        st, dp, ov, cnt, oob = step(tr, ns, stack, st, dp, ov, cnt, by[p:p + 1])
+                        bad = bad or oob
+                        if st[0] < 0:
+                            break
+                    if bad:
+                        pass
+                    elif st[0] < 0:
+                        flags = GUIDE_ERR_NO_EDGE
+                    else:
+                        c, d, k = int(st[0]), int(dp[0]), int(cnt[0])
+                        stack[d - k:d] = ov[0, :k][::-1]   # the token's pushes that are still held, oldest first
+        allowed = np.zeros(vocab, dtype=bool)
+        if not bad and c < ns:
+            lo, hi = off[:lim], off[1:lim + 1]
+            bad = bool(((lo < 0) | (hi < lo) | (hi > blen)).any())
+            if not bad:
+                ln = hi - lo
+                st = np.where((ln >= 1) & (ln <= GUIDE_MAX_TOKEN_BYTES), c, -1).astype(np.int64)
+                dp, cnt = np.full(lim, d, dtype=np.int64), np.zeros(lim, dtype=np.int64)
+                ov = np.zeros((lim, 4), dtype=np.int64)
+                for level in range(GUIDE_MAX_TOKEN_BYTES):
+                    idx = np.nonzero((st >= 0) & (level < ln))[0]
+                    if not len(idx):
+                        break
+                    st[idx], dp[idx], ov[idx], cnt[idx], oob = step(tr, ns, stack, st[idx], dp[idx], ov[idx],
+                                                                   cnt[idx], by[lo[idx] + level])
+                    bad = bad or oob
+                allowed[:lim] = st >= 0
+                allowed[eos] = bool(ac[c]) and d == 0
+        elif not bad:
+            allowed[eos] = True
+        if bad:
+            err[s] |= GUIDE_ERR_TABLE
+            continue
+        cur[s] = c
+        sdep[s] = d
+        sstk[s, :d] = torch.from_numpy(stack[:d]).to(sstk.dtype)
+        err[s] |= flags
+        allowed = torch.from_numpy(allowed)
+        logits[r, :vocab] = torch.where(allowed, logits[r, :vocab],
+                                        torch.tensor(float("-inf"), dtype=logits.dtype))
+        if lm_part is not None:
+            x = logits[r, :vocab].float()
+            ok = allowed & ~torch.isnan(x)  # a NaN never wins a comparison (sampling.hip's better())
+            x = torch.where(ok, x, torch.tensor(float("-inf")))
+            v = x.max()
+            first = ((x == v) & ok).nonzero()  # lowest allowed index holding the maximum
+            lm_part[r, :, 0] = torch.tensor(float("-inf")).view(torch.int32)
+            lm_part[r, :, 1] = 0x7fffffff
+            if first.numel():
+                lm_part[r, 0, 0] = x[int(first[0])].view(torch.int32)  # that entry's own bits (-0.0 equals +0.0)
+                lm_part[r, 0, 1] = int(first[0])
+    return logits
+
+
 POOL_MEAN, POOL_FIRST, POOL_FINAL = 1, 2, 4  # flag bits of a pool_embed segment descriptor
 
 

@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import asyncio
 import concurrent.futures as cf
+import json
 import math
 import os
 from dataclasses import dataclass, field
@@ -106,6 +107,11 @@ class SamplingParams:
     # with a single space after ',' and ':', then EOS (src/guided.py: a byte pushdown automaton that ops.json_guide
     # walks on the device). One of the "at most one" fields above.
     guided_json_object: bool = False
+    # structured outputs (the gateway's response_format {"type": "json_schema"}): a JSON Schema, a dict or its JSON
+    # text; the output is one document valid against it, in JSON mode's text conventions, then EOS
+    # (src/guided_schema.py: the supported keywords, everything else is refused by name; ops.schema_guide walks the
+    # compiled byte pushdown automaton on the device). One of the "at most one" fields above.
+    guided_json: Optional[Any] = None
     # embeddings: with pooling set the request generates nothing. It ends when its prompt does, and its result is
     # the pooled final-norm hidden state of the prompt (ops.pool_embed): "last" = the last prompt token's row,
     # "mean" = the mean over all prompt rows; cut to its first embed_dimensions components (None: all; a multiple
@@ -179,15 +185,15 @@ class SamplingParams:
             raise ValueError("pooling cannot be combined with penalties or logit_bias")
         if self.guided:
             raise ValueError("pooling cannot be combined with allowed_token_ids / guided_choice / guided_regex / "
-                             "guided_json_object")
+                             "guided_json_object / guided_json")
 
     def _check_guided(self) -> None:
         if not isinstance(self.guided_json_object, bool):
             raise ValueError("guided_json_object must be a boolean")
-        if sum(v is not None for v in (self.allowed_token_ids, self.guided_choice, self.guided_regex)) + \
-                self.guided_json_object > 1:
-            raise ValueError("at most one of allowed_token_ids, guided_choice, guided_regex and guided_json_object "
-                             "may be set")
+        if sum(v is not None for v in (self.allowed_token_ids, self.guided_choice, self.guided_regex,
+                                       self.guided_json)) + self.guided_json_object > 1:
+            raise ValueError("at most one of allowed_token_ids, guided_choice, guided_regex, guided_json_object and "
+                             "guided_json may be set")
 
         def ids_of(v, name):
             if not isinstance(v, (list, tuple)) or not v:
@@ -224,6 +230,17 @@ class SamplingParams:
             raise ValueError("guided_choice / guided_regex cannot be combined with ignore_eos")
         if self.ignore_eos and self.guided_json_object:
             raise ValueError("guided_json_object cannot be combined with ignore_eos")
+        if self.guided_json is not None:
+            from src.guided import schema_to_pda
+
+            if isinstance(self.guided_json, str):
+                try:
+                    self.guided_json = json.loads(self.guided_json)
+                except ValueError:
+                    raise ValueError("guided_json must be a JSON Schema: an object, or its JSON text") from None
+            if self.ignore_eos:
+                raise ValueError("guided_json cannot be combined with ignore_eos")
+            schema_to_pda(self.guided_json)  # table-free compile: a ValueError names the keyword and its pointer
 
     @property
     def greedy(self) -> bool:
@@ -239,7 +256,7 @@ class SamplingParams:
     def guided(self) -> bool:
         """Constrained decoding asked for: the request's rows go through ops.token_guide before sampling."""
         return (self.allowed_token_ids is not None or self.guided_choice is not None or self.guided_regex is not None
-                or self.guided_json_object)
+                or self.guided_json_object or self.guided_json is not None)
 
 
 @dataclass
@@ -252,7 +269,8 @@ class GenerationInputs:
 
 _SAMPLING_KEYS = ("max_tokens", "temperature", "top_k", "top_p", "seed", "ignore_eos", "stop_token_ids",
                   "logprobs", "prompt_logprobs", "presence_penalty", "frequency_penalty", "repetition_penalty",
-                  "logit_bias", "allowed_token_ids", "guided_choice", "guided_regex", "guided_json_object", "pooling",
+                  "logit_bias", "allowed_token_ids", "guided_choice", "guided_regex", "guided_json_object", "guided_json",
+                  "pooling",
                   "embed_normalize", "embed_dimensions")
 
 
