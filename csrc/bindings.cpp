@@ -136,18 +136,29 @@ void check_cache(const Tensor& c, int64_t hkv, int64_t head_dim, const char* nam
               " must be [num_blocks, num_kv_heads, block_size, head_dim]");
 }
 
+// positions, slot_mapping and cos_sin reach the RoPE kernels as raw pointers: dense arrays on the rows' device
+void check_rope_index(const Tensor& positions, const Tensor& slot_mapping, const Tensor& cos_sin, const Tensor& like,
+                      int64_t tokens, int64_t head_dim) {
+  CHK_DTYPE(positions, at::kLong);
+  CHK_DTYPE(slot_mapping, at::kLong);
+  CHK_DTYPE(cos_sin, at::kFloat);
+  CHK_CONTIG(positions);
+  CHK_CONTIG(slot_mapping);
+  CHK_CONTIG(cos_sin);
+  TORCH_CHECK(positions.device() == like.device() && slot_mapping.device() == like.device() &&
+                  cos_sin.device() == like.device(),
+              "positions, slot_mapping and cos_sin must be on the device of the rows");
+  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == head_dim, "cos_sin must be [max_pos, head_dim]");
+  TORCH_CHECK(positions.numel() >= tokens && slot_mapping.numel() >= tokens, "positions/slots too short");
+}
+
 void rope_and_cache(Tensor qkv, Tensor positions, Tensor cos_sin, Tensor slot_mapping, Tensor k_cache,
                     Tensor v_cache, int64_t hq, int64_t hkv, int64_t head_dim, bool rot_q, Tensor row_scale) {
   CHK_CUDA(qkv);
   CHK_BF16(qkv);
   check_rows(qkv, "qkv");
   TORCH_CHECK(qkv.size(1) >= (hq + 2 * hkv) * head_dim, "qkv width < (hq + 2*hkv) * head_dim");
-  CHK_DTYPE(positions, at::kLong);
-  CHK_DTYPE(slot_mapping, at::kLong);
-  CHK_DTYPE(cos_sin, at::kFloat);
-  CHK_CONTIG(cos_sin);
-  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == head_dim, "cos_sin must be [max_pos, head_dim]");
-  TORCH_CHECK(positions.numel() >= qkv.size(0) && slot_mapping.numel() >= qkv.size(0), "positions/slots too short");
+  check_rope_index(positions, slot_mapping, cos_sin, qkv, qkv.size(0), head_dim);
   check_cache(k_cache, hkv, head_dim, "k_cache");
   check_cache(v_cache, hkv, head_dim, "v_cache");
   TORCH_CHECK(k_cache.sizes() == v_cache.sizes(), "k/v cache shapes differ");
@@ -1184,11 +1195,7 @@ void rope_and_cache_slab(Tensor q_out, Tensor slab, Tensor positions, Tensor cos
   const int64_t T = slab.size(1);
   TORCH_CHECK(slab.dim() == 3 && slab.size(2) == (hq + 2 * hkv) * head_dim, "slab [sk, T, (hq+2hkv)*D]");
   TORCH_CHECK(q_out.numel() >= T * hq * head_dim, "q_out too small");
-  CHK_DTYPE(positions, at::kLong);
-  CHK_DTYPE(slot_mapping, at::kLong);
-  CHK_DTYPE(cos_sin, at::kFloat);
-  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.size(1) == head_dim, "cos_sin must be [max_pos, head_dim]");
-  TORCH_CHECK(positions.numel() >= T && slot_mapping.numel() >= T, "positions/slots too short");
+  check_rope_index(positions, slot_mapping, cos_sin, slab, T, head_dim);
   check_cache(k_cache, hkv, head_dim, "k_cache");
   check_cache(v_cache, hkv, head_dim, "v_cache");
   HIP_OK(die::launch_rope_and_cache_slab(bf(q_out), slab.data_ptr<float>(), (int)slab.size(0),

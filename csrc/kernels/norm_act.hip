@@ -310,8 +310,17 @@ __global__ void __launch_bounds__(256) silu_mul_kernel(bf16_t* __restrict__ out,
     unpack8(uv[i], b);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float ga = a[j] * r;
-      y[j] = ga * __builtin_amdgcn_rcpf(1.f + __expf(-ga)) * (b[j] * r);
+      const float ga = a[j] * r, ub = b[j] * r;
+      // silu(ga) * ub = ga / (1 + e) * ub with e = __expf(-ga) = exp2(t). From t = 126 up (ga <= -87.34; e = +inf
+      // below -88.72) the reciprocal of 1 + e is subnormal and v_rcp_f32 returns 0, although ga e^ga ub can still be
+      // a normal number. There 1 + e == e in fp32, so the denominator is taken as exp2(t - 64), inside the normal
+      // range of both instructions, and the 2^-64 is put back by an exact multiply at the end (ga / e first: ga ub
+      // can overflow). One exp and one reciprocal either way; every t < 126 keeps its bits.
+      const float t = 0x1.715476p+0f * -ga;
+      const bool far = t >= 126.f;
+      const float e = __builtin_amdgcn_exp2f(far ? t - 64.f : t);
+      const float v = ga * __builtin_amdgcn_rcpf(far ? e : 1.f + e) * ub;
+      y[j] = far ? v * 0x1p-64f : v;
     }
     if (c < nc) o[c] = pack8(y);
   }
