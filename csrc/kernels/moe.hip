@@ -29,7 +29,7 @@ __global__ void topk_softmax_kernel(float* __restrict__ w_out, int* __restrict__
     for (int e = 0; e < E; ++e) {
       if ((taken[e >> 6] >> (e & 63)) & 1ull) continue;
       const float v = bf2f(g[e]);
-      if (v > bv) {
+      if (v > bv || bi < 0) {  // as moe_route_kernel: nothing compares greater (-inf, NaN) -> lowest untaken index
         bv = v;
         bi = e;
       }

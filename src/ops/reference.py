@@ -681,8 +681,12 @@ def pool_embed_rows(hidden, segs, acc, out, dims: int = 0, normalize: bool = Tru
 
 
 def topk_softmax(gating: torch.Tensor, k: int, renorm: bool = True):
-    p = torch.softmax(gating.float(), dim=-1)
-    w, ids = torch.topk(p, k, dim=-1)
+    """Slots in descending logit order, the lowest expert index first among equal logits: the rule of the HIP
+    kernels (torch.topk leaves the order of ties open), stated by a stable descending sort."""
+    g = gating.float()
+    p = torch.softmax(g, dim=-1)
+    ids = torch.sort(g, dim=-1, descending=True, stable=True).indices[..., :k]
+    w = p.gather(-1, ids)
     if renorm:
         w = w / w.sum(-1, keepdim=True)
     return w, ids.int()
