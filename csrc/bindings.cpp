@@ -909,6 +909,10 @@ static void gemm_decode_impl(Tensor y, Tensor x, Tensor w, int64_t mode, int64_t
   const bool tiled = (mode & 32) != 0;  // w pre-packed by ops.gd_pack_weights for this (mode, wr)
   // mode bit 64: the half-LDS ring (mode 3, <= 32 rows), two workgroups resident per CU (GemmDecodeFuse.half_ring)
   fz.half_ring = (mode & 64) != 0 ? 1 : 0;
+  // mode bit 128: w in the lossless 13-bit layout (ops.gd_pack_weights_p13), its base7 in mode bits 8..14
+  fz.p13 = (mode & 128) != 0 ? 1 : 0;
+  fz.p13_base7 = fz.p13 ? (int)((mode >> 8) & 127) : 0;
+  TORCH_CHECK(!(fz.p13 && tiled), "gemm_decode: P13 weights are not also TILED");
   mode &= 31;
   const int64_t M = x.size(0), K = x.size(1);
   TORCH_CHECK(M >= 1 && M <= 128, "gemm_decode: 1 <= M <= 128");
@@ -931,7 +935,9 @@ static void gemm_decode_impl(Tensor y, Tensor x, Tensor w, int64_t mode, int64_t
     N = y.size(1);
     ldy = y.stride(0);
   }
-  TORCH_CHECK(w.dim() == 2 && w.size(1) == K && w.size(0) == (silu ? 2 * N : N), "gemm_decode w shape");
+  TORCH_CHECK(w.dim() == 2 && w.size(1) == K &&
+                  (fz.p13 ? w.size(0) * 16 == (silu ? 2 * N : N) * 13 : w.size(0) == (silu ? 2 * N : N)),
+              "gemm_decode w shape");
   TORCH_CHECK(N % (silu ? wrr / 2 : wrr) == 0, "N not a multiple of the column tile");
   TORCH_CHECK((int64_t)sk * M * N * 4 < ((int64_t)1 << 31) || mode != 3, "slab too large");
   fz.ts = g_gd_ts;
@@ -991,6 +997,7 @@ int64_t gd_occupancy(int64_t mode, int64_t wr, int64_t kc, int64_t sk, int64_t r
   if (!gd_tile_ok(wr, kc) || rows < 1 || rows > 128 || sk < 1) return -1;
   die::GemmDecodeFuse fz;
   fz.half_ring = (mode & 64) != 0 ? 1 : 0;
+  fz.p13 = (mode & 128) != 0 ? 1 : 0;
   const int m = (int)(mode & 31);
   // stand-ins for the pointers the launcher validates (never dereferenced: nothing is launched)
   static char dummy[64];
@@ -1014,7 +1021,8 @@ int64_t gd_occupancy(int64_t mode, int64_t wr, int64_t kc, int64_t sk, int64_t r
 // y = x @ w^T (mode 0, bf16) that also writes each column tile's per-row greedy candidate into amax
 // [M, N / wr, 2] int32 (value bits, column): the decode step's LM head, whose argmax then reduces N / wr
 // candidates per row (sample(..., lm_part=amax)) instead of re-reading the logits.
-void gemm_decode_argmax(Tensor y, Tensor x, Tensor w, int64_t wr, int64_t kc, bool tiled, Tensor amax) {
+// layout: 0 row-major w, 1 tile order (TILED), or a mode word's layout flags (P13 | base7 << 8).
+void gemm_decode_argmax(Tensor y, Tensor x, Tensor w, int64_t wr, int64_t kc, int64_t layout, Tensor amax) {
   CHK_DTYPE(amax, at::kInt);
   CHK_CONTIG(amax);
   TORCH_CHECK(amax.is_cuda() && amax.dim() == 3 && amax.size(0) >= x.size(0) && amax.size(2) == 2 &&
@@ -1023,7 +1031,8 @@ void gemm_decode_argmax(Tensor y, Tensor x, Tensor w, int64_t wr, int64_t kc, bo
   die::GemmDecodeFuse fz;
   fz.amax = reinterpret_cast<uint32_t*>(amax.data_ptr<int>());
   fz.amax_parts = (int)amax.size(1);
-  gemm_decode_impl(y, x, w, tiled ? 32 : 0, wr, kc, 1, true, x, x, x, x, 0.0, fz);
+  TORCH_CHECK(layout >= 0 && (layout & 31) <= 1, "gemm_decode_argmax: layout");
+  gemm_decode_impl(y, x, w, layout == 1 ? 32 : layout, wr, kc, 1, true, x, x, x, x, 0.0, fz);
 }
 
 // Tensor-parallel row-parallel projection in ONE launch (decode, mode 3): this rank's K-shard GEMM, the one-shot

@@ -32,6 +32,7 @@
 //    next RMSNorm's row statistics.
 #include "car_common.h"
 #include "common.h"
+#include "gd_p13.h"
 #include "gd_tiles.h"
 #include "launchers.h"
 
@@ -53,18 +54,25 @@ template <int AUX = 0>
 __device__ __forceinline__ void glds16(const void* src, char* lds_wave_base) {
   __builtin_amdgcn_global_load_lds((global_cvoid*)src, (lds_void*)lds_wave_base, 16, 0, AUX);
 }
+template <int AUX = 0>
+__device__ __forceinline__ void glds4(const void* src, char* lds_wave_base) {  // 4 B per lane: a 256-byte piece
+  __builtin_amdgcn_global_load_lds((global_cvoid*)src, (lds_void*)lds_wave_base, 4, 0, AUX);
+}
 
 // The kernel's `head` word: everything small that the entry reads before its first LDS-DMA, in one preloaded
 // dword (see gemm_decode_kernel): flags, the EPI 4 / 6 statistics tile count and the split-K count (grid y).
 constexpr uint32_t HEAD_TILED = 1u;   // fz.tiled
 constexpr uint32_t HEAD_TS = 2u;      // fz.ts != nullptr
 constexpr uint32_t HEAD_ROWS = 4u;    // fz.grp_rows != nullptr
-constexpr int HEAD_TILES_SHIFT = 8;   // 9 bits: fz.ssp_tiles (<= DECODE_SSP_MAX_TILES = 256)
+constexpr int HEAD_TILES_SHIFT = 3;   // 9 bits: fz.ssp_tiles (<= DECODE_SSP_MAX_TILES = 256)
 constexpr uint32_t HEAD_TILES_MASK = 0x1ffu;
+constexpr int HEAD_B7_SHIFT = 12;     // 7 bits: fz.p13_base7 (the P13 weights' exponent base, gd_p13.h)
+constexpr uint32_t HEAD_B7_MASK = 0x7fu;
 constexpr int HEAD_NY_SHIFT = 20;     // 12 bits: split-K slices
 constexpr int HEAD_NY_MAX = 4095;
-static_assert(DECODE_SSP_MAX_TILES <= (int)HEAD_TILES_MASK && HEAD_TILES_SHIFT + 9 <= HEAD_NY_SHIFT,
-              "tile count fits its field");
+static_assert(DECODE_SSP_MAX_TILES <= (int)HEAD_TILES_MASK && HEAD_TILES_SHIFT + 9 <= HEAD_B7_SHIFT &&
+                  HEAD_B7_SHIFT + 7 <= HEAD_NY_SHIFT,
+              "tile count and exponent base fit their fields");
 
 template <int N>
 __device__ __forceinline__ void wait_vm() {
@@ -173,7 +181,10 @@ __device__ __forceinline__ uint32_t car_tile_exchange(f4 (&own)[EPT], const Gemm
 // KC = K elements per ring slot. XR = activation rows staged per chunk.
 // NT: weight pieces are loaded non-temporal (aux = 2): each weight byte is read once per step by one CU,
 // so it should not displace the activations / KV in L2 and MALL (MI355X_MICROARCH.md "nt-weights").
-template <int WR, int EPI, int S, bool NT, int KC, int XR, int SKC = 0>
+// P13: W is the lossless 13-bit form of the tile-order weights (gd_p13.h: low-byte, code and sign planes per
+// K-chunk, 13/16 of the bytes). Only the slot geometry, the piece issue and the B-fragment load differ: the
+// fragment is rebuilt in registers to the same 8 bf16, so every accumulator sees the same operands in the same order.
+template <int WR, int EPI, int S, bool NT, int KC, int XR, int SKC = 0, bool P13 = false>
 __device__ __forceinline__ void gd_body(char* smem, void* Yv, int64_t ldy, const bf16_t* __restrict__ X, int64_t ldx,
                                         const bf16_t* __restrict__ W, int M, int N_out, int K, const uint32_t head,
                                         const int* __restrict__ grp_off, const float* __restrict__ ssp_in,
@@ -183,8 +194,10 @@ __device__ __forceinline__ void gd_body(char* smem, void* Yv, int64_t ldy, const
   constexpr int RPP = 64 / CPR;                // rows per 1-KiB DMA piece
   constexpr bool SILU = EPI == 1 || EPI == 4 || EPI == 6;
   constexpr int NO = SILU ? WR / 2 : WR;       // output columns per workgroup
-  constexpr int SLOT = (WR + XR) * ROWB;       // bytes per ring slot
-  constexpr int INSTR = (WR + XR) / RPP;       // 1-KiB DMA pieces per chunk
+  constexpr int WIMG = P13 ? p13::CHUNK_BYTES : WR * ROWB;            // bytes of the weight image in a slot
+  constexpr int WPIECES = P13 ? p13::W_PIECES : WR / RPP;             // its DMA pieces
+  constexpr int SLOT = WIMG + XR * ROWB;       // bytes per ring slot
+  constexpr int INSTR = WPIECES + XR / RPP;    // DMA pieces per chunk (1 KiB; P13's sign pieces 256 B)
   constexpr int SPLIT = XR >= 64 ? 2 : (KC >= 128 ? 0 : 1);  // waves split 0: K, 1: columns, 2: rows
   constexpr int NTILE = WR / 16;               // 16-column MFMA tiles
   constexpr int MT = SPLIT == 2 ? XR / 64 : XR / 16;   // 16-row MFMA tiles per wave
@@ -197,6 +210,9 @@ __device__ __forceinline__ void gd_body(char* smem, void* Yv, int64_t ldy, const
   static_assert(INSTR % 4 == 0 && WR % RPP == 0 && XR % RPP == 0, "pieces must split over 4 waves, W/X unmixed");
   static_assert((S - 1) * PER_WAVE <= 63 && S >= 2, "vmcnt field is 6 bits");
   static_assert(S * SLOT <= 160 * 1024, "ring exceeds LDS");
+  static_assert(!P13 || (WR == p13::WR && KC == p13::KC && XR <= 32 && NT && (EPI == 0 || EPI == 4) &&
+                         p13::SIGN_PIECE0 % 4 == 0 && p13::W_PIECES % 4 == 0),
+                "P13: the (128, 128) tile at <= 32 rows, nt loads, bf16 / row-norm SiLU epilogues");
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ny = (int)(head >> HEAD_NY_SHIFT);
   const int ssp_tiles = (int)((head >> HEAD_TILES_SHIFT) & HEAD_TILES_MASK);
@@ -240,11 +256,20 @@ __device__ __forceinline__ void gd_body(char* smem, void* Yv, int64_t ldy, const
   // Per-lane source rows for this wave's DMA pieces (fixed across chunks).
   const bf16_t* src[PER_WAVE];
   bool isw[PER_WAVE];
-  const int64_t wstep = tiled ? (int64_t)(WR / RPP) * 512 : KC;  // W elements per K-chunk
+  const int64_t wstep = P13 ? p13::CHUNK_BYTES / 2 : (tiled ? (int64_t)(WR / RPP) * 512 : KC);  // W elements per K-chunk
   // piece p of chunk c; a piece is all-weight or all-activation rows: wave-uniform branch
   auto issue_piece = [&](int c, int p) {
     char* slot = smem + (c % S) * SLOT;
-    if (isw[p]) {
+    if constexpr (P13) {
+      // pieces wave + 4 p: p < 6 the low-byte and code planes (1 KiB), p < 8 the sign plane (256 B), then X
+      const int q = wave + 4 * p;
+      if (4 * p < p13::SIGN_PIECE0)
+        glds16<2>(src[p] + (int64_t)c * wstep, slot + q * 1024);
+      else if (4 * p < p13::W_PIECES)
+        glds4<2>(src[p] + (int64_t)c * wstep, slot + p13::SIGN_OFF + (q - p13::SIGN_PIECE0) * 256);
+      else
+        glds16<0>(src[p] + (int64_t)c * KC, slot + WIMG + (q - p13::W_PIECES) * 1024);
+    } else if (isw[p]) {
       if (NT)
         glds16<2>(src[p] + (int64_t)c * wstep, slot + (wave + 4 * p) * 1024);
       else
@@ -262,7 +287,9 @@ __device__ __forceinline__ void gd_body(char* smem, void* Yv, int64_t ldy, const
 #pragma unroll
   for (int p = 0; p < PER_WAVE; ++p) {
     const int piece = wave + 4 * p;
-    const int row = RPP * piece + lane / CPR;  // image row: [0, WR) = W, [WR, WR+XR) = X
+    // image row: [0, WR) = W, [WR, WR+XR) = X (P13: the weight pieces are planes, not rows)
+    const int row = P13 ? (4 * p < p13::W_PIECES ? 0 : WR + RPP * (piece - p13::W_PIECES) + lane / CPR)
+                        : RPP * piece + lane / CPR;
     const int lch = (lane % CPR) ^ swz<ROWB>(row);
     const bf16_t* base;
     if (row < WR) {
@@ -278,6 +305,11 @@ __device__ __forceinline__ void gd_body(char* smem, void* Yv, int64_t ldy, const
       // pre-packed weights (gd_pack_weights): tile bx's K-chunk c is WR/RPP contiguous 1-KiB pieces
       // already in LDS-image order (rows, swizzle and all), so each piece is one linear 1-KiB read
       src[p] = W + ((int64_t)bx * (K / KC) + k0 / KC) * (WR / RPP) * 512 + piece * 512 + lane * 8;
+    }
+    if constexpr (P13) {
+      if (4 * p < p13::W_PIECES)  // chunk (bx, c): CHUNK_BYTES contiguous; this lane's 16 (sign plane: 4) bytes of the piece
+        src[p] = W + ((int64_t)bx * (K / KC) + k0 / KC) * (p13::CHUNK_BYTES / 2) + p13::piece_off(piece) / 2 +
+                 lane * (4 * p < p13::SIGN_PIECE0 ? 8 : 2);
     }
     isw[p] = row < WR;
     if (nch > 0) issue_piece(0, p);
@@ -310,7 +342,7 @@ __device__ __forceinline__ void gd_body(char* smem, void* Yv, int64_t ldy, const
     }
     __builtin_amdgcn_s_barrier();
     const char* slot = smem + (c % S) * SLOT;
-    const char* ximg = slot + WR * ROWB;
+    const char* ximg = slot + WIMG;
 #pragma unroll
     for (int kk = 0; kk < KSW; ++kk) {
       const int ks = SPLIT == 0 ? wave * KSW + kk : kk;
@@ -321,10 +353,30 @@ __device__ __forceinline__ void gd_body(char* smem, void* Yv, int64_t ldy, const
         const int r = 16 * (SPLIT == 2 ? wave * MT + mt : mt) + fr;
         a[mt] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(ximg + r * ROWB + 16 * (lch ^ swz<ROWB>(r))));
       }
+      if constexpr (P13) {
+        // three lane-linear reads per plane group, then the 8 fragments rebuilt in registers (gd_p13.h)
+        const uint32_t base7 = (head >> HEAD_B7_SHIFT) & HEAD_B7_MASK;
+        uint4 lo[4], cd[2];
 #pragma unroll
-      for (int nt = 0; nt < NTW; ++nt) {
-        const int r = 16 * (SPLIT == 1 ? wave * NTW + nt : nt) + fr;
-        b[nt] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(slot + r * ROWB + 16 * (lch ^ swz<ROWB>(r))));
+        for (int j = 0; j < 4; ++j) lo[j] = *reinterpret_cast<const uint4*>(slot + p13::low_read_off(wave, j, lane));
+#pragma unroll
+        for (int q = 0; q < 2; ++q) cd[q] = *reinterpret_cast<const uint4*>(slot + p13::code_read_off(wave, q, lane));
+        const uint2 sg = *reinterpret_cast<const uint2*>(slot + p13::sign_read_off(wave, lane));
+#pragma unroll
+        for (int nt = 0; nt < NTW; ++nt) {
+          const uint32_t l0 = nt & 1 ? lo[nt / 2].z : lo[nt / 2].x, l1 = nt & 1 ? lo[nt / 2].w : lo[nt / 2].y;
+          const uint4 c4 = cd[nt / 4];
+          const uint32_t code = (nt & 3) == 0 ? c4.x : ((nt & 3) == 1 ? c4.y : ((nt & 3) == 2 ? c4.z : c4.w));
+          uint32_t o[4];
+          p13::unpack8(l0, l1, code, nt < 4 ? sg.x : sg.y, nt, base7, o);
+          b[nt] = __builtin_bit_cast(bf16x8, uint4{o[0], o[1], o[2], o[3]});
+        }
+      } else {
+#pragma unroll
+        for (int nt = 0; nt < NTW; ++nt) {
+          const int r = 16 * (SPLIT == 1 ? wave * NTW + nt : nt) + fr;
+          b[nt] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const uint4*>(slot + r * ROWB + 16 * (lch ^ swz<ROWB>(r))));
+        }
       }
 #pragma unroll
       for (int mt = 0; mt < MT; ++mt)
@@ -655,7 +707,7 @@ __device__ __forceinline__ void gd_body(char* smem, void* Yv, int64_t ldy, const
 // of the by-value struct. The first 14 dwords are therefore exactly what the entry reads before its first
 // LDS-DMA (W, X, ldx, K, M, N_out, the `head` word, fz.grp_off and fz.ssp_in, lifted out of fz by the launcher);
 // the outputs and the struct (epilogue operands) follow and are loaded from the kernarg segment as before.
-template <int WR, int EPI, int S, bool NT, int KC, int XR, int SKC = 0>
+template <int WR, int EPI, int S, bool NT, int KC, int XR, int SKC = 0, bool P13 = false>
 __global__ void __launch_bounds__(NTH) gemm_decode_kernel(const bf16_t* __restrict__ W, const bf16_t* __restrict__ X,
                                                           int64_t ldx, int K, int M, int N_out, uint32_t head,
                                                           const int* __restrict__ grp_off,
@@ -664,7 +716,7 @@ __global__ void __launch_bounds__(NTH) gemm_decode_kernel(const bf16_t* __restri
   extern __shared__ __attribute__((aligned(16))) char smem[];
   long long t0 = 0;
   if (head & HEAD_TS) t0 = __builtin_amdgcn_s_memrealtime();
-  gd_body<WR, EPI, S, NT, KC, XR, SKC>(smem, Yv, ldy, X, ldx, W, M, N_out, K, head, grp_off, ssp_in, fz, blockIdx.x,
+  gd_body<WR, EPI, S, NT, KC, XR, SKC, P13>(smem, Yv, ldy, X, ldx, W, M, N_out, K, head, grp_off, ssp_in, fz, blockIdx.x,
                                        blockIdx.y);
   if ((head & HEAD_TS) && threadIdx.x == 0) {  // diagnostics only (bench/micro_gd_timeline.py)
     const long long t1 = __builtin_amdgcn_s_memrealtime();
@@ -680,6 +732,25 @@ __global__ void __launch_bounds__(NTH) gemm_decode_kernel(const bf16_t* __restri
 // tile geometry (ring_slots, gd_lds, gd_valid, half_ring_slots): gd_tiles.h
 
 // launch (or, with fz.occupancy set, only report the resident workgroups per CU of) one instantiation
+// the P13 form (gd_p13.h) of one (epilogue, activation image): nt loads, no split-K, no groups; the same
+// activation image behind a 26-KiB weight image (the partials + scratch fit the ring as before)
+template <int EPI, int XR>
+static hipError_t launch_gd_p13(void* Y, int64_t ldy, const bf16_t* X, int64_t ldx, const bf16_t* W, int M, int N_out,
+                                int K, const GemmDecodeFuse& fz, hipStream_t s) {
+  constexpr int WR = p13::WR, KC = p13::KC, S = p13::RING_SLOTS;
+  constexpr size_t lds = (size_t)S * (p13::CHUNK_BYTES + XR * KC * 2);
+  static_assert(lds >= gd_lds(WR, XR, KC, 1) && lds <= RING_BYTES, "the epilogue's partials fit the P13 ring");
+  if (fz.occupancy != nullptr)
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(fz.occupancy,
+                                                        gemm_decode_kernel<WR, EPI, S, true, KC, XR, 0, true>, NTH, lds);
+  const dim3 grid(N_out / (EPI == 4 ? WR / 2 : WR), 1, 1);
+  const uint32_t head = (fz.ts != nullptr ? HEAD_TS : 0u) | ((uint32_t)(EPI == 4 ? fz.ssp_tiles : 0) << HEAD_TILES_SHIFT) |
+                        ((uint32_t)fz.p13_base7 << HEAD_B7_SHIFT) | (1u << HEAD_NY_SHIFT);
+  hipLaunchKernelGGL((gemm_decode_kernel<WR, EPI, S, true, KC, XR, 0, true>), grid, dim3(NTH), lds, s, W, X, ldx, K, M,
+                     N_out, head, fz.grp_off, fz.ssp_in, Y, ldy, fz);
+  return hipGetLastError();
+}
+
 template <int WR, int EPI, int S, int KC, int XR, int SKC>
 static hipError_t launch_gd_s(void* Y, int64_t ldy, const bf16_t* X, int64_t ldx, const bf16_t* W, int M, int N_out,
                               int K, int sk, bool nt, const GemmDecodeFuse& fz, hipStream_t s) {
@@ -711,6 +782,14 @@ static hipError_t launch_gd_xr(void* Y, int64_t ldy, const bf16_t* X, int64_t ld
   if constexpr (!gd_valid(WR, XR, KC)) {
     return hipErrorInvalidValue;
   } else {
+    if (fz.p13) {
+      // the lossless 13-bit weight stream (gd_p13.h): the (128, 128) tile at <= 32 rows, modes 0 and 4
+      // (launch_gemm_decode has refused nt = false, split-K and groups)
+      if constexpr (WR == p13::WR && KC == p13::KC && XR <= 32 && (EPI == 0 || EPI == 4) && SKC == 0)
+        return launch_gd_p13<EPI, XR>(Y, ldy, X, ldx, W, M, N_out, K, fz, s);
+      else
+        return hipErrorInvalidValue;
+    }
     if (fz.half_ring) {
       // mode 3 at <= 32 rows on the nt path only (the TP shard shapes): bounds the instantiations
       if constexpr (EPI == 3 && XR <= 32 && half_ring_slots(WR, XR, KC) >= 2 &&
@@ -794,6 +873,9 @@ hipError_t launch_gemm_decode(void* Y, int64_t ldy, const bf16_t* X, int64_t ldx
   // partner inside the row (wr = 48 / 96 / 112 would mix rows and straddle waves)
   if (fz.amax != nullptr && (wr % 8 || ((wr / 8) & (wr / 8 - 1)))) return hipErrorInvalidValue;
   if (fz.half_ring && (mode != 3 || M > 32)) return hipErrorInvalidValue;
+  if (fz.p13 && (wr != p13::WR || kc != p13::KC || (mode != 0 && mode != 4) || !nt || sk != 1 || M > 32 ||
+                 fz.half_ring || fz.grp_off != nullptr || fz.p13_base7 < 0 || fz.p13_base7 > 112))
+    return hipErrorInvalidValue;  // P13 weights: one tile, two epilogues, the 32-row bucket
   if ((mode == 4 || mode == 6) &&
       (fz.ssp_in == nullptr || fz.ssp_tiles < 1 ||
        fz.ssp_tiles > (M <= 32 ? DECODE_SSP_MAX_TILES : DECODE_SSP_MAX_TILES_WIDE)))

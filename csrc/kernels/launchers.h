@@ -271,6 +271,10 @@ struct GemmDecodeFuse {
   // mode 3 at <= 32 rows: a ring of <= 76 KiB so that two workgroups are resident per CU (gemm_decode.hip
   // half_ring_slots) — the TP exchange's co-residency margin at one-workgroup-per-CU grids
   int half_ring = 0;
+  // modes 0 / 4, tile (128, 128), <= 32 rows, nt: W is the lossless 13-bit "P13" form of the tile-order weights
+  // (gd_p13.h; 13/16 of the bytes, the same result bit for bit) with this per-tensor exponent base
+  int p13 = 0;
+  int p13_base7 = 0;
   // query only: no launch; *occupancy = resident workgroups per CU of the instantiation this call would launch
   int* occupancy = nullptr;
 };

@@ -123,6 +123,10 @@ class LLMEngine:
                 model.tiled_decode_weights = False
             if model.pack_decode_weights(buckets):
                 self.decode_weight_layout = "tiled"
+            p13 = getattr(model, "p13_stats", None)
+            if p13 and (p13["packed"] or p13["raw"]):
+                logger.info("decode weights: %d tensors in the 13-bit layout, %d kept in tile order", p13["packed"],
+                            p13["raw"])
             logger.info("decode weights: %s (%s)", self.decode_weight_layout,
                         f"+{model.decode_copy_bytes(buckets) / 2**30:.1f} GiB of tile-order copies"
                         if self.decode_weight_layout == "tiled" else "one copy, HBM left to the KV pool")
@@ -757,6 +761,9 @@ class LLMEngine:
         s["kv_pool_gib"] = self.pool.nbytes / 2**30
         s["graphs"] = list(self.runner.graph_sizes)
         s["decode_weight_layout"] = self.decode_weight_layout
+        # decode weight tensors streamed in the lossless 13-bit layout / kept in tile order (outside its window)
+        p13 = getattr(self.model, "p13_stats", None) or {"packed": 0, "raw": 0}
+        s["p13_tensors_packed"], s["p13_tensors_raw"] = p13["packed"], p13["raw"]
         s["logprob_launches"] = getattr(self.runner, "logprob_launches", 0)  # ops.token_logprobs launches
         s["logit_process_launches"] = getattr(self.runner, "logit_process_launches", 0)  # ops.logit_process
         s["token_guide_launches"] = getattr(self.runner, "token_guide_launches", 0)  # ops.token_guide

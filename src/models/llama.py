@@ -21,6 +21,7 @@ The same module runs CPU tensors through :mod:`src.ops.reference` for tests.
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass
 from typing import Callable, Dict, List, Optional
 
@@ -121,6 +122,10 @@ class CausalLM:
         self.sequence_parallel = bool(sequence_parallel and self.tp.enabled)
         self.tiled_decode_weights = True  # decode GEMMs on tile-order copies (pack_decode_weights)
         self.lm_head_tile = None          # (wr, kc) once the LM head is re-laid in place in tile order
+        # the 32-row bucket's gate/up decode copy in the lossless 13-bit layout (ops.gd_pack_weights_p13) where its
+        # tile is (128, 128) and the tensor's exponents fit the window; DIE_P13=0 keeps the tile-order copy (A/B)
+        self.p13_weights = os.environ.get("DIE_P13", "1") != "0"
+        self.p13_stats = {"packed": 0, "raw": 0}  # tensors packed / kept in tile order (outside the window)
         self.prefill_gemm_residual = True  # TP=1 prefill: o / down add into the residual in the GEMM (beta = 1)
         self.layers: List[LayerWeights] = []
         self._init_random(seed, init_std)
@@ -260,6 +265,7 @@ class CausalLM:
         False while streaming several files, then call :meth:`fold_norm_weights` once)."""
         for lw in self.layers:  # decode tile-order copies go stale: re-packed by alloc_decode_scratch
             lw.tiled = {}
+        self.p13_stats = {"packed": 0, "raw": 0}
         if self.lm_head_tile is not None:  # back to row-major for the checkpoint's rows (re-packed likewise)
             self.lm_head.copy_(self.lm_head_rows())
             self.lm_head_tile = None
@@ -723,12 +729,34 @@ class CausalLM:
         total = torch.cuda.get_device_properties(self.device).total_memory
         if self.weight_bytes() + extra > total // 2:
             return False
+        p13 = self._p13_layout(buckets)
+        # the tile-order copy of the P13 tensor is still made where another row bucket streams the same tile
+        p13_only = p13 is not None and p13 not in self._packed_layouts([b for b in buckets if b != 32])
         for lw in self.layers:
             for name, wr, kc in need:
+                if (name, wr, kc) == p13 and (name, wr, kc, "p13") not in lw.tiled and (name, wr, kc) not in lw.tiled:
+                    packed = ops.gd_pack_weights_p13(getattr(lw, name), wr, kc, silu=name == "gate_up")
+                    self.p13_stats["packed" if packed is not None else "raw"] += 1
+                    if packed is not None:  # else: outside the window, this tensor keeps the tile order
+                        lw.tiled[(name, wr, kc, "p13")] = packed
+                if p13_only and (name, wr, kc, "p13") in lw.tiled:
+                    continue
                 if (name, wr, kc) not in lw.tiled:
                     lw.tiled[(name, wr, kc)] = ops.gd_pack_weights(getattr(lw, name), wr, silu=name == "gate_up",
                                                                    kc=kc)
+        if p13 is not None:
+            torch.cuda.empty_cache()  # the packing transients, before the KV pool is sized
         return True
+
+    def _p13_layout(self, buckets):
+        """("gate_up", 128, 128) when the 32-row bucket's gate/up streams the P13 layout: its plan's tile is the
+        one with a P13 kernel, full-K, on one GPU; else None."""
+        if not self.p13_weights or 32 not in buckets or self.tp.enabled or self.arch.is_moe:
+            return None
+        p = self.decode_plan(32)
+        if p["gate_up"] is None or tuple(p["gate_up"]) != ops.P13_TILE or p["gate_up_sk"] != 1:
+            return None
+        return ("gate_up", *ops.P13_TILE)
 
     def _decode_copy_plan(self, buckets):
         """(tile layouts, bytes) of the tile-order decode weight copies these row buckets would use."""
@@ -741,6 +769,11 @@ class CausalLM:
 
         need = {t for t in self._packed_layouts(buckets) if tiles(*t)}
         extra = sum(getattr(lw0, name).numel() * lw0.qkv.element_size() for name, _, _ in need) * len(self.layers)
+        p13 = self._p13_layout(buckets)
+        if p13 in need:  # 13/16 of the bytes, unless another bucket keeps the tile-order copy beside it
+            n = getattr(lw0, p13[0]).numel() * lw0.qkv.element_size() * len(self.layers)
+            extra += (n * ops.P13_NUM // ops.P13_DEN if p13 in self._packed_layouts([b for b in buckets if b != 32])
+                      else -(n * (ops.P13_DEN - ops.P13_NUM) // ops.P13_DEN))
         return need, extra
 
     def decode_copy_bytes(self, buckets) -> int:
@@ -844,6 +877,10 @@ class CausalLM:
                 wg, kg = plan["gate_up"]
                 gsk = plan.get("gate_up_sk", 1)
                 wgu, tg = tw(lw, "gate_up", wg, kg)
+                b7 = None  # <= 32 rows: the P13 copy where this tensor has one
+                pk = lw.tiled.get(("gate_up", wg, kg, "p13")) if h.shape[0] <= 32 and gsk == 1 else None
+                if pk is not None:
+                    wgu, b7 = pk
                 if self.tp.enabled and plan["tp_fused"]:
                     # row-parallel GEMM + one-shot all-reduce + residual + statistics: one launch each
                     wdn_, kd, sd = plan["down"]
@@ -867,7 +904,7 @@ class CausalLM:
                     wd_t, td_ = tw(lw, "down", wdn_, kd)
                     ops.linear_slab_residual(attn, wo_t, h, ssp_a, sc["cnt_a"], wo, so, tiled=to_, kc=ko)
                     act = ops.linear_silu_mul_rownorm(h, wgu, ssp_a, eps, wg, tiled=tg, kc=kg, sk=gsk,
-                                                      slab=sc["slab6"], counters=sc["cnt6"])
+                                                      slab=sc["slab6"], counters=sc["cnt6"], p13_base7=b7)
                     ops.linear_slab_residual(act, wd_t, h, ssp_b, sc["cnt_b"], wdn_, sd, tiled=td_, kc=kd)
             ssp_prev = ssp_b
         return ops.rms_norm(h, self.norm, eps)

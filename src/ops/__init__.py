@@ -15,9 +15,11 @@ import torch
 from . import reference as ref
 # the decode GEMM's mode word, tiles, measured table and lookup: one module, re-exported for the callers of ops
 from .decode_tiles import (DECODE_GEMM_MAX_M, DECODE_TILE_CFG, HALF_RING, MODE_BF16, MODE_MASK, MODE_RESID, MODE_SILU,
-                           MODE_SILU_NORM, MODE_SILU_NORM_SK, MODE_SLAB, SSP_LD, SSP_MAX_TILES, SSP_MAX_TILES_WIDE,
-                           TILED, _tile_overrides, decode_bucket, decode_tile, decode_tile_silu, gd_tile,
-                           gd_tile_valid, moe_decode_tiles)
+                           MODE_SILU_NORM, MODE_SILU_NORM_SK, MODE_SLAB, P13, P13_BASE_SHIFT, SSP_LD, SSP_MAX_TILES,
+                           SSP_MAX_TILES_WIDE, TILED, _tile_overrides, decode_bucket, decode_tile, decode_tile_silu,
+                           gd_tile, gd_tile_valid, moe_decode_tiles)
+# the lossless 13-bit weight layout of the (128, 128) tile: packer and exact inverse (pure torch)
+from .p13 import P13_DEN, P13_NUM, P13_TILE, gd_pack_weights_p13, gd_unpack_weights_p13, p13_base7
 
 _C = None
 _C_ERR: Optional[BaseException] = None
@@ -506,12 +508,13 @@ def gemm_decode(x: torch.Tensor, w: torch.Tensor, mode: int = 0, wr: int = 64, s
                 out: Optional[torch.Tensor] = None, nt: Optional[bool] = None, kc: Optional[int] = None) -> torch.Tensor:
     """Raw access to the decode GEMM kernel (see csrc/kernels/gemm_decode.hip).
     ``mode``: a decode_tiles.MODE_* epilogue (MODE_BF16: bf16 x@w^T; MODE_SILU: bf16 silu(gate)*up, w = [gate; up];
-    MODE_SLAB: fp32 split-K slabs [sk, M, N]), | TILED for a w packed by gd_pack_weights. ``(wr, kc)``: the
-    workgroup tile (:func:`gd_tile`)."""
+    MODE_SLAB: fp32 split-K slabs [sk, M, N]), | TILED for a w packed by gd_pack_weights, or :func:`p13_mode`'s
+    flags for one packed by gd_pack_weights_p13. ``(wr, kc)``: the workgroup tile (:func:`gd_tile`)."""
     m = x.shape[0]
     wr, kc = gd_tile(wr, kc)
     base = mode & MODE_MASK
-    n = w.shape[0] // 2 if base == MODE_SILU else w.shape[0]
+    rows = w.shape[0] * P13_DEN // P13_NUM if mode & P13 else w.shape[0]
+    n = rows // 2 if base == MODE_SILU else rows
     if out is None:
         if base == MODE_SLAB:
             out = torch.empty(sk, m, n, dtype=torch.float32, device=x.device)
@@ -520,6 +523,11 @@ def gemm_decode(x: torch.Tensor, w: torch.Tensor, mode: int = 0, wr: int = 64, s
     e = _empty(x.device)
     _kern().gemm_decode(out, x, w, mode, wr, kc, sk, DECODE_GEMM_NT if nt is None else nt, e, e, e, e, 0.0)
     return out
+
+
+def p13_mode(base7: int) -> int:
+    """The mode-word flags of a weight packed by gd_pack_weights_p13 with this base7."""
+    return P13 | (int(base7) << P13_BASE_SHIFT)
 
 
 def gd_swizzle(r: torch.Tensor, kc: int) -> torch.Tensor:
@@ -614,12 +622,20 @@ def gd_occupancy(mode: int, wr: int, kc: int, sk: int, rows: int, half_ring: boo
 
 def linear_silu_mul_rownorm(x: torch.Tensor, w_gate_up: torch.Tensor, ssp_in: torch.Tensor, eps: float,
                             wr: Optional[int] = None, tiled: bool = False, kc: Optional[int] = None, sk: int = 1,
-                            slab: Optional[torch.Tensor] = None,
-                            counters: Optional[torch.Tensor] = None) -> torch.Tensor:
+                            slab: Optional[torch.Tensor] = None, counters: Optional[torch.Tensor] = None,
+                            p13_base7: Optional[int] = None) -> torch.Tensor:
     """silu(r * x @ gate^T) * (r * x @ up^T) with r = rsqrt(sum_t ssp_in[t] / K + eps) per row:
     RMSNorm (weight folded into w_gate_up) + gate/up + SiLU*mul in one weight stream. sk > 1 (MODE_SILU_NORM_SK): K
     split over sk workgroups per tile with fp32 partials in ``slab`` (>= sk * rows * 2N floats) and the tile's
-    last arriver finishing (``counters``: >= N / (wr / 2) int32, zero; re-armed by the kernel)."""
+    last arriver finishing (``counters``: >= N / (wr / 2) int32, zero; re-armed by the kernel). ``p13_base7``:
+    w_gate_up is the P13 form (gd_pack_weights_p13) with this base — tile (128, 128), <= 32 rows, sk = 1."""
+    if p13_base7 is not None:
+        n = w_gate_up.shape[0] * P13_DEN // P13_NUM // 2
+        out = torch.empty(x.shape[0], n, dtype=x.dtype, device=x.device)
+        e = _empty(x.device)
+        _kern().gemm_decode(out, x, w_gate_up, MODE_SILU_NORM | p13_mode(p13_base7), *P13_TILE, 1, True, e, e, e,
+                            ssp_in, float(eps))
+        return out
     n = w_gate_up.shape[0] // 2
     if wr is None:
         wr, kc, _ = decode_tile(n, x.shape[1], MODE_SILU_NORM, decode_bucket(x.shape[0]))
@@ -703,7 +719,14 @@ def linear_tiled_argmax(x: torch.Tensor, w: torch.Tensor, wr: int, kc: int, amax
     """linear_tiled that also writes every wr-column tile's per-row greedy candidate (max of the bf16 outputs,
     lowest column on ties) into amax [M, N / wr, 2] int32 — the LM head's share of a decode step's argmax."""
     out = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)
-    _kern().gemm_decode_argmax(out, x, w, wr, kc, True, amax)
+    _kern().gemm_decode_argmax(out, x, w, wr, kc, 1, amax)
+    return out
+
+
+def linear_p13_argmax(x: torch.Tensor, w: torch.Tensor, base7: int, amax: torch.Tensor) -> torch.Tensor:
+    """:func:`linear_tiled_argmax` on a weight packed by gd_pack_weights_p13 (tile (128, 128), <= 32 rows)."""
+    out = torch.empty(x.shape[0], w.shape[0] * P13_DEN // P13_NUM, dtype=x.dtype, device=x.device)
+    _kern().gemm_decode_argmax(out, x, w, *P13_TILE, p13_mode(base7), amax)
     return out
 
 

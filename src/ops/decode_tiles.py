@@ -21,6 +21,8 @@ MODE_SILU_NORM_SK = 6  # MODE_SILU_NORM split over sk K slices, the tile's last 
 MODE_MASK = 31
 TILED = 32             # flag: w in tile order (ops.gd_pack_weights)
 HALF_RING = 64         # flag: half-LDS ring, two workgroups per CU (MODE_RESID at <= 32 rows)
+P13 = 128              # flag: w in the lossless 13-bit layout (ops.gd_pack_weights_p13): tile (128, 128), <= 32 rows,
+P13_BASE_SHIFT = 8     # MODE_BF16 / MODE_SILU_NORM, nt loads; the tensor's base7 rides in mode bits 8..14
 
 DECODE_GEMM_MAX_M = 128   # weight-streaming decode GEMM / fused decode path (gemm_decode.hip)
 SSP_LD = 128              # row stride of the norm-statistics arrays [tiles, SSP_LD]
