@@ -1273,7 +1273,7 @@ void car_all_reduce_residual(Tensor x, Tensor resid, Tensor ssp, int64_t rank, s
   TORCH_CHECK(x.dim() == 2 && resid.sizes() == x.sizes(), "x and resid must both be [rows, hidden]");
   const int64_t rows = x.size(0), hidden = x.size(1);
   TORCH_CHECK(hidden % 8 == 0 && rows <= die::CAR_MAX_BLOCKS && rows * hidden <= cap_elems,
-              "all_reduce_residual: hidden % 8, rows <= 64, size <= cap");
+              "all_reduce_residual: hidden % 8, rows <= 256 (one flag slot per row), size <= cap");
   TORCH_CHECK(ssp.numel() >= rows, "ssp too small");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(x.data_ptr()) % 16 == 0 &&
                   reinterpret_cast<uintptr_t>(resid.data_ptr()) % 16 == 0, "16-byte alignment");

@@ -115,7 +115,7 @@ __global__ void __launch_bounds__(car::NTH) custom_all_reduce_kernel(const bf16_
 // Fused variant for the tensor-parallel decode layer: the row-parallel projection's partial sums are
 // all-reduced AND added into the residual stream, and the new residual's per-row sums of squares (the
 // next RMSNorm's statistics, consumed as a row scale by the gate/up or qkv kernels) are written — what
-// all_reduce + residual_add_sumsq did in two launches. One workgroup per row (M <= 64 decode rows), so
+// all_reduce + residual_add_sumsq did in two launches. One workgroup per row (at most CAR_MAX_BLOCKS rows), so
 // each row's statistics come from one deterministic block reduction. Same protocol as above.
 __global__ void __launch_bounds__(car::NTH) custom_all_reduce_residual_kernel(
     const bf16_t* __restrict__ in, bf16_t* __restrict__ resid, float* __restrict__ ssp, int hidden, int rank,

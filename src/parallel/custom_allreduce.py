@@ -141,7 +141,8 @@ class CustomAllReduce:
 
     def all_reduce_residual(self, x: torch.Tensor, resid: torch.Tensor, ssp: torch.Tensor) -> None:
         """resid += sum over the group of x (bf16, in place), ssp[row] = that row's sum of squares of the
-        new residual — all-reduce and residual_add_sumsq in one launch (decode rows, <= 64)."""
+        new residual — all-reduce and residual_add_sumsq in one launch. One workgroup and one flag slot per row:
+        the launcher takes up to SIG_BLOCKS (256) rows; can_run_residual routes decode steps of <= 64 rows here."""
         _kern().car_all_reduce_residual(x, resid, ssp, self.rank, self.bufs, self.sigs, self.ctl, self.cap)
 
     def fused_ok(self, n_tiles: int, grid: int = 0, per_cu: int = 0) -> bool:
