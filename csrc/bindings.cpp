@@ -385,6 +385,18 @@ void token_logprobs(Tensor lp, Tensor rank, Tensor top_lp, Tensor top_id, Tensor
                                      (int)std::min<int64_t>(std::max<int64_t>(top_n, -1), 1 << 20), cur_stream()));
 }
 
+// lm_part int32 [>= rows, parts, 2], optional: the LM-head candidates that logit_process and the guide ops rewrite.
+// Returns its pointer (null without one) and the parts; op names the op in the message.
+static uint32_t* lm_part_arg(const char* op, int64_t rows, const c10::optional<Tensor>& lm_part, int* lparts) {
+  *lparts = 0;
+  if (!lm_part.has_value()) return nullptr;
+  TORCH_CHECK(lm_part->is_cuda() && lm_part->scalar_type() == at::kInt && lm_part->dim() == 3 &&
+                  lm_part->size(0) >= rows && lm_part->size(2) == 2 && lm_part->is_contiguous(),
+              op, ": lm_part [rows, parts, 2] int32");
+  *lparts = (int)lm_part->size(1);
+  return reinterpret_cast<uint32_t*>(lm_part->data_ptr<int>());
+}
+
 // Penalties and logit_bias on logits [rows, vocab] in place (logit_process.hip). slot int32 [>= rows]; state int16
 // [slots, vocab] (the kernel reads it as uint16); params fp32 [slots, 4]; bias_cnt int32 [slots]; bias_ids int32 /
 // bias_vals fp32 [slots, cap]; count_ids int64 [>= rows] and lm_part int32 [>= rows, parts, 2] optional. The
@@ -417,223 +429,134 @@ void logit_process(Tensor logits, Tensor slot, Tensor state, Tensor params, Tens
                     count_ids->numel() >= rows, "logit_process: count_ids int64 [rows]");
     cp = count_ids->data_ptr<int64_t>();
   }
-  uint32_t* lp = nullptr;
   int lparts = 0;
-  if (lm_part.has_value()) {
-    TORCH_CHECK(lm_part->is_cuda() && lm_part->scalar_type() == at::kInt && lm_part->dim() == 3 &&
-                    lm_part->size(0) >= rows && lm_part->size(2) == 2 && lm_part->is_contiguous(),
-                "logit_process: lm_part [rows, parts, 2] int32");
-    lp = reinterpret_cast<uint32_t*>(lm_part->data_ptr<int>());
-    lparts = (int)lm_part->size(1);
-  }
+  uint32_t* lp = lm_part_arg("logit_process", rows, lm_part, &lparts);
   HIP_OK(die::launch_logit_process(bf(logits), logits.stride(0), (int)rows, (int)vocab, slot.data_ptr<int>(),
                                     (int)slots, slots ? reinterpret_cast<uint16_t*>(state.data_ptr<int16_t>()) : nullptr,
                                     params.data_ptr<float>(), bias_cnt.data_ptr<int>(), bias_ids.data_ptr<int>(),
                                     bias_vals.data_ptr<float>(), (int)bias_ids.size(1), cp, lp, lparts, cur_stream()));
 }
 
-// Constrained decoding on logits [rows, vocab] in place (token_guide.hip). slot int32 [>= rows]; desc int32 [slots,
-// 4]; rowptr int32 [R]; edges int32 [E, 2]; cur / err int32 [slots]; advance_ids int64 [>= rows] and lm_part int32
-// [>= rows, parts, 2] optional. The launcher itself refuses vocab % 8 != 0, a bad stride and oversized arenas.
-void token_guide(Tensor logits, Tensor slot, Tensor desc, Tensor rowptr, Tensor edges, Tensor cur, Tensor err,
-                 c10::optional<Tensor> advance_ids, c10::optional<Tensor> lm_part) {
+// What the four guide ops check alike; op names the op in the messages. The launchers themselves refuse vocab % 8
+// != 0, a bad stride, null tables and oversized arenas.
+struct GuideArgs {
+  int64_t rows, vocab, slots;
+  const int64_t* ap;  // advance_ids, or null
+  uint32_t* lp;       // lm_part, or null
+  int lparts;
+};
+
+// logits bf16 [rows, vocab] (16-B aligned); slot int32 [>= rows]; desc int32 [slots, 4]; cur / err int32 [slots];
+// advance_ids int64 [>= rows] and lm_part int32 [>= rows, parts, 2] optional
+static GuideArgs guide_args(const char* op, const Tensor& logits, const Tensor& slot, const Tensor& desc,
+                            const Tensor& cur, const Tensor& err, const c10::optional<Tensor>& advance_ids,
+                            const c10::optional<Tensor>& lm_part) {
   CHK_CUDA(logits);
   CHK_BF16(logits);
   check_rows(logits, "logits");
-  const int64_t rows = logits.size(0), vocab = logits.size(1);
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0, "token_guide: logits must be 16-B aligned");
-  TORCH_CHECK(slot.is_cuda() && slot.scalar_type() == at::kInt && slot.is_contiguous() && slot.numel() >= rows,
-              "token_guide: slot int32 [rows]");
+  GuideArgs g{logits.size(0), logits.size(1), 0, nullptr, nullptr, 0};
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0, op, ": logits must be 16-B aligned");
+  TORCH_CHECK(slot.is_cuda() && slot.scalar_type() == at::kInt && slot.is_contiguous() && slot.numel() >= g.rows, op,
+              ": slot int32 [rows]");
   TORCH_CHECK(desc.is_cuda() && desc.scalar_type() == at::kInt && desc.is_contiguous() && desc.dim() == 2 &&
                   desc.size(1) == 4 && reinterpret_cast<uintptr_t>(desc.data_ptr()) % 16 == 0,
-              "token_guide: desc int32 [slots, 4]");
-  const int64_t slots = desc.size(0);
+              op, ": desc int32 [slots, 4]");
+  g.slots = desc.size(0);
+  TORCH_CHECK(cur.is_cuda() && cur.scalar_type() == at::kInt && cur.is_contiguous() && cur.numel() >= g.slots &&
+                  err.is_cuda() && err.scalar_type() == at::kInt && err.is_contiguous() && err.numel() >= g.slots,
+              op, ": cur / err int32 [slots]");
+  if (advance_ids.has_value()) {
+    TORCH_CHECK(advance_ids->is_cuda() && advance_ids->scalar_type() == at::kLong && advance_ids->is_contiguous() &&
+                    advance_ids->numel() >= g.rows, op, ": advance_ids int64 [rows]");
+    g.ap = advance_ids->data_ptr<int64_t>();
+  }
+  g.lp = lm_part_arg(op, g.rows, lm_part, &g.lparts);
+  return g;
+}
+
+// the vocabulary's byte table of the byte guides: tok_off int32 [n_tok + 1]; tok_bytes uint8 [B]
+static void guide_tok_table(const char* op, const Tensor& tok_off, const Tensor& tok_bytes) {
+  TORCH_CHECK(tok_off.is_cuda() && tok_off.scalar_type() == at::kInt && tok_off.is_contiguous() && tok_off.dim() == 1,
+              op, ": tok_off int32 [n_tok + 1]");
+  TORCH_CHECK(tok_bytes.is_cuda() && tok_bytes.scalar_type() == at::kByte && tok_bytes.is_contiguous() &&
+                  tok_bytes.dim() == 1, op, ": tok_bytes uint8 [B]");
+}
+
+// Constrained decoding on logits [rows, vocab] in place (token_guide.hip). desc int32 [slots, 4]; rowptr int32 [R];
+// edges int32 [E, 2]; the rest as guide_args takes it.
+void token_guide(Tensor logits, Tensor slot, Tensor desc, Tensor rowptr, Tensor edges, Tensor cur, Tensor err,
+                 c10::optional<Tensor> advance_ids, c10::optional<Tensor> lm_part) {
+  const GuideArgs g = guide_args("token_guide", logits, slot, desc, cur, err, advance_ids, lm_part);
   TORCH_CHECK(rowptr.is_cuda() && rowptr.scalar_type() == at::kInt && rowptr.is_contiguous() && rowptr.dim() == 1,
               "token_guide: rowptr int32 [R]");
   TORCH_CHECK(edges.is_cuda() && edges.scalar_type() == at::kInt && edges.is_contiguous() && edges.dim() == 2 &&
                   edges.size(1) == 2 && reinterpret_cast<uintptr_t>(edges.data_ptr()) % 8 == 0,
               "token_guide: edges int32 [E, 2]");
-  TORCH_CHECK(cur.is_cuda() && cur.scalar_type() == at::kInt && cur.is_contiguous() && cur.numel() >= slots &&
-                  err.is_cuda() && err.scalar_type() == at::kInt && err.is_contiguous() && err.numel() >= slots,
-              "token_guide: cur / err int32 [slots]");
-  const int64_t* ap = nullptr;
-  if (advance_ids.has_value()) {
-    TORCH_CHECK(advance_ids->is_cuda() && advance_ids->scalar_type() == at::kLong && advance_ids->is_contiguous() &&
-                    advance_ids->numel() >= rows, "token_guide: advance_ids int64 [rows]");
-    ap = advance_ids->data_ptr<int64_t>();
-  }
-  uint32_t* lp = nullptr;
-  int lparts = 0;
-  if (lm_part.has_value()) {
-    TORCH_CHECK(lm_part->is_cuda() && lm_part->scalar_type() == at::kInt && lm_part->dim() == 3 &&
-                    lm_part->size(0) >= rows && lm_part->size(2) == 2 && lm_part->is_contiguous(),
-                "token_guide: lm_part [rows, parts, 2] int32");
-    lp = reinterpret_cast<uint32_t*>(lm_part->data_ptr<int>());
-    lparts = (int)lm_part->size(1);
-  }
-  HIP_OK(die::launch_token_guide(bf(logits), logits.stride(0), (int)rows, (int)vocab, slot.data_ptr<int>(), (int)slots,
-                                  desc.data_ptr<int>(), rowptr.data_ptr<int>(), rowptr.numel(), edges.data_ptr<int>(),
-                                  edges.size(0), cur.data_ptr<int>(), err.data_ptr<int>(), ap, lp, lparts,
-                                  cur_stream()));
+  HIP_OK(die::launch_token_guide(bf(logits), logits.stride(0), (int)g.rows, (int)g.vocab, slot.data_ptr<int>(),
+                                  (int)g.slots, desc.data_ptr<int>(), rowptr.data_ptr<int>(), rowptr.numel(),
+                                  edges.data_ptr<int>(), edges.size(0), cur.data_ptr<int>(), err.data_ptr<int>(), g.ap,
+                                  g.lp, g.lparts, cur_stream()));
 }
 
-// Constrained decoding over a multi-byte vocabulary on logits [rows, vocab] in place (byte_guide.hip). slot int32
-// [>= rows]; desc int32 [slots, 4] = (state_base, n_states, eos, 0); trans int16 [A, 256]; accept uint8 [A];
-// tok_off int32 [n_tok + 1]; tok_bytes uint8 [B]; cur / err int32 [slots] (token_guide's); advance_ids int64
-// [>= rows] and lm_part int32 [>= rows, parts, 2] optional. The launcher itself refuses vocab % 8 != 0, a bad
-// stride, null tables and oversized arenas.
+// Constrained decoding over a multi-byte vocabulary on logits [rows, vocab] in place (byte_guide.hip). desc int32
+// [slots, 4] = (state_base, n_states, eos, 0); trans int16 [A, 256]; accept uint8 [A]; tok_off / tok_bytes as
+// guide_tok_table takes them; cur / err are token_guide's.
 void byte_guide(Tensor logits, Tensor slot, Tensor desc, Tensor trans, Tensor accept, Tensor tok_off, Tensor tok_bytes,
                 Tensor cur, Tensor err, c10::optional<Tensor> advance_ids, c10::optional<Tensor> lm_part) {
-  CHK_CUDA(logits);
-  CHK_BF16(logits);
-  check_rows(logits, "logits");
-  const int64_t rows = logits.size(0), vocab = logits.size(1);
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0, "byte_guide: logits must be 16-B aligned");
-  TORCH_CHECK(slot.is_cuda() && slot.scalar_type() == at::kInt && slot.is_contiguous() && slot.numel() >= rows,
-              "byte_guide: slot int32 [rows]");
-  TORCH_CHECK(desc.is_cuda() && desc.scalar_type() == at::kInt && desc.is_contiguous() && desc.dim() == 2 &&
-                  desc.size(1) == 4 && reinterpret_cast<uintptr_t>(desc.data_ptr()) % 16 == 0,
-              "byte_guide: desc int32 [slots, 4]");
-  const int64_t slots = desc.size(0);
+  const GuideArgs g = guide_args("byte_guide", logits, slot, desc, cur, err, advance_ids, lm_part);
   TORCH_CHECK(trans.is_cuda() && trans.scalar_type() == at::kShort && trans.is_contiguous() && trans.dim() == 2 &&
                   trans.size(1) == 256, "byte_guide: trans int16 [A, 256]");
   TORCH_CHECK(accept.is_cuda() && accept.scalar_type() == at::kByte && accept.is_contiguous() && accept.dim() == 1,
               "byte_guide: accept uint8 [A]");
-  TORCH_CHECK(tok_off.is_cuda() && tok_off.scalar_type() == at::kInt && tok_off.is_contiguous() && tok_off.dim() == 1,
-              "byte_guide: tok_off int32 [n_tok + 1]");
-  TORCH_CHECK(tok_bytes.is_cuda() && tok_bytes.scalar_type() == at::kByte && tok_bytes.is_contiguous() &&
-                  tok_bytes.dim() == 1, "byte_guide: tok_bytes uint8 [B]");
-  TORCH_CHECK(cur.is_cuda() && cur.scalar_type() == at::kInt && cur.is_contiguous() && cur.numel() >= slots &&
-                  err.is_cuda() && err.scalar_type() == at::kInt && err.is_contiguous() && err.numel() >= slots,
-              "byte_guide: cur / err int32 [slots]");
-  const int64_t* ap = nullptr;
-  if (advance_ids.has_value()) {
-    TORCH_CHECK(advance_ids->is_cuda() && advance_ids->scalar_type() == at::kLong && advance_ids->is_contiguous() &&
-                    advance_ids->numel() >= rows, "byte_guide: advance_ids int64 [rows]");
-    ap = advance_ids->data_ptr<int64_t>();
-  }
-  uint32_t* lp = nullptr;
-  int lparts = 0;
-  if (lm_part.has_value()) {
-    TORCH_CHECK(lm_part->is_cuda() && lm_part->scalar_type() == at::kInt && lm_part->dim() == 3 &&
-                    lm_part->size(0) >= rows && lm_part->size(2) == 2 && lm_part->is_contiguous(),
-                "byte_guide: lm_part [rows, parts, 2] int32");
-    lp = reinterpret_cast<uint32_t*>(lm_part->data_ptr<int>());
-    lparts = (int)lm_part->size(1);
-  }
-  HIP_OK(die::launch_byte_guide(bf(logits), logits.stride(0), (int)rows, (int)vocab, slot.data_ptr<int>(), (int)slots,
-                                 desc.data_ptr<int>(), trans.data_ptr<int16_t>(), trans.size(0),
+  guide_tok_table("byte_guide", tok_off, tok_bytes);
+  HIP_OK(die::launch_byte_guide(bf(logits), logits.stride(0), (int)g.rows, (int)g.vocab, slot.data_ptr<int>(),
+                                 (int)g.slots, desc.data_ptr<int>(), trans.data_ptr<int16_t>(), trans.size(0),
                                  accept.data_ptr<uint8_t>(), accept.numel(), tok_off.data_ptr<int>(),
                                  tok_off.numel() - 1, tok_bytes.data_ptr<uint8_t>(), tok_bytes.numel(),
-                                 cur.data_ptr<int>(), err.data_ptr<int>(), ap, lp, lparts, cur_stream()));
+                                 cur.data_ptr<int>(), err.data_ptr<int>(), g.ap, g.lp, g.lparts, cur_stream()));
 }
 
-// JSON mode on logits [rows, vocab] in place (json_guide.hip). slot int32 [>= rows]; desc int32 [slots, 4] =
-// (n_states, done, eos, 0); trans int16 [S, 256], the pushdown table; tok_off / tok_bytes: byte_guide's tables; cur /
-// err int32 [slots] (token_guide's); jstk int32 [slots, 2] = (depth, stack bits); advance_ids and lm_part optional.
-// The launcher itself refuses vocab % 8 != 0, a bad stride, null tables and an oversized table.
+// JSON mode on logits [rows, vocab] in place (json_guide.hip). desc int32 [slots, 4] = (n_states, done, eos, 0); trans
+// int16 [S, 256], the pushdown table; tok_off / tok_bytes: byte_guide's tables; cur / err are token_guide's; jstk
+// int32 [slots, 2] = (depth, stack bits).
 void json_guide(Tensor logits, Tensor slot, Tensor desc, Tensor trans, Tensor tok_off, Tensor tok_bytes, Tensor cur,
                 Tensor jstk, Tensor err, c10::optional<Tensor> advance_ids, c10::optional<Tensor> lm_part) {
-  CHK_CUDA(logits);
-  CHK_BF16(logits);
-  check_rows(logits, "logits");
-  const int64_t rows = logits.size(0), vocab = logits.size(1);
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0, "json_guide: logits must be 16-B aligned");
-  TORCH_CHECK(slot.is_cuda() && slot.scalar_type() == at::kInt && slot.is_contiguous() && slot.numel() >= rows,
-              "json_guide: slot int32 [rows]");
-  TORCH_CHECK(desc.is_cuda() && desc.scalar_type() == at::kInt && desc.is_contiguous() && desc.dim() == 2 &&
-                  desc.size(1) == 4 && reinterpret_cast<uintptr_t>(desc.data_ptr()) % 16 == 0,
-              "json_guide: desc int32 [slots, 4]");
-  const int64_t slots = desc.size(0);
+  const GuideArgs g = guide_args("json_guide", logits, slot, desc, cur, err, advance_ids, lm_part);
   TORCH_CHECK(trans.is_cuda() && trans.scalar_type() == at::kShort && trans.is_contiguous() && trans.dim() == 2 &&
                   trans.size(1) == 256, "json_guide: trans int16 [S, 256]");
-  TORCH_CHECK(tok_off.is_cuda() && tok_off.scalar_type() == at::kInt && tok_off.is_contiguous() && tok_off.dim() == 1,
-              "json_guide: tok_off int32 [n_tok + 1]");
-  TORCH_CHECK(tok_bytes.is_cuda() && tok_bytes.scalar_type() == at::kByte && tok_bytes.is_contiguous() &&
-                  tok_bytes.dim() == 1, "json_guide: tok_bytes uint8 [B]");
-  TORCH_CHECK(cur.is_cuda() && cur.scalar_type() == at::kInt && cur.is_contiguous() && cur.numel() >= slots &&
-                  err.is_cuda() && err.scalar_type() == at::kInt && err.is_contiguous() && err.numel() >= slots,
-              "json_guide: cur / err int32 [slots]");
+  guide_tok_table("json_guide", tok_off, tok_bytes);
   TORCH_CHECK(jstk.is_cuda() && jstk.scalar_type() == at::kInt && jstk.is_contiguous() && jstk.dim() == 2 &&
-                  jstk.size(0) >= slots && jstk.size(1) == 2, "json_guide: jstk int32 [slots, 2]");
-  const int64_t* ap = nullptr;
-  if (advance_ids.has_value()) {
-    TORCH_CHECK(advance_ids->is_cuda() && advance_ids->scalar_type() == at::kLong && advance_ids->is_contiguous() &&
-                    advance_ids->numel() >= rows, "json_guide: advance_ids int64 [rows]");
-    ap = advance_ids->data_ptr<int64_t>();
-  }
-  uint32_t* lp = nullptr;
-  int lparts = 0;
-  if (lm_part.has_value()) {
-    TORCH_CHECK(lm_part->is_cuda() && lm_part->scalar_type() == at::kInt && lm_part->dim() == 3 &&
-                    lm_part->size(0) >= rows && lm_part->size(2) == 2 && lm_part->is_contiguous(),
-                "json_guide: lm_part [rows, parts, 2] int32");
-    lp = reinterpret_cast<uint32_t*>(lm_part->data_ptr<int>());
-    lparts = (int)lm_part->size(1);
-  }
-  HIP_OK(die::launch_json_guide(bf(logits), logits.stride(0), (int)rows, (int)vocab, slot.data_ptr<int>(), (int)slots,
-                                 desc.data_ptr<int>(), trans.data_ptr<int16_t>(), trans.size(0),
+                  jstk.size(0) >= g.slots && jstk.size(1) == 2, "json_guide: jstk int32 [slots, 2]");
+  HIP_OK(die::launch_json_guide(bf(logits), logits.stride(0), (int)g.rows, (int)g.vocab, slot.data_ptr<int>(),
+                                 (int)g.slots, desc.data_ptr<int>(), trans.data_ptr<int16_t>(), trans.size(0),
                                  tok_off.data_ptr<int>(), tok_off.numel() - 1, tok_bytes.data_ptr<uint8_t>(),
-                                 tok_bytes.numel(), cur.data_ptr<int>(), jstk.data_ptr<int>(), err.data_ptr<int>(), ap,
-                                 lp, lparts, cur_stream()));
+                                 tok_bytes.numel(), cur.data_ptr<int>(), jstk.data_ptr<int>(), err.data_ptr<int>(),
+                                 g.ap, g.lp, g.lparts, cur_stream()));
 }
 
-// Structured outputs on logits [rows, vocab] in place (schema_guide.hip). slot int32 [>= rows]; desc int32 [slots, 4]
-// = (state_base, n_states, eos, 0); trans int32 [A, 256] and accept uint8 [A], the pushdown arenas; tok_off / tok_bytes:
-// byte_guide's tables; cur / err int32 [slots] (token_guide's); sdep int32 [slots] and sstk int16 [slots, 32], the
-// depth and the return states; advance_ids and lm_part optional. The launcher itself refuses vocab % 8 != 0, a bad
-// stride, null tables and an oversized arena.
+// Structured outputs on logits [rows, vocab] in place (schema_guide.hip). desc int32 [slots, 4] = (state_base,
+// n_states, eos, 0); trans int32 [A, 256] and accept uint8 [A], the pushdown arenas; tok_off / tok_bytes: byte_guide's
+// tables; cur / err are token_guide's; sdep int32 [slots] and sstk int16 [slots, 32], the depth and the return states.
 void schema_guide(Tensor logits, Tensor slot, Tensor desc, Tensor trans, Tensor accept, Tensor tok_off,
                   Tensor tok_bytes, Tensor cur, Tensor sdep, Tensor sstk, Tensor err,
                   c10::optional<Tensor> advance_ids, c10::optional<Tensor> lm_part) {
-  CHK_CUDA(logits);
-  CHK_BF16(logits);
-  check_rows(logits, "logits");
-  const int64_t rows = logits.size(0), vocab = logits.size(1);
-  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % 16 == 0, "schema_guide: logits must be 16-B aligned");
-  TORCH_CHECK(slot.is_cuda() && slot.scalar_type() == at::kInt && slot.is_contiguous() && slot.numel() >= rows,
-              "schema_guide: slot int32 [rows]");
-  TORCH_CHECK(desc.is_cuda() && desc.scalar_type() == at::kInt && desc.is_contiguous() && desc.dim() == 2 &&
-                  desc.size(1) == 4 && reinterpret_cast<uintptr_t>(desc.data_ptr()) % 16 == 0,
-              "schema_guide: desc int32 [slots, 4]");
-  const int64_t slots = desc.size(0);
+  const GuideArgs g = guide_args("schema_guide", logits, slot, desc, cur, err, advance_ids, lm_part);
   TORCH_CHECK(trans.is_cuda() && trans.scalar_type() == at::kInt && trans.is_contiguous() && trans.dim() == 2 &&
                   trans.size(1) == 256, "schema_guide: trans int32 [A, 256]");
   TORCH_CHECK(accept.is_cuda() && accept.scalar_type() == at::kByte && accept.is_contiguous() && accept.dim() == 1,
               "schema_guide: accept uint8 [A]");
-  TORCH_CHECK(tok_off.is_cuda() && tok_off.scalar_type() == at::kInt && tok_off.is_contiguous() && tok_off.dim() == 1,
-              "schema_guide: tok_off int32 [n_tok + 1]");
-  TORCH_CHECK(tok_bytes.is_cuda() && tok_bytes.scalar_type() == at::kByte && tok_bytes.is_contiguous() &&
-                  tok_bytes.dim() == 1, "schema_guide: tok_bytes uint8 [B]");
-  TORCH_CHECK(cur.is_cuda() && cur.scalar_type() == at::kInt && cur.is_contiguous() && cur.numel() >= slots &&
-                  err.is_cuda() && err.scalar_type() == at::kInt && err.is_contiguous() && err.numel() >= slots,
-              "schema_guide: cur / err int32 [slots]");
-  TORCH_CHECK(sdep.is_cuda() && sdep.scalar_type() == at::kInt && sdep.is_contiguous() && sdep.numel() >= slots,
+  guide_tok_table("schema_guide", tok_off, tok_bytes);
+  TORCH_CHECK(sdep.is_cuda() && sdep.scalar_type() == at::kInt && sdep.is_contiguous() && sdep.numel() >= g.slots,
               "schema_guide: sdep int32 [slots]");
   TORCH_CHECK(sstk.is_cuda() && sstk.scalar_type() == at::kShort && sstk.is_contiguous() && sstk.dim() == 2 &&
-                  sstk.size(0) >= slots && sstk.size(1) == die::GUIDE_SCHEMA_MAX_DEPTH,
+                  sstk.size(0) >= g.slots && sstk.size(1) == die::GUIDE_SCHEMA_MAX_DEPTH,
               "schema_guide: sstk int16 [slots, 32]");
-  const int64_t* ap = nullptr;
-  if (advance_ids.has_value()) {
-    TORCH_CHECK(advance_ids->is_cuda() && advance_ids->scalar_type() == at::kLong && advance_ids->is_contiguous() &&
-                    advance_ids->numel() >= rows, "schema_guide: advance_ids int64 [rows]");
-    ap = advance_ids->data_ptr<int64_t>();
-  }
-  uint32_t* lp = nullptr;
-  int lparts = 0;
-  if (lm_part.has_value()) {
-    TORCH_CHECK(lm_part->is_cuda() && lm_part->scalar_type() == at::kInt && lm_part->dim() == 3 &&
-                    lm_part->size(0) >= rows && lm_part->size(2) == 2 && lm_part->is_contiguous(),
-                "schema_guide: lm_part [rows, parts, 2] int32");
-    lp = reinterpret_cast<uint32_t*>(lm_part->data_ptr<int>());
-    lparts = (int)lm_part->size(1);
-  }
-  HIP_OK(die::launch_schema_guide(bf(logits), logits.stride(0), (int)rows, (int)vocab, slot.data_ptr<int>(),
-                                   (int)slots, desc.data_ptr<int>(), trans.data_ptr<int>(), trans.size(0),
+  HIP_OK(die::launch_schema_guide(bf(logits), logits.stride(0), (int)g.rows, (int)g.vocab, slot.data_ptr<int>(),
+                                   (int)g.slots, desc.data_ptr<int>(), trans.data_ptr<int>(), trans.size(0),
                                    accept.data_ptr<uint8_t>(), accept.numel(), tok_off.data_ptr<int>(),
                                    tok_off.numel() - 1, tok_bytes.data_ptr<uint8_t>(), tok_bytes.numel(),
                                    cur.data_ptr<int>(), sdep.data_ptr<int>(), sstk.data_ptr<int16_t>(),
-                                   err.data_ptr<int>(), ap, lp, lparts, cur_stream()));
+                                   err.data_ptr<int>(), g.ap, g.lp, g.lparts, cur_stream()));
 }
 
 // Embedding pooling (pooling.hip): hidden bf16 [T, H] (row stride allowed); segs int32 [S, 8]; acc fp32 [slots, H]

@@ -18,40 +18,28 @@
 //      from cur; a dead transition, a token with no bytes, beyond the table or the vocabulary, or over the length
 //      cap, and any non-EOS token in the sink: err |= GUIDE_ERR_NO_EDGE. The state is kept in every such case.
 //   2. Token t is allowed next: in the sink only EOS; else EOS iff accept[c]; else iff t < min(vocab, n_tok), it
-//      has 1..GUIDE_MAX_TOKEN_BYTES bytes and its walk from c never dies. One lane per token, BG_TU independent
+//      has 1..GUIDE_MAX_TOKEN_BYTES bytes and its walk from c never dies. One lane per token, GUIDE_TU independent
 //      chains per lane in flight, level by level, a chain's bytes fetched eight at a time and its state updated by
 //      selects (written with branches the compiler serialised the chains: 269 us per launch at 32 x 128,256 against
-//      217); a wave's 64 verdicts become two bitmap words by ballot (plain LDS stores, no atomics). A guide of up to BG_LDS_STATES states has its trans rows copied to LDS first
-//      (the walk's lookups then never leave the CU), a larger one is read through L2.
-//   3. One dense pass, as token_guide: a barred entry becomes bf16 -inf (0xFF80), an allowed entry keeps its exact
-//      bits; a 16-B group with no allowed entry is stored without being loaded, one with all eight is not stored.
-//   4. lm_part != nullptr: the row's LM-head candidates are rewritten as token_guide does (candidate 0 = the best
+//      217); a wave's 64 verdicts become two bitmap words by ballot (guide_common.h has the fetch and the ballot
+//      write-out). A guide of up to BG_LDS_STATES states has its trans rows copied to LDS first (the walk's lookups
+//      then never leave the CU), a larger one is read through L2.
+//   3. One dense pass (guide_common.h's guide_mask_row): a barred entry becomes bf16 -inf (0xFF80), an allowed entry
+//      keeps its exact bits; a 16-B group with no allowed entry is stored without being loaded, one with all eight
+//      is not stored.
+//   4. lm_part != nullptr: the row's LM-head candidates are rewritten by the same pass (candidate 0 = the best
 //      ALLOWED entry in sampling.hip's better() order, the others (-inf, 0x7fffffff)).
 //   5. Everything is checked BEFORE it is used as an index: state_base + n_states within the arenas, cur in
 //      [0, n_states], eos in [0, vocab), 0 <= off[t] <= off[t + 1] <= bytes_len for every token looked at, every
 //      trans value read in [-1, n_states). A violation: err |= GUIDE_ERR_TABLE, and the row, the candidates and
 //      cur stay untouched — which is why the bitmap is complete before the row is written. No table content leads
 //      to an out-of-range access.
-#include "common.h"
-#include "launchers.h"
+#include "guide_common.h"
 
 namespace die {
 
-constexpr int BGT = 1024;
-constexpr int BG_MAX_MAP_BYTES = 48 * 1024;  // the bitmap's share of LDS: vocab <= 393216 (as token_guide)
-constexpr uint32_t BG_NINF2 = 0xFF80FF80u;   // two bf16 -inf
-constexpr int BG_TU = 4;                     // tokens (independent chains) per lane in flight
 constexpr int BG_LDS_STATES = GUIDE_BYTE_LDS_STATES;
 constexpr int BG_LDS_TRANS_BYTES = BG_LDS_STATES * 512;
-
-struct BgBest {
-  float v;
-  int i;
-};
-// sampling.hip's better(): larger value first, then lower index
-__device__ __forceinline__ BgBest bg_better(BgBest a, BgBest b) {
-  return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
-}
 
 // The allowed bits of tokens [0, lim) from state c into s_map; returns true when a table value was out of bounds.
 // tr: the guide's trans rows, their LDS copy or the arena itself (inlined once for each). Uniform trip counts: every
@@ -60,13 +48,12 @@ __device__ __forceinline__ bool bg_walk_tokens(const int16_t* __restrict__ tr, i
                                                const int* __restrict__ tok_off, const uint8_t* __restrict__ tok_bytes,
                                                int bytes_len, uint32_t* s_map, int map_words) {
   bool bad = false;
-  const int lane = threadIdx.x & 63;
-  for (int t0 = 0; t0 < lim; t0 += BGT * BG_TU) {
-    int s[BG_TU], p[BG_TU], e[BG_TU];
-    unsigned long long w[BG_TU];  // the chain's next bytes, lowest first
+  for (int t0 = 0; t0 < lim; t0 += GUIDE_T * GUIDE_TU) {
+    int s[GUIDE_TU], p[GUIDE_TU], e[GUIDE_TU];
+    unsigned long long w[GUIDE_TU];  // the chain's next bytes, lowest first
 #pragma unroll
-    for (int u = 0; u < BG_TU; ++u) {
-      const int t = t0 + u * BGT + (int)threadIdx.x;
+    for (int u = 0; u < GUIDE_TU; ++u) {
+      const int t = t0 + u * GUIDE_T + (int)threadIdx.x;
       w[u] = 0ull;
       s[u] = -1;
       p[u] = e[u] = 0;
@@ -82,37 +69,29 @@ __device__ __forceinline__ bool bg_walk_tokens(const int16_t* __restrict__ tr, i
       }
     }
     for (int step = 0; step < GUIDE_MAX_TOKEN_BYTES; ++step) {
-      bool act[BG_TU], any = false;
+      bool act[GUIDE_TU], any = false;
 #pragma unroll
-      for (int u = 0; u < BG_TU; ++u) {
+      for (int u = 0; u < GUIDE_TU; ++u) {
         act[u] = s[u] >= 0 && p[u] < e[u];
         any |= act[u];
       }
       if (__ballot(any) == 0ull) break;  // nothing left to read in this wave
       // a lane with nothing to read loads the head of each table (both exist): the loads stay unconditional, so the
-      // BG_TU chains' loads issue together
-      if ((step & 7) == 0) {
-        // every eighth step (uniform) a chain fetches its next eight bytes in one load, so that the steps between
-        // depend on the trans lookup alone. The window [q, q + 8) is pulled back from the table's end (the launcher
-        // requires bytes_len >= 8); p - q <= 7 because p < e <= bytes_len
+      // GUIDE_TU chains' loads issue together
+      if ((step & 7) == 0) {  // uniform
 #pragma unroll
-        for (int u = 0; u < BG_TU; ++u) {
-          const int q = act[u] ? (p[u] < bytes_len - 8 ? p[u] : bytes_len - 8) : 0;
-          unsigned long long x;
-          __builtin_memcpy(&x, tok_bytes + q, 8);
-          w[u] = x >> (8 * (act[u] ? p[u] - q : 0));
-        }
+        for (int u = 0; u < GUIDE_TU; ++u) w[u] = guide_next_bytes(tok_bytes, bytes_len, act[u], p[u]);
       }
-      int b[BG_TU], v[BG_TU];
+      int b[GUIDE_TU], v[GUIDE_TU];
 #pragma unroll
-      for (int u = 0; u < BG_TU; ++u) {
+      for (int u = 0; u < GUIDE_TU; ++u) {
         b[u] = (int)(w[u] & 0xffull);
         w[u] >>= 8;
       }
 #pragma unroll
-      for (int u = 0; u < BG_TU; ++u) v[u] = (int)tr[(act[u] ? s[u] : 0) * 256 + b[u]];
+      for (int u = 0; u < GUIDE_TU; ++u) v[u] = (int)tr[(act[u] ? s[u] : 0) * 256 + b[u]];
 #pragma unroll
-      for (int u = 0; u < BG_TU; ++u) {  // selects, not branches: the four chains stay one instruction stream
+      for (int u = 0; u < GUIDE_TU; ++u) {  // selects, not branches: the four chains stay one instruction stream
         const bool oob = v[u] < -1 || v[u] >= n_states;
         bad |= act[u] & oob;
         s[u] = act[u] ? (oob ? -1 : v[u]) : s[u];  // -1: the walk died, or read a value out of bounds
@@ -120,32 +99,25 @@ __device__ __forceinline__ bool bg_walk_tokens(const int16_t* __restrict__ tr, i
       }
     }
 #pragma unroll
-    for (int u = 0; u < BG_TU; ++u) {
-      const unsigned long long m = __ballot(s[u] >= 0);
-      const int wi = (t0 + u * BGT + (int)threadIdx.x - lane) >> 5;  // the wave's 64 tokens start at a multiple of 64
-      if (lane == 0) {
-        if (wi < map_words) s_map[wi] = (uint32_t)m;
-        if (wi + 1 < map_words) s_map[wi + 1] = (uint32_t)(m >> 32);
-      }
-    }
+    for (int u = 0; u < GUIDE_TU; ++u)
+      guide_write_verdicts(s_map, map_words, t0 + u * GUIDE_T + (int)threadIdx.x, s[u] >= 0);
   }
   return bad;
 }
 
-__global__ void __launch_bounds__(BGT) byte_guide_kernel(bf16_t* __restrict__ logits, int64_t stride, int vocab,
-                                                         const int* __restrict__ slot_of_row, int num_slots,
-                                                         const int4* __restrict__ desc,
-                                                         const int16_t* __restrict__ trans,
-                                                         const uint8_t* __restrict__ accept, int arena_states,
-                                                         const int* __restrict__ tok_off, int n_tok,
-                                                         const uint8_t* __restrict__ tok_bytes, int bytes_len,
-                                                         int* __restrict__ cur, int* __restrict__ err,
-                                                         const int64_t* __restrict__ advance_ids,
-                                                         uint32_t* __restrict__ lm_part, int lm_parts, int map_words,
-                                                         int tr_off_words) {
+__global__ void __launch_bounds__(GUIDE_T) byte_guide_kernel(bf16_t* __restrict__ logits, int64_t stride, int vocab,
+                                                             const int* __restrict__ slot_of_row, int num_slots,
+                                                             const int4* __restrict__ desc,
+                                                             const int16_t* __restrict__ trans,
+                                                             const uint8_t* __restrict__ accept, int arena_states,
+                                                             const int* __restrict__ tok_off, int n_tok,
+                                                             const uint8_t* __restrict__ tok_bytes, int bytes_len,
+                                                             int* __restrict__ cur, int* __restrict__ err,
+                                                             const int64_t* __restrict__ advance_ids,
+                                                             uint32_t* __restrict__ lm_part, int lm_parts,
+                                                             int map_words, int tr_off_words) {
   extern __shared__ uint32_t s_map[];  // bit t: token t is allowed; behind it (16-B aligned) the trans rows' copy
   __shared__ int s_bad;
-  __shared__ BgBest red[BGT / 64];
   const int r = blockIdx.x;
   const int slot = slot_of_row[r];
   if (slot < 0 || slot >= num_slots) return;  // uniform
@@ -200,23 +172,21 @@ __global__ void __launch_bounds__(BGT) byte_guide_kernel(bf16_t* __restrict__ lo
       }
     }
   }
-  for (int w = threadIdx.x; w < map_words; w += BGT) s_map[w] = 0u;
+  for (int w = threadIdx.x; w < map_words; w += GUIDE_T) s_map[w] = 0u;
   if (threadIdx.x == 0) s_bad = 0;
   const bool in_lds = c < n_states && n_states <= BG_LDS_STATES;
   int16_t* s_tr = reinterpret_cast<int16_t*>(s_map + tr_off_words);
   if (in_lds) {  // n_states * 512 bytes, 16 B per lane and trip; both sides are 16-B aligned
     const uint4* src = reinterpret_cast<const uint4*>(tr);
     uint4* dst = reinterpret_cast<uint4*>(s_tr);
-    for (int q = threadIdx.x; q < n_states * 32; q += BGT) dst[q] = src[q];
+    for (int q = threadIdx.x; q < n_states * 32; q += GUIDE_T) dst[q] = src[q];
   }
   __syncthreads();
   if (c == n_states) {
     if (threadIdx.x == 0) s_map[eos >> 5] = 1u << (eos & 31);
   } else {
-    const bool bad = in_lds ? bg_walk_tokens(s_tr, c, n_states, lim, tok_off, tok_bytes, bytes_len, s_map,
-                                                      map_words)
-                            : bg_walk_tokens(tr, c, n_states, lim, tok_off, tok_bytes, bytes_len, s_map,
-                                                      map_words);
+    const bool bad = in_lds ? bg_walk_tokens(s_tr, c, n_states, lim, tok_off, tok_bytes, bytes_len, s_map, map_words)
+                            : bg_walk_tokens(tr, c, n_states, lim, tok_off, tok_bytes, bytes_len, s_map, map_words);
     if (bad) s_bad = 1;
     __syncthreads();
     if (threadIdx.x == 0) {  // EOS by the state alone, whatever bytes the table gives it
@@ -237,72 +207,8 @@ __global__ void __launch_bounds__(BGT) byte_guide_kernel(bf16_t* __restrict__ lo
     cur[slot] = c;
     if (flags) err[slot] |= flags;
   }
-  const uint8_t* map8 = reinterpret_cast<const uint8_t*>(s_map);
-  bf16_t* row = logits + (int64_t)r * stride;
-  const int lane = threadIdx.x & 63;
-
-  constexpr int AU = 4;  // 16-B groups per lane in flight
-  BgBest best{-INFINITY, 0x7fffffff};
-  for (int i0 = threadIdx.x * 8; i0 < vocab; i0 += BGT * 8 * AU) {
-    uint4 lv[AU];
-    uint32_t mb[AU];
-#pragma unroll
-    for (int u = 0; u < AU; ++u) {
-      const int i = i0 + u * BGT * 8;
-      mb[u] = 0u;
-      if (i < vocab) {
-        mb[u] = (uint32_t)map8[i >> 3];
-        if (mb[u] != 0u) lv[u] = *reinterpret_cast<const uint4*>(row + i);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < AU; ++u) {
-      const int i = i0 + u * BGT * 8;
-      if (i >= vocab) continue;
-      const uint32_t m = mb[u];
-      if (m == 0u) {  // nothing allowed here: the group was not loaded
-        *reinterpret_cast<uint4*>(row + i) = make_uint4(BG_NINF2, BG_NINF2, BG_NINF2, BG_NINF2);
-        continue;
-      }
-      uint32_t w[4] = {lv[u].x, lv[u].y, lv[u].z, lv[u].w};
-      if (m != 0xffu) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (!(m & (1u << (2 * j)))) w[j] = (w[j] & 0xffff0000u) | 0xFF80u;
-          if (!(m & (1u << (2 * j + 1)))) w[j] = (w[j] & 0x0000ffffu) | 0xFF800000u;
-        }
-        *reinterpret_cast<uint4*>(row + i) = make_uint4(w[0], w[1], w[2], w[3]);
-      }
-      if (lm_part != nullptr) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          if (m & (1u << j)) {
-            const uint32_t h = (j & 1) ? (w[j >> 1] & 0xffff0000u) : (w[j >> 1] << 16);
-            best = bg_better(best, BgBest{__uint_as_float(h), i + j});
-          }
-        }
-      }
-    }
-  }
-  if (lm_part == nullptr) return;  // uniform
-
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    BgBest y;
-    y.v = __shfl_xor(best.v, off, 64);
-    y.i = __shfl_xor(best.i, off, 64);
-    best = bg_better(best, y);
-  }
-  const int wid = threadIdx.x >> 6;
-  if (lane == 0) red[wid] = best;
-  __syncthreads();
-  BgBest wn = red[0];
-  for (int q = 1; q < BGT / 64; ++q) wn = bg_better(wn, red[q]);
-  uint32_t* pc = lm_part + (int64_t)r * lm_parts * 2;
-  for (int q = threadIdx.x; q < lm_parts; q += BGT) {
-    const uint2 cd = q == 0 ? make_uint2(__float_as_uint(wn.v), (uint32_t)wn.i) : make_uint2(0xff800000u, 0x7fffffffu);
-    *reinterpret_cast<uint2*>(pc + 2 * q) = cd;
-  }
+  guide_mask_row<GUIDE_T>(logits + (int64_t)r * stride, vocab, s_map,
+                          lm_part != nullptr ? lm_part + (int64_t)r * lm_parts * 2 : nullptr, lm_parts);
 }
 
 hipError_t launch_byte_guide(bf16_t* logits, int64_t stride, int rows, int vocab, const int* slot, int num_slots,
@@ -310,38 +216,25 @@ hipError_t launch_byte_guide(bf16_t* logits, int64_t stride, int rows, int vocab
                              int64_t accept_len, const int* tok_off, int64_t n_tok, const uint8_t* tok_bytes,
                              int64_t bytes_len, int* cur, int* err, const int64_t* advance_ids, uint32_t* lm_part,
                              int lm_parts, hipStream_t s) {
-  if (vocab <= 0 || vocab % 8 || rows < 0 || num_slots < 1) return hipErrorInvalidValue;
+  int map_words;
+  if (!guide_row_args_ok(vocab, stride, rows, num_slots, lm_part, lm_parts, &map_words)) return hipErrorInvalidValue;
   if (logits == nullptr || slot == nullptr || desc == nullptr || trans == nullptr || accept == nullptr ||
       tok_off == nullptr || tok_bytes == nullptr || cur == nullptr || err == nullptr)
     return hipErrorInvalidValue;
-  if (stride < vocab || stride % 8) return hipErrorInvalidValue;
   if (trans_states < 1 || trans_states > GUIDE_BYTE_STATE_ARENA || accept_len < 1 ||
       accept_len > GUIDE_BYTE_STATE_ARENA)
     return hipErrorInvalidValue;
-  // bytes_len >= 8: the kernel fetches a token's bytes eight at a time, from a window that lies inside the table
-  if (n_tok < 1 || n_tok > GUIDE_TOK_TABLE_MAX || bytes_len < 8 || bytes_len > GUIDE_TOK_BYTES_MAX)
-    return hipErrorInvalidValue;
+  if (!guide_tok_table_ok(n_tok, bytes_len)) return hipErrorInvalidValue;
   if (reinterpret_cast<uintptr_t>(trans) % 16) return hipErrorInvalidValue;  // the rows' copy to LDS moves 16 B
-  if (lm_part != nullptr && lm_parts < 1) return hipErrorInvalidValue;
-  const int map_words = (vocab / 8 + 3) / 4;
-  if (map_words * 4 > BG_MAX_MAP_BYTES) return hipErrorInvalidValue;
   if (rows == 0) return hipSuccess;
   const int tr_off_words = (map_words + 3) & ~3;
   const int lds = tr_off_words * 4 + BG_LDS_TRANS_BYTES;
-  // more than 64 KiB of dynamic LDS has to be asked for, once per device
   static bool asked[64] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  const hipError_t e = guide_ask_dynamic_lds(reinterpret_cast<const void*>(byte_guide_kernel),
+                                             GUIDE_MAX_MAP_BYTES + BG_LDS_TRANS_BYTES, asked);
   if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64) return hipErrorInvalidValue;
-  if (!asked[dev]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(byte_guide_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, BG_MAX_MAP_BYTES + BG_LDS_TRANS_BYTES);
-    if (e != hipSuccess) return e;
-    asked[dev] = true;
-  }
   const int arena_states = (int)(trans_states < accept_len ? trans_states : accept_len);
-  hipLaunchKernelGGL(byte_guide_kernel, dim3(rows), dim3(BGT), lds, s, logits, stride, vocab, slot, num_slots,
+  hipLaunchKernelGGL(byte_guide_kernel, dim3(rows), dim3(GUIDE_T), lds, s, logits, stride, vocab, slot, num_slots,
                      reinterpret_cast<const int4*>(desc), trans, accept, arena_states, tok_off, (int)n_tok, tok_bytes,
                      (int)bytes_len, cur, err, advance_ids, lm_part, lm_parts, map_words, tr_off_words);
   return hipGetLastError();

@@ -23,14 +23,15 @@
 //   2. Token t is allowed next: in the sink only EOS; else EOS iff the state is DONE; else iff t < min(vocab, n_tok),
 //      it has 1..GUIDE_MAX_TOKEN_BYTES bytes and its walk from the current configuration never dies (one token may
 //      push and pop several times).
-//   3. One lane per token, JG_TU independent chains per lane in flight, level by level, a chain's bytes fetched eight
-//      at a time; state, depth and stack are updated by selects, not branches (byte_guide.hip's header has the
-//      measurement behind that); a wave's 64 verdicts become two bitmap words by ballot. The table always fits LDS
-//      (GUIDE_JSON_MAX_STATES * 512 bytes behind the bitmap) and is copied there first.
-//   4. The dense pass over the row and the rewrite of the LM-head candidates are byte_guide's: a barred entry becomes
-//      bf16 -inf (0xFF80), an allowed entry keeps its exact bits; a 16-B group with no allowed entry is stored
-//      without being loaded, one with all eight is not stored; lm_part != nullptr: candidate 0 = the best ALLOWED
-//      entry in sampling.hip's better() order, the others (-inf, 0x7fffffff).
+//   3. One lane per token, GUIDE_TU independent chains per lane in flight, level by level, a chain's bytes fetched
+//      eight at a time; state, depth and stack are updated by selects, not branches (byte_guide.hip's header has the
+//      measurement behind that); a wave's 64 verdicts become two bitmap words by ballot (guide_common.h has the fetch
+//      and the ballot write-out). The table always fits LDS (GUIDE_JSON_MAX_STATES * 512 bytes behind the bitmap) and
+//      is copied there first.
+//   4. The dense pass over the row and the rewrite of the LM-head candidates are guide_common.h's guide_mask_row: a
+//      barred entry becomes bf16 -inf (0xFF80), an allowed entry keeps its exact bits; a 16-B group with no allowed
+//      entry is stored without being loaded, one with all eight is not stored; lm_part != nullptr: candidate 0 = the
+//      best ALLOWED entry in sampling.hip's better() order, the others (-inf, 0x7fffffff).
 //   5. Everything is checked BEFORE it is used as an index: n_states in [3, table_states], done in [0, n_states),
 //      state in [0, n_states], depth in [0, 32], no stack bit at or above the depth, eos in [0, vocab), 0 <= off[t] <=
 //      off[t + 1] <= bytes_len for every token looked at, every entry of the table's first n_states rows either -1
@@ -40,25 +41,11 @@
 //      violation: err |= GUIDE_ERR_TABLE, and the row, the candidates, cur and jstk stay untouched — which is why
 //      the bitmap is complete before anything is written. No table content leads to an out-of-range access.
 // Plain C++ and vector stores only.
-#include "common.h"
-#include "launchers.h"
+#include "guide_common.h"
 
 namespace die {
 
-constexpr int JGT = 1024;
-constexpr int JG_MAX_MAP_BYTES = 48 * 1024;  // the bitmap's share of LDS: vocab <= 393216 (as byte_guide)
-constexpr uint32_t JG_NINF2 = 0xFF80FF80u;   // two bf16 -inf
-constexpr int JG_TU = 4;                     // tokens (independent chains) per lane in flight
 constexpr int JG_TRANS_BYTES = GUIDE_JSON_MAX_STATES * 512;
-
-struct JgBest {
-  float v;
-  int i;
-};
-// sampling.hip's better(): larger value first, then lower index
-__device__ __forceinline__ JgBest jg_better(JgBest a, JgBest b) {
-  return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
-}
 
 // One byte from configuration (s, d, k) over table entry v, by selects. s becomes -1 when the walk dies (no
 // transition, or a push at the cap); returns true when the entry or the pop is out of bounds (s is -1 then too).
@@ -103,14 +90,13 @@ __device__ __forceinline__ bool jg_walk_tokens(const int16_t* __restrict__ tr, i
                                                const int* __restrict__ tok_off, const uint8_t* __restrict__ tok_bytes,
                                                int bytes_len, uint32_t* s_map, int map_words) {
   bool bad = false;
-  const int lane = threadIdx.x & 63;
-  for (int t0 = 0; t0 < lim; t0 += JGT * JG_TU) {
-    int s[JG_TU], p[JG_TU], e[JG_TU], d[JG_TU];
-    uint32_t k[JG_TU];
-    unsigned long long w[JG_TU];  // the chain's next bytes, lowest first
+  for (int t0 = 0; t0 < lim; t0 += GUIDE_T * GUIDE_TU) {
+    int s[GUIDE_TU], p[GUIDE_TU], e[GUIDE_TU], d[GUIDE_TU];
+    uint32_t k[GUIDE_TU];
+    unsigned long long w[GUIDE_TU];  // the chain's next bytes, lowest first
 #pragma unroll
-    for (int u = 0; u < JG_TU; ++u) {
-      const int t = t0 + u * JGT + (int)threadIdx.x;
+    for (int u = 0; u < GUIDE_TU; ++u) {
+      const int t = t0 + u * GUIDE_T + (int)threadIdx.x;
       w[u] = 0ull;
       s[u] = -1;
       p[u] = e[u] = 0;
@@ -128,36 +114,28 @@ __device__ __forceinline__ bool jg_walk_tokens(const int16_t* __restrict__ tr, i
       }
     }
     for (int step = 0; step < GUIDE_MAX_TOKEN_BYTES; ++step) {
-      bool act[JG_TU], any = false;
+      bool act[GUIDE_TU], any = false;
 #pragma unroll
-      for (int u = 0; u < JG_TU; ++u) {
+      for (int u = 0; u < GUIDE_TU; ++u) {
         act[u] = s[u] >= 0 && p[u] < e[u];
         any |= act[u];
       }
       if (__ballot(any) == 0ull) break;  // nothing left to read in this wave
-      if ((step & 7) == 0) {
-        // every eighth step (uniform) a chain fetches its next eight bytes in one load. The window [q, q + 8) is
-        // pulled back from the table's end (the launcher requires bytes_len >= 8); p - q <= 7 because p < e <=
-        // bytes_len. A lane with nothing to read loads the table's head: the loads stay unconditional
+      if ((step & 7) == 0) {  // uniform
 #pragma unroll
-        for (int u = 0; u < JG_TU; ++u) {
-          const int q = act[u] ? (p[u] < bytes_len - 8 ? p[u] : bytes_len - 8) : 0;
-          unsigned long long x;
-          __builtin_memcpy(&x, tok_bytes + q, 8);
-          w[u] = x >> (8 * (act[u] ? p[u] - q : 0));
-        }
+        for (int u = 0; u < GUIDE_TU; ++u) w[u] = guide_next_bytes(tok_bytes, bytes_len, act[u], p[u]);
       }
-      int b[JG_TU], v[JG_TU];
+      int b[GUIDE_TU], v[GUIDE_TU];
 #pragma unroll
-      for (int u = 0; u < JG_TU; ++u) {
+      for (int u = 0; u < GUIDE_TU; ++u) {
         b[u] = (int)(w[u] & 0xffull);
         w[u] >>= 8;
       }
       // s[u] < n_states here: it starts at c < n_states and the validated table only yields states below it
 #pragma unroll
-      for (int u = 0; u < JG_TU; ++u) v[u] = (int)tr[(act[u] ? s[u] : 0) * 256 + b[u]];
+      for (int u = 0; u < GUIDE_TU; ++u) v[u] = (int)tr[(act[u] ? s[u] : 0) * 256 + b[u]];
 #pragma unroll
-      for (int u = 0; u < JG_TU; ++u) {  // selects, not branches: the chains stay one instruction stream
+      for (int u = 0; u < GUIDE_TU; ++u) {  // selects, not branches: the chains stay one instruction stream
         int sn = s[u];
         const bool bad_pop = jg_step_lean(v[u], sn, d[u], k[u]);  // d, k of a chain that does not read: never used
         bad |= act[u] & bad_pop;
@@ -166,32 +144,25 @@ __device__ __forceinline__ bool jg_walk_tokens(const int16_t* __restrict__ tr, i
       }
     }
 #pragma unroll
-    for (int u = 0; u < JG_TU; ++u) {
-      const unsigned long long m = __ballot(s[u] >= 0);
-      const int wi = (t0 + u * JGT + (int)threadIdx.x - lane) >> 5;  // the wave's 64 tokens start at a multiple of 64
-      if (lane == 0) {
-        if (wi < map_words) s_map[wi] = (uint32_t)m;
-        if (wi + 1 < map_words) s_map[wi + 1] = (uint32_t)(m >> 32);
-      }
-    }
+    for (int u = 0; u < GUIDE_TU; ++u)
+      guide_write_verdicts(s_map, map_words, t0 + u * GUIDE_T + (int)threadIdx.x, s[u] >= 0);
   }
   return bad;
 }
 
-__global__ void __launch_bounds__(JGT) json_guide_kernel(bf16_t* __restrict__ logits, int64_t stride, int vocab,
-                                                         const int* __restrict__ slot_of_row, int num_slots,
-                                                         const int4* __restrict__ desc,
-                                                         const int16_t* __restrict__ trans, int table_states,
-                                                         const int* __restrict__ tok_off, int n_tok,
-                                                         const uint8_t* __restrict__ tok_bytes, int bytes_len,
-                                                         int* __restrict__ cur, int* __restrict__ jstk,
-                                                         int* __restrict__ err,
-                                                         const int64_t* __restrict__ advance_ids,
-                                                         uint32_t* __restrict__ lm_part, int lm_parts, int map_words,
-                                                         int tr_off_words) {
+__global__ void __launch_bounds__(GUIDE_T) json_guide_kernel(bf16_t* __restrict__ logits, int64_t stride, int vocab,
+                                                             const int* __restrict__ slot_of_row, int num_slots,
+                                                             const int4* __restrict__ desc,
+                                                             const int16_t* __restrict__ trans, int table_states,
+                                                             const int* __restrict__ tok_off, int n_tok,
+                                                             const uint8_t* __restrict__ tok_bytes, int bytes_len,
+                                                             int* __restrict__ cur, int* __restrict__ jstk,
+                                                             int* __restrict__ err,
+                                                             const int64_t* __restrict__ advance_ids,
+                                                             uint32_t* __restrict__ lm_part, int lm_parts,
+                                                             int map_words, int tr_off_words) {
   extern __shared__ uint32_t s_map[];  // bit t: token t is allowed; behind it (16-B aligned) the table's copy
   __shared__ int s_bad;
-  __shared__ JgBest red[JGT / 64];
   const int r = blockIdx.x;
   const int slot = slot_of_row[r];
   if (slot < 0 || slot >= num_slots) return;  // uniform
@@ -249,14 +220,14 @@ __global__ void __launch_bounds__(JGT) json_guide_kernel(bf16_t* __restrict__ lo
       }
     }
   }
-  for (int w = threadIdx.x; w < map_words; w += JGT) s_map[w] = 0u;
+  for (int w = threadIdx.x; w < map_words; w += GUIDE_T) s_map[w] = 0u;
   if (threadIdx.x == 0) s_bad = 0;
   int16_t* s_tr = reinterpret_cast<int16_t*>(s_map + tr_off_words);
   bool bad_entry = false;
   {  // n_states * 512 bytes, 16 B per lane and trip; both sides are 16-B aligned. Every entry is validated on the way
     const uint4* src = reinterpret_cast<const uint4*>(trans);
     uint4* dst = reinterpret_cast<uint4*>(s_tr);
-    for (int q = threadIdx.x; q < n_states * 32; q += JGT) {
+    for (int q = threadIdx.x; q < n_states * 32; q += GUIDE_T) {
       const uint4 x = src[q];
       dst[q] = x;
       const uint32_t w4[4] = {x.x, x.y, x.z, x.w};
@@ -294,108 +265,31 @@ __global__ void __launch_bounds__(JGT) json_guide_kernel(bf16_t* __restrict__ lo
     *reinterpret_cast<int2*>(jstk + 2 * slot) = make_int2(d, (int)k);
     if (flags) err[slot] |= flags;
   }
-  const uint8_t* map8 = reinterpret_cast<const uint8_t*>(s_map);
-  bf16_t* row = logits + (int64_t)r * stride;
-  const int lane = threadIdx.x & 63;
-
-  constexpr int AU = 4;  // 16-B groups per lane in flight
-  JgBest best{-INFINITY, 0x7fffffff};
-  for (int i0 = threadIdx.x * 8; i0 < vocab; i0 += JGT * 8 * AU) {
-    uint4 lv[AU];
-    uint32_t mb[AU];
-#pragma unroll
-    for (int u = 0; u < AU; ++u) {
-      const int i = i0 + u * JGT * 8;
-      mb[u] = 0u;
-      if (i < vocab) {
-        mb[u] = (uint32_t)map8[i >> 3];
-        if (mb[u] != 0u) lv[u] = *reinterpret_cast<const uint4*>(row + i);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < AU; ++u) {
-      const int i = i0 + u * JGT * 8;
-      if (i >= vocab) continue;
-      const uint32_t m = mb[u];
-      if (m == 0u) {  // nothing allowed here: the group was not loaded
-        *reinterpret_cast<uint4*>(row + i) = make_uint4(JG_NINF2, JG_NINF2, JG_NINF2, JG_NINF2);
-        continue;
-      }
-      uint32_t w[4] = {lv[u].x, lv[u].y, lv[u].z, lv[u].w};
-      if (m != 0xffu) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (!(m & (1u << (2 * j)))) w[j] = (w[j] & 0xffff0000u) | 0xFF80u;
-          if (!(m & (1u << (2 * j + 1)))) w[j] = (w[j] & 0x0000ffffu) | 0xFF800000u;
-        }
-        *reinterpret_cast<uint4*>(row + i) = make_uint4(w[0], w[1], w[2], w[3]);
-      }
-      if (lm_part != nullptr) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          if (m & (1u << j)) {
-            const uint32_t h = (j & 1) ? (w[j >> 1] & 0xffff0000u) : (w[j >> 1] << 16);
-            best = jg_better(best, JgBest{__uint_as_float(h), i + j});
-          }
-        }
-      }
-    }
-  }
-  if (lm_part == nullptr) return;  // uniform
-
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    JgBest y;
-    y.v = __shfl_xor(best.v, off, 64);
-    y.i = __shfl_xor(best.i, off, 64);
-    best = jg_better(best, y);
-  }
-  const int wid = threadIdx.x >> 6;
-  if (lane == 0) red[wid] = best;
-  __syncthreads();
-  JgBest wn = red[0];
-  for (int q = 1; q < JGT / 64; ++q) wn = jg_better(wn, red[q]);
-  uint32_t* pc = lm_part + (int64_t)r * lm_parts * 2;
-  for (int q = threadIdx.x; q < lm_parts; q += JGT) {
-    const uint2 cd = q == 0 ? make_uint2(__float_as_uint(wn.v), (uint32_t)wn.i) : make_uint2(0xff800000u, 0x7fffffffu);
-    *reinterpret_cast<uint2*>(pc + 2 * q) = cd;
-  }
+  guide_mask_row<GUIDE_T>(logits + (int64_t)r * stride, vocab, s_map,
+                          lm_part != nullptr ? lm_part + (int64_t)r * lm_parts * 2 : nullptr, lm_parts);
 }
 
 hipError_t launch_json_guide(bf16_t* logits, int64_t stride, int rows, int vocab, const int* slot, int num_slots,
                              const int* desc, const int16_t* trans, int64_t table_states, const int* tok_off,
                              int64_t n_tok, const uint8_t* tok_bytes, int64_t bytes_len, int* cur, int* jstk, int* err,
                              const int64_t* advance_ids, uint32_t* lm_part, int lm_parts, hipStream_t s) {
-  if (vocab <= 0 || vocab % 8 || rows < 0 || num_slots < 1) return hipErrorInvalidValue;
+  int map_words;
+  if (!guide_row_args_ok(vocab, stride, rows, num_slots, lm_part, lm_parts, &map_words)) return hipErrorInvalidValue;
   if (logits == nullptr || slot == nullptr || desc == nullptr || trans == nullptr || tok_off == nullptr ||
       tok_bytes == nullptr || cur == nullptr || jstk == nullptr || err == nullptr)
     return hipErrorInvalidValue;
-  if (stride < vocab || stride % 8) return hipErrorInvalidValue;
   if (table_states < 3 || table_states > GUIDE_JSON_MAX_STATES) return hipErrorInvalidValue;
-  // bytes_len >= 8: the kernel fetches a token's bytes eight at a time, from a window that lies inside the table
-  if (n_tok < 1 || n_tok > GUIDE_TOK_TABLE_MAX || bytes_len < 8 || bytes_len > GUIDE_TOK_BYTES_MAX)
-    return hipErrorInvalidValue;
+  if (!guide_tok_table_ok(n_tok, bytes_len)) return hipErrorInvalidValue;
   if (reinterpret_cast<uintptr_t>(trans) % 16) return hipErrorInvalidValue;  // the table's copy to LDS moves 16 B
   if (reinterpret_cast<uintptr_t>(jstk) % 8) return hipErrorInvalidValue;    // (depth, bits) is stored as one pair
-  if (lm_part != nullptr && lm_parts < 1) return hipErrorInvalidValue;
-  const int map_words = (vocab / 8 + 3) / 4;
-  if (map_words * 4 > JG_MAX_MAP_BYTES) return hipErrorInvalidValue;
   if (rows == 0) return hipSuccess;
   const int tr_off_words = (map_words + 3) & ~3;
   const int lds = tr_off_words * 4 + JG_TRANS_BYTES;
-  // more than 64 KiB of dynamic LDS has to be asked for, once per device
   static bool asked[64] = {};
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
+  const hipError_t e = guide_ask_dynamic_lds(reinterpret_cast<const void*>(json_guide_kernel),
+                                             GUIDE_MAX_MAP_BYTES + JG_TRANS_BYTES, asked);
   if (e != hipSuccess) return e;
-  if (dev < 0 || dev >= 64) return hipErrorInvalidValue;
-  if (!asked[dev]) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(json_guide_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, JG_MAX_MAP_BYTES + JG_TRANS_BYTES);
-    if (e != hipSuccess) return e;
-    asked[dev] = true;
-  }
-  hipLaunchKernelGGL(json_guide_kernel, dim3(rows), dim3(JGT), lds, s, logits, stride, vocab, slot, num_slots,
+  hipLaunchKernelGGL(json_guide_kernel, dim3(rows), dim3(GUIDE_T), lds, s, logits, stride, vocab, slot, num_slots,
                      reinterpret_cast<const int4*>(desc), trans, (int)table_states, tok_off, (int)n_tok, tok_bytes,
                      (int)bytes_len, cur, jstk, err, advance_ids, lm_part, lm_parts, map_words, tr_off_words);
   return hipGetLastError();

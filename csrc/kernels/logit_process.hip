@@ -25,8 +25,7 @@
 // agree with the rewritten row: candidate 0 = the processed row's (max, lowest index) in better()'s total order
 // (sampling.hip), the others (-inf, 0x7fffffff); the unchanged sampling tail then yields the processed argmax.
 // Rows stream 16 B per lane (logits load + state load + logits store: 750 KiB per 128256-entry row).
-#include "common.h"
-#include "launchers.h"
+#include "guide_common.h"  // Best, better() and the candidate write, shared with the guide kernels
 
 namespace die {
 
@@ -37,15 +36,6 @@ constexpr uint32_t LP_EMPTY = 0xffffffffu;
 static_assert(LP_HASH >= 2 * LOGIT_BIAS_MAX && (LP_HASH & (LP_HASH - 1)) == 0, "bias table size");
 
 __device__ __forceinline__ uint32_t lp_hash(uint32_t id) { return (id * 2654435761u) >> 22; }  // 10 bits
-
-struct LpBest {
-  float v;
-  int i;
-};
-// sampling.hip's better(): larger value first, then lower index
-__device__ __forceinline__ LpBest lp_better(LpBest a, LpBest b) {
-  return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
-}
 
 __global__ void __launch_bounds__(LPT) logit_process_kernel(bf16_t* __restrict__ logits, int64_t stride, int vocab,
                                                             const int* __restrict__ slot_of_row, int num_slots,
@@ -59,7 +49,6 @@ __global__ void __launch_bounds__(LPT) logit_process_kernel(bf16_t* __restrict__
   extern __shared__ uint32_t s_map[];  // bit t: token t has a bias entry
   __shared__ uint32_t s_key[LP_HASH];
   __shared__ float s_val[LP_HASH];
-  __shared__ LpBest red[LPT / 64];
   const int r = blockIdx.x;
   const int slot = slot_of_row[r];
   if (slot < 0 || slot >= num_slots) return;  // uniform
@@ -96,7 +85,7 @@ __global__ void __launch_bounds__(LPT) logit_process_kernel(bf16_t* __restrict__
   const uint8_t* map8 = reinterpret_cast<const uint8_t*>(s_map);
 
   constexpr int AU = 4;  // 16-B groups per lane in flight (logits and state: 8 loads)
-  LpBest best{-INFINITY, 0x7fffffff};
+  Best best{-INFINITY, 0x7fffffff};
   for (int i0 = threadIdx.x * 8; i0 < vocab; i0 += LPT * 8 * AU) {
     uint4 lv[AU], sv[AU];
 #pragma unroll
@@ -140,29 +129,12 @@ __global__ void __launch_bounds__(LPT) logit_process_kernel(bf16_t* __restrict__
       if (lm_part != nullptr) {
         unpack8(ov, o);  // the values as the sampler will read them
 #pragma unroll
-        for (int j = 0; j < 8; ++j) best = lp_better(best, LpBest{o[j], i + j});
+        for (int j = 0; j < 8; ++j) best = better(best, Best{o[j], i + j});
       }
     }
   }
   if (lm_part == nullptr) return;  // uniform
-
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    LpBest y;
-    y.v = __shfl_xor(best.v, off, 64);
-    y.i = __shfl_xor(best.i, off, 64);
-    best = lp_better(best, y);
-  }
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  if (lane == 0) red[wid] = best;
-  __syncthreads();
-  LpBest w = red[0];
-  for (int q = 1; q < LPT / 64; ++q) w = lp_better(w, red[q]);
-  uint32_t* pc = lm_part + (int64_t)r * lm_parts * 2;
-  for (int q = threadIdx.x; q < lm_parts; q += LPT) {
-    const uint2 c = q == 0 ? make_uint2(__float_as_uint(w.v), (uint32_t)w.i) : make_uint2(0xff800000u, 0x7fffffffu);
-    *reinterpret_cast<uint2*>(pc + 2 * q) = c;
-  }
+  write_best_candidate<LPT>(best, lm_part + (int64_t)r * lm_parts * 2, lm_parts);
 }
 
 hipError_t launch_logit_process(bf16_t* logits, int64_t stride, int rows, int vocab, const int* slot, int num_slots,

@@ -31,16 +31,17 @@
 //      err |= GUIDE_ERR_NO_EDGE. The configuration is kept in every such case.
 //   3. Token t is allowed next: in the sink only EOS; else EOS iff the state accepts and the depth is 0; else iff
 //      t < min(vocab, n_tok), it has 1..GUIDE_MAX_TOKEN_BYTES bytes and its walk from the current configuration
-//      never dies. One lane per token, SG_TU independent chains per lane in flight, level by level, a chain's bytes
+//      never dies. One lane per token, GUIDE_TU independent chains per lane in flight, level by level, a chain's bytes
 //      fetched eight at a time; state, depth, the push register and its count are updated by selects, not branches
 //      (byte_guide.hip's header has the measurement behind that); a wave's 64 verdicts become two bitmap words by
-//      ballot. The table is read from the arena through L2: a guide may hold 16 MiB. Copying a small guide's rows
-//      to LDS behind the bitmap first was built and measured, and did not pay: 856.1 us against 856.8 us per launch
-//      at 32 x 128,256 for the 88 states of {"type": "object"} (docs/performance.md), so no copy is made.
-//   4. The dense pass over the row and the rewrite of the LM-head candidates are json_guide's: a barred entry becomes
-//      bf16 -inf (0xFF80), an allowed entry keeps its exact bits; a 16-B group with no allowed entry is stored
-//      without being loaded, one with all eight is not stored; lm_part != nullptr: candidate 0 = the best ALLOWED
-//      entry in sampling.hip's better() order, the others (-inf, 0x7fffffff).
+//      ballot (guide_common.h has the fetch and the ballot write-out). The table is read from the arena through L2:
+//      a guide may hold 16 MiB. Copying a small guide's rows to LDS behind the bitmap first was built and measured,
+//      and did not pay: 856.1 us against 856.8 us per launch at 32 x 128,256 for the 88 states of {"type": "object"}
+//      (docs/performance.md), so no copy is made.
+//   4. The dense pass over the row and the rewrite of the LM-head candidates are guide_common.h's guide_mask_row: a
+//      barred entry becomes bf16 -inf (0xFF80), an allowed entry keeps its exact bits; a 16-B group with no allowed
+//      entry is stored without being loaded, one with all eight is not stored; lm_part != nullptr: candidate 0 = the
+//      best ALLOWED entry in sampling.hip's better() order, the others (-inf, 0x7fffffff).
 //   5. Everything is checked BEFORE it is used as an index: the region within the arena, n_states in
 //      [1, GUIDE_MAX_STATES], state in [0, n_states], depth in [0, 32], every live stack entry in [0, n_states), eos
 //      in [0, vocab), 0 <= off[t] <= off[t + 1] <= bytes_len for every token looked at, and every entry READ (the
@@ -49,28 +50,14 @@
 //      sdep and sstk stay untouched — which is why the bitmap is complete before anything is written. No table
 //      content leads to an out-of-range access.
 // Plain C++ and vector stores only.
-#include "common.h"
-#include "launchers.h"
+#include "guide_common.h"
 
 namespace die {
 
-constexpr int SGT = 1024;
-constexpr int SG_MAX_MAP_BYTES = 48 * 1024;  // the bitmap's share of LDS: vocab <= 393216 (as byte_guide)
-constexpr uint32_t SG_NINF2 = 0xFF80FF80u;   // two bf16 -inf
-constexpr int SG_TU = 4;                     // tokens (independent chains) per lane in flight
 constexpr int SG_STATE_MASK = 0x3fff;
 static_assert(GUIDE_SCHEMA_MAX_DEPTH == 32, "the stack index is masked with 31");
 static_assert(GUIDE_SCHEMA_TOKEN_PUSHES == 4, "a chain's pushes are four 16-bit fields of one 64-bit register");
 static_assert(GUIDE_MAX_STATES <= SG_STATE_MASK + 1, "a state is a 14-bit field");
-
-struct SgBest {
-  float v;
-  int i;
-};
-// sampling.hip's better(): larger value first, then lower index
-__device__ __forceinline__ SgBest sg_better(SgBest a, SgBest b) {
-  return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
-}
 
 // One byte from configuration (s, d) with the chain's own pushes (ov, cnt) over table entry v, by selects. stk: the
 // sequence's stack in LDS, 32 entries, every live one below n_states. s becomes -1 when the walk dies (no
@@ -104,14 +91,13 @@ __device__ __forceinline__ bool sg_walk_tokens(const int* __restrict__ tr, int n
                                                const uint8_t* __restrict__ tok_bytes, int bytes_len, uint32_t* s_map,
                                                int map_words) {
   bool bad = false;
-  const int lane = threadIdx.x & 63;
-  for (int t0 = 0; t0 < lim; t0 += SGT * SG_TU) {
-    int s[SG_TU], p[SG_TU], e[SG_TU], d[SG_TU], cnt[SG_TU];
-    unsigned long long ov[SG_TU];  // the chain's own pushes, the latest in the low 16 bits
-    unsigned long long w[SG_TU];   // the chain's next bytes, lowest first
+  for (int t0 = 0; t0 < lim; t0 += GUIDE_T * GUIDE_TU) {
+    int s[GUIDE_TU], p[GUIDE_TU], e[GUIDE_TU], d[GUIDE_TU], cnt[GUIDE_TU];
+    unsigned long long ov[GUIDE_TU];  // the chain's own pushes, the latest in the low 16 bits
+    unsigned long long w[GUIDE_TU];   // the chain's next bytes, lowest first
 #pragma unroll
-    for (int u = 0; u < SG_TU; ++u) {
-      const int t = t0 + u * SGT + (int)threadIdx.x;
+    for (int u = 0; u < GUIDE_TU; ++u) {
+      const int t = t0 + u * GUIDE_T + (int)threadIdx.x;
       w[u] = ov[u] = 0ull;
       s[u] = -1;
       p[u] = e[u] = cnt[u] = 0;
@@ -128,36 +114,28 @@ __device__ __forceinline__ bool sg_walk_tokens(const int* __restrict__ tr, int n
       }
     }
     for (int step = 0; step < GUIDE_MAX_TOKEN_BYTES; ++step) {
-      bool act[SG_TU], any = false;
+      bool act[GUIDE_TU], any = false;
 #pragma unroll
-      for (int u = 0; u < SG_TU; ++u) {
+      for (int u = 0; u < GUIDE_TU; ++u) {
         act[u] = s[u] >= 0 && p[u] < e[u];
         any |= act[u];
       }
       if (__ballot(any) == 0ull) break;  // nothing left to read in this wave
-      if ((step & 7) == 0) {
-        // every eighth step (uniform) a chain fetches its next eight bytes in one load. The window [q, q + 8) is
-        // pulled back from the table's end (the launcher requires bytes_len >= 8); p - q <= 7 because p < e <=
-        // bytes_len. A lane with nothing to read loads the table's head: the loads stay unconditional
+      if ((step & 7) == 0) {  // uniform
 #pragma unroll
-        for (int u = 0; u < SG_TU; ++u) {
-          const int q = act[u] ? (p[u] < bytes_len - 8 ? p[u] : bytes_len - 8) : 0;
-          unsigned long long x;
-          __builtin_memcpy(&x, tok_bytes + q, 8);
-          w[u] = x >> (8 * (act[u] ? p[u] - q : 0));
-        }
+        for (int u = 0; u < GUIDE_TU; ++u) w[u] = guide_next_bytes(tok_bytes, bytes_len, act[u], p[u]);
       }
-      int b[SG_TU], v[SG_TU];
+      int b[GUIDE_TU], v[GUIDE_TU];
 #pragma unroll
-      for (int u = 0; u < SG_TU; ++u) {
+      for (int u = 0; u < GUIDE_TU; ++u) {
         b[u] = (int)(w[u] & 0xffull);
         w[u] >>= 8;
       }
       // an active chain's s is in [0, n_states): it starts at c < n_states and sg_step keeps it there
 #pragma unroll
-      for (int u = 0; u < SG_TU; ++u) v[u] = tr[(act[u] ? s[u] : 0) * 256 + b[u]];
+      for (int u = 0; u < GUIDE_TU; ++u) v[u] = tr[(act[u] ? s[u] : 0) * 256 + b[u]];
 #pragma unroll
-      for (int u = 0; u < SG_TU; ++u) {  // selects, not branches: the chains stay one instruction stream
+      for (int u = 0; u < GUIDE_TU; ++u) {  // selects, not branches: the chains stay one instruction stream
         int sn = s[u], dn = d[u], cn = cnt[u];
         unsigned long long on = ov[u];
         const bool oob = sg_step(v[u], n_states, stk, sn, dn, on, cn);
@@ -170,34 +148,27 @@ __device__ __forceinline__ bool sg_walk_tokens(const int* __restrict__ tr, int n
       }
     }
 #pragma unroll
-    for (int u = 0; u < SG_TU; ++u) {
-      const unsigned long long m = __ballot(s[u] >= 0);
-      const int wi = (t0 + u * SGT + (int)threadIdx.x - lane) >> 5;  // the wave's 64 tokens start at a multiple of 64
-      if (lane == 0) {
-        if (wi < map_words) s_map[wi] = (uint32_t)m;
-        if (wi + 1 < map_words) s_map[wi + 1] = (uint32_t)(m >> 32);
-      }
-    }
+    for (int u = 0; u < GUIDE_TU; ++u)
+      guide_write_verdicts(s_map, map_words, t0 + u * GUIDE_T + (int)threadIdx.x, s[u] >= 0);
   }
   return bad;
 }
 
-__global__ void __launch_bounds__(SGT) schema_guide_kernel(bf16_t* __restrict__ logits, int64_t stride, int vocab,
-                                                           const int* __restrict__ slot_of_row, int num_slots,
-                                                           const int4* __restrict__ desc,
-                                                           const int* __restrict__ trans,
-                                                           const uint8_t* __restrict__ accept, int arena_states,
-                                                           const int* __restrict__ tok_off, int n_tok,
-                                                           const uint8_t* __restrict__ tok_bytes, int bytes_len,
-                                                           int* __restrict__ cur, int* __restrict__ sdep,
-                                                           int16_t* __restrict__ sstk, int* __restrict__ err,
-                                                           const int64_t* __restrict__ advance_ids,
-                                                           uint32_t* __restrict__ lm_part, int lm_parts,
-                                                           int map_words) {
+__global__ void __launch_bounds__(GUIDE_T) schema_guide_kernel(bf16_t* __restrict__ logits, int64_t stride, int vocab,
+                                                               const int* __restrict__ slot_of_row, int num_slots,
+                                                               const int4* __restrict__ desc,
+                                                               const int* __restrict__ trans,
+                                                               const uint8_t* __restrict__ accept, int arena_states,
+                                                               const int* __restrict__ tok_off, int n_tok,
+                                                               const uint8_t* __restrict__ tok_bytes, int bytes_len,
+                                                               int* __restrict__ cur, int* __restrict__ sdep,
+                                                               int16_t* __restrict__ sstk, int* __restrict__ err,
+                                                               const int64_t* __restrict__ advance_ids,
+                                                               uint32_t* __restrict__ lm_part, int lm_parts,
+                                                               int map_words) {
   extern __shared__ uint32_t s_map[];  // bit t: token t is allowed
   __shared__ int s_stk[GUIDE_SCHEMA_MAX_DEPTH];
   __shared__ int s_bad;
-  __shared__ SgBest red[SGT / 64];
   const int r = blockIdx.x;
   const int slot = slot_of_row[r];
   if (slot < 0 || slot >= num_slots) return;  // uniform
@@ -276,7 +247,7 @@ __global__ void __launch_bounds__(SGT) schema_guide_kernel(bf16_t* __restrict__ 
   // d - acnt >= 0 (each held push raised d by one) and d <= 32
   if ((int)threadIdx.x < acnt)
     s_stk[d - acnt + (int)threadIdx.x] = (int)((aov >> (16 * (acnt - 1 - (int)threadIdx.x))) & 0xffffull);
-  for (int w = threadIdx.x; w < map_words; w += SGT) s_map[w] = 0u;
+  for (int w = threadIdx.x; w < map_words; w += GUIDE_T) s_map[w] = 0u;
   if (threadIdx.x == 0) s_bad = 0;
   __syncthreads();
   if (c == n_states) {
@@ -308,72 +279,8 @@ __global__ void __launch_bounds__(SGT) schema_guide_kernel(bf16_t* __restrict__ 
     const int at = d - acnt + (int)threadIdx.x;
     sstk[slot * GUIDE_SCHEMA_MAX_DEPTH + at] = (int16_t)s_stk[at];
   }
-  const uint8_t* map8 = reinterpret_cast<const uint8_t*>(s_map);
-  bf16_t* row = logits + (int64_t)r * stride;
-  const int lane = threadIdx.x & 63;
-
-  constexpr int AU = 4;  // 16-B groups per lane in flight
-  SgBest best{-INFINITY, 0x7fffffff};
-  for (int i0 = threadIdx.x * 8; i0 < vocab; i0 += SGT * 8 * AU) {
-    uint4 lv[AU];
-    uint32_t mb[AU];
-#pragma unroll
-    for (int u = 0; u < AU; ++u) {
-      const int i = i0 + u * SGT * 8;
-      mb[u] = 0u;
-      if (i < vocab) {
-        mb[u] = (uint32_t)map8[i >> 3];
-        if (mb[u] != 0u) lv[u] = *reinterpret_cast<const uint4*>(row + i);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < AU; ++u) {
-      const int i = i0 + u * SGT * 8;
-      if (i >= vocab) continue;
-      const uint32_t m = mb[u];
-      if (m == 0u) {  // nothing allowed here: the group was not loaded
-        *reinterpret_cast<uint4*>(row + i) = make_uint4(SG_NINF2, SG_NINF2, SG_NINF2, SG_NINF2);
-        continue;
-      }
-      uint32_t w[4] = {lv[u].x, lv[u].y, lv[u].z, lv[u].w};
-      if (m != 0xffu) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (!(m & (1u << (2 * j)))) w[j] = (w[j] & 0xffff0000u) | 0xFF80u;
-          if (!(m & (1u << (2 * j + 1)))) w[j] = (w[j] & 0x0000ffffu) | 0xFF800000u;
-        }
-        *reinterpret_cast<uint4*>(row + i) = make_uint4(w[0], w[1], w[2], w[3]);
-      }
-      if (lm_part != nullptr) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          if (m & (1u << j)) {
-            const uint32_t h = (j & 1) ? (w[j >> 1] & 0xffff0000u) : (w[j >> 1] << 16);
-            best = sg_better(best, SgBest{__uint_as_float(h), i + j});
-          }
-        }
-      }
-    }
-  }
-  if (lm_part == nullptr) return;  // uniform
-
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    SgBest y;
-    y.v = __shfl_xor(best.v, off, 64);
-    y.i = __shfl_xor(best.i, off, 64);
-    best = sg_better(best, y);
-  }
-  const int wid = threadIdx.x >> 6;
-  if (lane == 0) red[wid] = best;
-  __syncthreads();
-  SgBest wn = red[0];
-  for (int q = 1; q < SGT / 64; ++q) wn = sg_better(wn, red[q]);
-  uint32_t* pc = lm_part + (int64_t)r * lm_parts * 2;
-  for (int q = threadIdx.x; q < lm_parts; q += SGT) {
-    const uint2 cd = q == 0 ? make_uint2(__float_as_uint(wn.v), (uint32_t)wn.i) : make_uint2(0xff800000u, 0x7fffffffu);
-    *reinterpret_cast<uint2*>(pc + 2 * q) = cd;
-  }
+  guide_mask_row<GUIDE_T>(logits + (int64_t)r * stride, vocab, s_map,
+                          lm_part != nullptr ? lm_part + (int64_t)r * lm_parts * 2 : nullptr, lm_parts);
 }
 
 hipError_t launch_schema_guide(bf16_t* logits, int64_t stride, int rows, int vocab, const int* slot, int num_slots,
@@ -381,22 +288,17 @@ hipError_t launch_schema_guide(bf16_t* logits, int64_t stride, int rows, int voc
                                int64_t accept_len, const int* tok_off, int64_t n_tok, const uint8_t* tok_bytes,
                                int64_t bytes_len, int* cur, int* sdep, int16_t* sstk, int* err,
                                const int64_t* advance_ids, uint32_t* lm_part, int lm_parts, hipStream_t s) {
-  if (vocab <= 0 || vocab % 8 || rows < 0 || num_slots < 1) return hipErrorInvalidValue;
+  int map_words;
+  if (!guide_row_args_ok(vocab, stride, rows, num_slots, lm_part, lm_parts, &map_words)) return hipErrorInvalidValue;
   if (logits == nullptr || slot == nullptr || desc == nullptr || trans == nullptr || accept == nullptr ||
       tok_off == nullptr || tok_bytes == nullptr || cur == nullptr || sdep == nullptr || sstk == nullptr ||
       err == nullptr)
     return hipErrorInvalidValue;
-  if (stride < vocab || stride % 8) return hipErrorInvalidValue;
   const int64_t arena = trans_states < accept_len ? trans_states : accept_len;
   if (arena < 1 || arena > GUIDE_SCHEMA_STATE_ARENA) return hipErrorInvalidValue;
-  // bytes_len >= 8: the kernel fetches a token's bytes eight at a time, from a window that lies inside the table
-  if (n_tok < 1 || n_tok > GUIDE_TOK_TABLE_MAX || bytes_len < 8 || bytes_len > GUIDE_TOK_BYTES_MAX)
-    return hipErrorInvalidValue;
-  if (lm_part != nullptr && lm_parts < 1) return hipErrorInvalidValue;
-  const int map_words = (vocab / 8 + 3) / 4;
-  if (map_words * 4 > SG_MAX_MAP_BYTES) return hipErrorInvalidValue;
+  if (!guide_tok_table_ok(n_tok, bytes_len)) return hipErrorInvalidValue;
   if (rows == 0) return hipSuccess;
-  hipLaunchKernelGGL(schema_guide_kernel, dim3(rows), dim3(SGT), map_words * 4, s, logits, stride, vocab, slot,
+  hipLaunchKernelGGL(schema_guide_kernel, dim3(rows), dim3(GUIDE_T), map_words * 4, s, logits, stride, vocab, slot,
                      num_slots, reinterpret_cast<const int4*>(desc), trans, accept, (int)arena, tok_off, (int)n_tok,
                      tok_bytes, (int)bytes_len, cur, sdep, sstk, err, advance_ids, lm_part, lm_parts, map_words);
   return hipGetLastError();

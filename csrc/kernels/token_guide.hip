@@ -14,46 +14,34 @@
 //      a state). No such edge: err |= GUIDE_ERR_NO_EDGE and the state is kept.
 //   2. The (new) state's edge tokens become a bitmap in LDS (vocab / 8 bytes, one BYTE per 16-B group). Both edge
 //      loops keep TG_EU loads per lane in flight.
-//   3. One dense pass: a barred entry becomes bf16 -inf (0xFF80), an allowed entry keeps its exact bits. A group
-//      with no allowed entry is stored without being loaded, a group with all eight allowed is not stored.
-//   4. lm_part != nullptr: the row's LM-head candidates are rewritten as logit_process does: candidate 0 = the
-//      best ALLOWED entry in better()'s order (sampling.hip), the others (-inf, 0x7fffffff).
+//   3. One dense pass (guide_common.h's guide_mask_row): a barred entry becomes bf16 -inf (0xFF80), an allowed entry
+//      keeps its exact bits. A group with no allowed entry is stored without being loaded, a group with all eight
+//      allowed is not stored.
+//   4. lm_part != nullptr: the row's LM-head candidates are rewritten by the same pass (guide_common.h's
+//      write_best_candidate): candidate 0 = the best ALLOWED entry in better()'s order (sampling.hip), the others
+//      (-inf, 0x7fffffff).
 //   5. Every index is checked against its descriptor and every descriptor against the arena sizes BEFORE use: a
 //      descriptor outside its arena, a state outside [0, n_states), a row pointer outside [0, n_edges] or
 //      descending, a next state outside [0, n_states), an edge token outside [0, vocab): err |= GUIDE_ERR_TABLE,
 //      the row, the candidates and cur stay untouched. No table content leads to an out-of-range access.
 // A slot belongs to one row of a launch (the runner maps one sequence to one slot), so cur / err have one writer.
 // Rows stream 16 B per lane: at most one load and one store per group, 500 KiB per 128256-entry row.
-#include "common.h"
-#include "launchers.h"
+#include "guide_common.h"
 
 namespace die {
 
-constexpr int TGT = 1024;
-constexpr int TG_MAX_MAP_BYTES = 48 * 1024;  // the bitmap's share of LDS: vocab <= 393216 (as logit_process)
-constexpr uint32_t TG_NINF2 = 0xFF80FF80u;   // two bf16 -inf
-constexpr int TG_EU = 8;                     // edges per lane in flight in the two edge loops
+constexpr int TG_EU = 8;  // edges per lane in flight in the two edge loops
 
-struct TgBest {
-  float v;
-  int i;
-};
-// sampling.hip's better(): larger value first, then lower index
-__device__ __forceinline__ TgBest tg_better(TgBest a, TgBest b) {
-  return (b.v > a.v || (b.v == a.v && b.i < a.i)) ? b : a;
-}
-
-__global__ void __launch_bounds__(TGT) token_guide_kernel(bf16_t* __restrict__ logits, int64_t stride, int vocab,
-                                                          const int* __restrict__ slot_of_row, int num_slots,
-                                                          const int4* __restrict__ desc,
-                                                          const int* __restrict__ rowptr, int rowptr_len,
-                                                          const int2* __restrict__ edges, int edges_len,
-                                                          int* __restrict__ cur, int* __restrict__ err,
-                                                          const int64_t* __restrict__ advance_ids,
-                                                          uint32_t* __restrict__ lm_part, int lm_parts) {
+__global__ void __launch_bounds__(GUIDE_T) token_guide_kernel(bf16_t* __restrict__ logits, int64_t stride, int vocab,
+                                                              const int* __restrict__ slot_of_row, int num_slots,
+                                                              const int4* __restrict__ desc,
+                                                              const int* __restrict__ rowptr, int rowptr_len,
+                                                              const int2* __restrict__ edges, int edges_len,
+                                                              int* __restrict__ cur, int* __restrict__ err,
+                                                              const int64_t* __restrict__ advance_ids,
+                                                              uint32_t* __restrict__ lm_part, int lm_parts) {
   extern __shared__ uint32_t s_map[];  // bit t: token t is allowed
   __shared__ int s_hit, s_next, s_bad;
-  __shared__ TgBest red[TGT / 64];
   const int r = blockIdx.x;
   const int slot = slot_of_row[r];
   if (slot < 0 || slot >= num_slots) return;  // uniform
@@ -80,17 +68,17 @@ __global__ void __launch_bounds__(TGT) token_guide_kernel(bf16_t* __restrict__ l
     }
     if (threadIdx.x == 0) s_hit = 0;
     __syncthreads();
-    for (int e0 = lo + threadIdx.x; e0 < hi; e0 += TGT * TG_EU) {
+    for (int e0 = lo + threadIdx.x; e0 < hi; e0 += GUIDE_T * TG_EU) {
       int2 ev[TG_EU];
 #pragma unroll
       for (int u = 0; u < TG_EU; ++u) {
-        const int e = e0 + u * TGT;
+        const int e = e0 + u * GUIDE_T;
         if (e < hi) ev[u] = ed[e];
       }
 #pragma unroll
       for (int u = 0; u < TG_EU; ++u) {
         // unique within a state by contract; were it not, one of the writers wins
-        if (e0 + u * TGT < hi && (int64_t)ev[u].x == tok) {
+        if (e0 + u * GUIDE_T < hi && (int64_t)ev[u].x == tok) {
           s_next = ev[u].y;
           s_hit = 1;
         }
@@ -114,7 +102,7 @@ __global__ void __launch_bounds__(TGT) token_guide_kernel(bf16_t* __restrict__ l
     return;
   }
   const int words = (vocab / 8 + 3) / 4;
-  for (int w = threadIdx.x; w < words; w += TGT) s_map[w] = 0u;
+  for (int w = threadIdx.x; w < words; w += GUIDE_T) s_map[w] = 0u;
   if (threadIdx.x == 0) s_bad = 0;
   __syncthreads();
   // Tokens ascend within a state, so the lanes of a wave that hit one bitmap word are neighbours: a segmented OR
@@ -125,17 +113,17 @@ __global__ void __launch_bounds__(TGT) token_guide_kernel(bf16_t* __restrict__ l
   // single row costs the same as 32): a state with n edges adds about n / 1500 us. Next step, not taken here:
   // stage the tokens through LDS so that a lane combines 8 consecutive edges in registers, without shuffles.
   const int lane = threadIdx.x & 63;
-  for (int e0 = lo; e0 < hi; e0 += TGT * TG_EU) {  // uniform trip count: the shuffles need every lane
+  for (int e0 = lo; e0 < hi; e0 += GUIDE_T * TG_EU) {  // uniform trip count: the shuffles need every lane
     int tk[TG_EU];
 #pragma unroll
     for (int u = 0; u < TG_EU; ++u) {
-      const int e = e0 + u * TGT + (int)threadIdx.x;
+      const int e = e0 + u * GUIDE_T + (int)threadIdx.x;
       if (e < hi) tk[u] = ed[e].x;
     }
 #pragma unroll
     for (int u = 0; u < TG_EU; ++u) {
-      if (e0 + u * TGT >= hi) break;  // uniform
-      const int e = e0 + u * TGT + (int)threadIdx.x;
+      if (e0 + u * GUIDE_T >= hi) break;  // uniform
+      const int e = e0 + u * GUIDE_T + (int)threadIdx.x;
       uint32_t w = 0x80000000u | (uint32_t)lane, b = 0u;  // no edge, or a bad one: a word of its own, no bit
       if (e < hi) {
         const int t = tk[u];
@@ -164,91 +152,25 @@ __global__ void __launch_bounds__(TGT) token_guide_kernel(bf16_t* __restrict__ l
     cur[slot] = c;
     if (flags) err[slot] |= flags;
   }
-  const uint8_t* map8 = reinterpret_cast<const uint8_t*>(s_map);
-  bf16_t* row = logits + (int64_t)r * stride;
-
-  constexpr int AU = 4;  // 16-B groups per lane in flight
-  TgBest best{-INFINITY, 0x7fffffff};
-  for (int i0 = threadIdx.x * 8; i0 < vocab; i0 += TGT * 8 * AU) {
-    uint4 lv[AU];
-    uint32_t mb[AU];
-#pragma unroll
-    for (int u = 0; u < AU; ++u) {
-      const int i = i0 + u * TGT * 8;
-      mb[u] = 0u;
-      if (i < vocab) {
-        mb[u] = (uint32_t)map8[i >> 3];
-        if (mb[u] != 0u) lv[u] = *reinterpret_cast<const uint4*>(row + i);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < AU; ++u) {
-      const int i = i0 + u * TGT * 8;
-      if (i >= vocab) continue;
-      const uint32_t m = mb[u];
-      if (m == 0u) {  // nothing allowed here: the group was not loaded
-        *reinterpret_cast<uint4*>(row + i) = make_uint4(TG_NINF2, TG_NINF2, TG_NINF2, TG_NINF2);
-        continue;
-      }
-      uint32_t w[4] = {lv[u].x, lv[u].y, lv[u].z, lv[u].w};
-      if (m != 0xffu) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          if (!(m & (1u << (2 * j)))) w[j] = (w[j] & 0xffff0000u) | 0xFF80u;
-          if (!(m & (1u << (2 * j + 1)))) w[j] = (w[j] & 0x0000ffffu) | 0xFF800000u;
-        }
-        *reinterpret_cast<uint4*>(row + i) = make_uint4(w[0], w[1], w[2], w[3]);
-      }
-      if (lm_part != nullptr) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          if (m & (1u << j)) {
-            const uint32_t h = (j & 1) ? (w[j >> 1] & 0xffff0000u) : (w[j >> 1] << 16);
-            best = tg_better(best, TgBest{__uint_as_float(h), i + j});
-          }
-        }
-      }
-    }
-  }
-  if (lm_part == nullptr) return;  // uniform
-
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    TgBest y;
-    y.v = __shfl_xor(best.v, off, 64);
-    y.i = __shfl_xor(best.i, off, 64);
-    best = tg_better(best, y);
-  }
-  const int wid = threadIdx.x >> 6;
-  if (lane == 0) red[wid] = best;
-  __syncthreads();
-  TgBest wn = red[0];
-  for (int q = 1; q < TGT / 64; ++q) wn = tg_better(wn, red[q]);
-  uint32_t* pc = lm_part + (int64_t)r * lm_parts * 2;
-  for (int q = threadIdx.x; q < lm_parts; q += TGT) {
-    const uint2 cd = q == 0 ? make_uint2(__float_as_uint(wn.v), (uint32_t)wn.i) : make_uint2(0xff800000u, 0x7fffffffu);
-    *reinterpret_cast<uint2*>(pc + 2 * q) = cd;
-  }
+  guide_mask_row<GUIDE_T>(logits + (int64_t)r * stride, vocab, s_map,
+                          lm_part != nullptr ? lm_part + (int64_t)r * lm_parts * 2 : nullptr, lm_parts);
 }
 
 hipError_t launch_token_guide(bf16_t* logits, int64_t stride, int rows, int vocab, const int* slot, int num_slots,
                               const int* desc, const int* rowptr, int64_t rowptr_len, const int* edges,
                               int64_t edges_len, int* cur, int* err, const int64_t* advance_ids, uint32_t* lm_part,
                               int lm_parts, hipStream_t s) {
-  if (vocab <= 0 || vocab % 8 || rows < 0 || num_slots < 1) return hipErrorInvalidValue;
+  int map_words;
+  if (!guide_row_args_ok(vocab, stride, rows, num_slots, lm_part, lm_parts, &map_words)) return hipErrorInvalidValue;
   if (logits == nullptr || slot == nullptr || desc == nullptr || rowptr == nullptr || edges == nullptr ||
       cur == nullptr || err == nullptr)
     return hipErrorInvalidValue;
-  if (stride < vocab || stride % 8) return hipErrorInvalidValue;
   if (rowptr_len < 2 || rowptr_len > GUIDE_ROWPTR_ARENA || edges_len < 1 || edges_len > GUIDE_EDGE_ARENA)
     return hipErrorInvalidValue;
-  if (lm_part != nullptr && lm_parts < 1) return hipErrorInvalidValue;
-  const int map_bytes = ((vocab / 8 + 3) / 4) * 4;
-  if (map_bytes > TG_MAX_MAP_BYTES) return hipErrorInvalidValue;
   if (rows == 0) return hipSuccess;
-  hipLaunchKernelGGL(token_guide_kernel, dim3(rows), dim3(TGT), map_bytes, s, logits, stride, vocab, slot, num_slots,
-                     reinterpret_cast<const int4*>(desc), rowptr, (int)rowptr_len, reinterpret_cast<const int2*>(edges),
-                     (int)edges_len, cur, err, advance_ids, lm_part, lm_parts);
+  hipLaunchKernelGGL(token_guide_kernel, dim3(rows), dim3(GUIDE_T), map_words * 4, s, logits, stride, vocab, slot,
+                     num_slots, reinterpret_cast<const int4*>(desc), rowptr, (int)rowptr_len,
+                     reinterpret_cast<const int2*>(edges), (int)edges_len, cur, err, advance_ids, lm_part, lm_parts);
   return hipGetLastError();
 }
 

@@ -228,6 +228,24 @@ GUIDE_ERR_NO_EDGE = 1  # err bits of token_guide: the advance token has no edge 
 GUIDE_ERR_TABLE = 2    # a descriptor, state, row pointer or edge outside its bounds: the row is left untouched
 
 
+def _guide_mask_row(logits, r, vocab, allowed, lm_part):
+    """The tail of every *_guide_rows: row r's entries outside allowed (bool [vocab]) become -inf, the others keep
+    their bits; lm_part candidates are overwritten with the best allowed entry (largest value, then lowest index)."""
+    logits[r, :vocab] = torch.where(allowed, logits[r, :vocab], torch.tensor(float("-inf"), dtype=logits.dtype))
+    if lm_part is None:
+        return
+    x = logits[r, :vocab].float()
+    ok = allowed & ~torch.isnan(x)  # a NaN never wins a comparison (sampling.hip's better())
+    x = torch.where(ok, x, torch.tensor(float("-inf")))
+    v = x.max()
+    first = ((x == v) & ok).nonzero()  # lowest allowed index holding the maximum
+    lm_part[r, :, 0] = torch.tensor(float("-inf")).view(torch.int32)
+    lm_part[r, :, 1] = 0x7fffffff
+    if first.numel():
+        lm_part[r, 0, 0] = x[int(first[0])].view(torch.int32)  # that entry's own bits (-0.0 equals +0.0)
+        lm_part[r, 0, 1] = int(first[0])
+
+
 def token_guide_rows(logits, slot, desc, rowptr, edges, cur, err, advance_ids=None, lm_part=None):
     """ops.token_guide on host tensors (the contract of csrc/kernels/token_guide.hip): row r -> slot[r] -> desc
     (state_base, n_states, edge_base, n_edges) into rowptr / edges [E, 2]; the state advances over advance_ids[r]
@@ -273,19 +291,7 @@ def token_guide_rows(logits, slot, desc, rowptr, edges, cur, err, advance_ids=No
         err[s] |= flags
         allowed = torch.zeros(vocab, dtype=torch.bool)
         allowed[toks] = True
-        logits[r, :vocab] = torch.where(allowed, logits[r, :vocab],
-                                        torch.tensor(float("-inf"), dtype=logits.dtype))
-        if lm_part is not None:
-            x = logits[r, :vocab].float()
-            ok = allowed & ~torch.isnan(x)  # a NaN never wins a comparison (sampling.hip's better())
-            x = torch.where(ok, x, torch.tensor(float("-inf")))
-            v = x.max()
-            first = ((x == v) & ok).nonzero()  # lowest allowed index holding the maximum
-            lm_part[r, :, 0] = torch.tensor(float("-inf")).view(torch.int32)
-            lm_part[r, :, 1] = 0x7fffffff
-            if first.numel():
-                lm_part[r, 0, 0] = x[int(first[0])].view(torch.int32)  # that entry's own bits (-0.0 equals +0.0)
-                lm_part[r, 0, 1] = int(first[0])
+        _guide_mask_row(logits, r, vocab, allowed, lm_part)
     return logits
 
 
@@ -369,20 +375,7 @@ def byte_guide_rows(logits, slot, desc, trans, accept, tok_off, tok_bytes, cur, 
             continue
         cur[s] = c
         err[s] |= flags
-        allowed = torch.from_numpy(allowed)
-        logits[r, :vocab] = torch.where(allowed, logits[r, :vocab],
-                                        torch.tensor(float("-inf"), dtype=logits.dtype))
-        if lm_part is not None:
-            x = logits[r, :vocab].float()
-            ok = allowed & ~torch.isnan(x)  # a NaN never wins a comparison (sampling.hip's better())
-            x = torch.where(ok, x, torch.tensor(float("-inf")))
-            v = x.max()
-            first = ((x == v) & ok).nonzero()  # lowest allowed index holding the maximum
-            lm_part[r, :, 0] = torch.tensor(float("-inf")).view(torch.int32)
-            lm_part[r, :, 1] = 0x7fffffff
-            if first.numel():
-                lm_part[r, 0, 0] = x[int(first[0])].view(torch.int32)  # that entry's own bits (-0.0 equals +0.0)
-                lm_part[r, 0, 1] = int(first[0])
+        _guide_mask_row(logits, r, vocab, torch.from_numpy(allowed), lm_part)
     return logits
 
 
@@ -494,20 +487,7 @@ def json_guide_rows(logits, slot, desc, trans, tok_off, tok_bytes, cur, jstk, er
         jstk[s, 0] = d
         jstk[s, 1] = k - (1 << 32) if k >= 1 << 31 else k
         err[s] |= flags
-        allowed = torch.from_numpy(allowed)
-        logits[r, :vocab] = torch.where(allowed, logits[r, :vocab],
-                                        torch.tensor(float("-inf"), dtype=logits.dtype))
-        if lm_part is not None:
-            x = logits[r, :vocab].float()
-            ok = allowed & ~torch.isnan(x)  # a NaN never wins a comparison (sampling.hip's better())
-            x = torch.where(ok, x, torch.tensor(float("-inf")))
-            v = x.max()
-            first = ((x == v) & ok).nonzero()  # lowest allowed index holding the maximum
-            lm_part[r, :, 0] = torch.tensor(float("-inf")).view(torch.int32)
-            lm_part[r, :, 1] = 0x7fffffff
-            if first.numel():
-                lm_part[r, 0, 0] = x[int(first[0])].view(torch.int32)  # that entry's own bits (-0.0 equals +0.0)
-                lm_part[r, 0, 1] = int(first[0])
+        _guide_mask_row(logits, r, vocab, torch.from_numpy(allowed), lm_part)
     return logits
 
 
@@ -630,20 +610,7 @@ def schema_guide_rows(logits, slot, desc, trans, accept, tok_off, tok_bytes, cur
         sdep[s] = d
         sstk[s, :d] = torch.from_numpy(stack[:d]).to(sstk.dtype)
         err[s] |= flags
-        allowed = torch.from_numpy(allowed)
-        logits[r, :vocab] = torch.where(allowed, logits[r, :vocab],
-                                        torch.tensor(float("-inf"), dtype=logits.dtype))
-        if lm_part is not None:
-            x = logits[r, :vocab].float()
-            ok = allowed & ~torch.isnan(x)  # a NaN never wins a comparison (sampling.hip's better())
-            x = torch.where(ok, x, torch.tensor(float("-inf")))
-            v = x.max()
-            first = ((x == v) & ok).nonzero()  # lowest allowed index holding the maximum
-            lm_part[r, :, 0] = torch.tensor(float("-inf")).view(torch.int32)
-            lm_part[r, :, 1] = 0x7fffffff
-            if first.numel():
-                lm_part[r, 0, 0] = x[int(first[0])].view(torch.int32)  # that entry's own bits (-0.0 equals +0.0)
-                lm_part[r, 0, 1] = int(first[0])
+        _guide_mask_row(logits, r, vocab, torch.from_numpy(allowed), lm_part)
     return logits
 
 
