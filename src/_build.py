@@ -81,7 +81,8 @@ def build_kernels(force: bool = False, jobs: int = 8, verbose: bool = False) -> 
     bsrc = os.path.join(CSRC, "bindings.cpp")
     bobj = os.path.join(OBJ, "bindings.o")
     objs.append(bobj)
-    if force or _newer(bobj, [bsrc] + hdrs):
+    # arg_check.h is host-only and lives outside kernels/: a change there rebuilds the bindings, no kernel
+    if force or _newer(bobj, [bsrc, os.path.join(CSRC, "arg_check.h")] + hdrs):
         cmd = ["g++", "-O2", "-std=c++17", "-fPIC",
                f"-D_GLIBCXX_USE_CXX11_ABI={abi}", "-D__HIP_PLATFORM_AMD__=1",
                "-DUSE_ROCM=1", "-DTORCH_EXTENSION_NAME=_C", "-DTORCH_API_INCLUDE_EXTENSION_H",
