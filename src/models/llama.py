@@ -338,6 +338,9 @@ class CausalLM:
                         put(lw.w2[x], t[:, r * inter:(r + 1) * inter])
         if fold:
             self.fold_norm_weights()  # checkpoint norm weights -> folded into Wqkv / Wgate_up
+        else:  # gains still in the norms: the paths that take them as folded (row scale, fused decode) stay off
+            self.norms_folded = all(bool((lw.ln1 == 1).all()) and (a.is_moe or bool((lw.ln2 == 1).all()))
+                                    for lw in self.layers)
         return n
 
     def reference_copy(self, device="cpu", dtype=torch.float32) -> "CausalLM":

@@ -15,20 +15,26 @@ from typing import Optional
 import torch
 
 
+def _wide(x: torch.Tensor) -> torch.Tensor:
+    """The working precision of the model ops: fp32, or float64 for a float64 tensor (a float64 copy of the
+    model is not cut to fp32 at every op)."""
+    return x if x.dtype == torch.float64 else x.float()
+
+
 def rms_norm(x: torch.Tensor, w: torch.Tensor, eps: float) -> torch.Tensor:
-    xf = x.float()
+    xf = _wide(x)
     var = xf.pow(2).mean(-1, keepdim=True)
-    return (xf * torch.rsqrt(var + eps) * w.float()).to(x.dtype)
+    return (xf * torch.rsqrt(var + eps) * _wide(w)).to(x.dtype)
 
 
 def fused_add_rms_norm(x: torch.Tensor, residual: torch.Tensor, w: torch.Tensor, eps: float):
-    r = (x.float() + residual.float()).to(residual.dtype)
+    r = (_wide(x) + _wide(residual)).to(residual.dtype)
     return rms_norm(r, w, eps), r
 
 
 def silu_and_mul(x: torch.Tensor) -> torch.Tensor:
     i = x.shape[-1] // 2
-    g, u = x[..., :i].float(), x[..., i:].float()
+    g, u = _wide(x[..., :i]), _wide(x[..., i:])
     return (torch.nn.functional.silu(g) * u).to(x.dtype)
 
 
@@ -57,7 +63,7 @@ def apply_rope(x: torch.Tensor, positions: torch.Tensor, cos_sin: torch.Tensor) 
     half = d // 2
     cs = cos_sin[positions.long()]
     cos, sin = cs[:, None, :half], cs[:, None, half:]
-    xf = x.float()
+    xf = _wide(x)
     a, b = xf[..., :half], xf[..., half:]
     return torch.cat([a * cos - b * sin, b * cos + a * sin], dim=-1).to(x.dtype)
 
@@ -97,9 +103,9 @@ def attention(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, hq, hkv, scale)
         qlen, ctx = b - a, int(ctx_lens[s])
         if qlen == 0:
             continue
-        qs = q[a:b, : hq * d].reshape(qlen, hq, d).float()
-        k = gather_kv(k_cache, block_tables[s], ctx).float().repeat_interleave(g, dim=1)
-        v = gather_kv(v_cache, block_tables[s], ctx).float().repeat_interleave(g, dim=1)
+        qs = _wide(q[a:b, : hq * d].reshape(qlen, hq, d))
+        k = _wide(gather_kv(k_cache, block_tables[s], ctx)).repeat_interleave(g, dim=1)
+        v = _wide(gather_kv(v_cache, block_tables[s], ctx)).repeat_interleave(g, dim=1)
         sc = torch.einsum("qhd,khd->hqk", qs, k) * scale
         qpos = torch.arange(ctx - qlen, ctx, device=q.device)[:, None]
         kpos = torch.arange(ctx, device=q.device)[None, :]
