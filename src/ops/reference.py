@@ -656,7 +656,7 @@ def pool_embed_rows(hidden, segs, acc, out, dims: int = 0, normalize: bool = Tru
 def topk_softmax(gating: torch.Tensor, k: int, renorm: bool = True):
     """Slots in descending logit order, the lowest expert index first among equal logits: the rule of the HIP
     kernels (torch.topk leaves the order of ties open), stated by a stable descending sort."""
-    g = gating.float()
+    g = _wide(gating)
     p = torch.softmax(g, dim=-1)
     ids = torch.sort(g, dim=-1, descending=True, stable=True).indices[..., :k]
     w = p.gather(-1, ids)
@@ -673,14 +673,14 @@ def moe_forward(x, w13, w2, gating, k: int, renorm: bool = True):
 
 def moe_experts(x, w13, w2, w, ids):
     """Experts' weighted sum for given routing (w [T,k], ids [T,k]); ids >= E are skipped."""
-    out = torch.zeros(x.shape, dtype=torch.float32, device=x.device)
+    out = torch.zeros(x.shape, dtype=_wide(x).dtype, device=x.device)
     inter = w2.shape[-1]
     for e in range(w13.shape[0]):
         tok, slot = (ids == e).nonzero(as_tuple=True)
         if tok.numel() == 0:
             continue
-        h = x[tok].float() @ w13[e].float().t()
+        h = _wide(x[tok]) @ _wide(w13[e]).t()
         a = torch.nn.functional.silu(h[:, :inter]) * h[:, inter:]
-        y = a.to(x.dtype).float() @ w2[e].float().t()
-        out.index_add_(0, tok, y * w[tok, slot][:, None])
+        y = _wide(a.to(x.dtype)) @ _wide(w2[e]).t()
+        out.index_add_(0, tok, y * w[tok, slot][:, None].to(out.dtype))
     return out.to(x.dtype)

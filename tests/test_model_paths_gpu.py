@@ -24,7 +24,7 @@ from src.preproc import SamplingParams  # noqa: E402
 from tests import model_reference as mr  # noqa: E402
 
 CASES = mr.cases()
-TINY = [n for n, c in CASES.items() if c.arch == "tiny"]
+TINY = [n for n, c in CASES.items() if c.arch == "tiny" and c.world == 1]   # the groups: test_model_paths_tp_moe_gpu.py
 
 
 @pytest.fixture(scope="module")
