@@ -8,7 +8,7 @@
 //   * a bias list of at most LOGIT_BIAS_MAX (id, value) pairs, ids unique (validated on the host).
 // Contract (tests/logit_process_reference.py is the oracle; tests/test_logit_process_kernel_gpu.py compares bit
 // for bit). From the bf16 logit z of token t with output count c, each step ONE individually rounded fp32
-// operation (__fadd_rn / __fmul_rn / __fsub_rn: no FMA contraction):
+// operation (add_rn / mul_rn / sub_rn below, compiled with contraction off: no FMA):
 //   1. x = float(z) + bias[t]                (0 where the list has no entry for t)
 //   2. if t is in the prompt or c > 0:       x = x > 0 ? x * inv_rp : x * rp
 //   3. x = x - freq * float(c)
@@ -27,6 +27,13 @@
 // Rows stream 16 B per lane (logits load + state load + logits store: 750 KiB per 128256-entry row).
 #include "guide_common.h"  // Best, better() and the candidate write, shared with the guide kernels
 
+// The five steps must stay five roundings. The __fadd_rn / __fmul_rn / __fsub_rn of this toolchain's headers are plain
+// operators compiled under HIP's default -ffp-contract=fast-honor-pragmas, so step 3 was fused into one v_fma_f32
+// (x - freq * c with an exact product): on tests/logit_process_reference.py's `rounding` rows (shape_1016, row 2) 29
+// bf16 values differed from the CPU path. The operators below are this file's own, under a pragma that no build flag
+// overrides.
+#pragma clang fp contract(off)
+
 namespace die {
 
 constexpr int LPT = 1024;
@@ -34,6 +41,10 @@ constexpr int LP_MAX_MAP_BYTES = 48 * 1024;  // the bitmap's share of LDS: vocab
 constexpr int LP_HASH = 1024;                // bias table slots (>= 3 x LOGIT_BIAS_MAX: short probe chains)
 constexpr uint32_t LP_EMPTY = 0xffffffffu;
 static_assert(LP_HASH >= 2 * LOGIT_BIAS_MAX && (LP_HASH & (LP_HASH - 1)) == 0, "bias table size");
+
+__device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
+__device__ __forceinline__ float sub_rn(float a, float b) { return a - b; }
+__device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
 
 __device__ __forceinline__ uint32_t lp_hash(uint32_t id) { return (id * 2654435761u) >> 22; }  // 10 bits
 
@@ -118,10 +129,10 @@ __global__ void __launch_bounds__(LPT) logit_process_kernel(bf16_t* __restrict__
           c = c < 0x7fffu ? c + 1u : c;
           srow[i + j] = (uint16_t)((st & 0x8000u) | c);
         }
-        float x = __fadd_rn(z[j], b);
-        if ((st & 0x8000u) != 0u || c > 0u) x = x > 0.f ? __fmul_rn(x, inv_rp) : __fmul_rn(x, rp);
-        x = __fsub_rn(x, __fmul_rn(freq, (float)c));
-        if (c > 0u) x = __fsub_rn(x, pres);
+        float x = add_rn(z[j], b);
+        if ((st & 0x8000u) != 0u || c > 0u) x = x > 0.f ? mul_rn(x, inv_rp) : mul_rn(x, rp);
+        x = sub_rn(x, mul_rn(freq, (float)c));
+        if (c > 0u) x = sub_rn(x, pres);
         o[j] = x;
       }
       const uint4 ov = pack8(o);

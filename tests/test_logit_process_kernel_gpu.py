@@ -2,15 +2,23 @@
 rows: BIT equality — the contract is a fixed sequence of individually rounded fp32 operations, so there is no
 tolerance to choose. Integer-valued rows make ties; the state holds prompt bits and counts 0, 1, small, 32766 and
 32767; the bias lists have 0, 1 and 300 entries and name ids 0 and vocab - 1; rows map to permuted slots and one
-row has slot -1."""
+row has slot -1.
+
+The named cases of tests/logit_process_reference.py follow (tests/test_logit_process_reference_cpu.py proves their
+premises): the `rounding` rows, found by a seeded search, on which an FMA contraction, a folded epilogue, float64
+arithmetic, a division or a misplaced bias or penalty each change >= 8 bf16 outputs; the bias-table families (probe
+chains, the wrap from slot 1023 to 0, all eight ids of a group, stray list entries, counts outside [0, cap], bias
+-inf) at vocab 8 .. 393,216; tied processed maxima across threads, waves and sweeps for the candidates."""
 
 import functools
 
+import numpy as np
 import pytest
 import torch
 
 from src import ops
 
+from tests import logit_process_reference as lpr
 from tests.logit_process_reference import COUNT_MAX, inv_f32, logit_process
 
 pytestmark = pytest.mark.gpu
@@ -167,3 +175,102 @@ def test_launcher_rejects_bad_arguments():
         ops.logit_process(logits, slot, torch.empty(0, dtype=torch.int16, device=DEV), *args)
     torch.cuda.synchronize()
     assert torch.equal(bits(logits.cpu()), bits(x))                         # nothing ran
+
+
+# ------------------------------------------------------------------------------------------------- the named cases
+GAP = 64
+NEG_INF_I32 = int(torch.tensor(float("-inf")).view(torch.int32))
+
+
+def bf16_of(bits):
+    return torch.from_numpy(np.ascontiguousarray(bits).view(np.int16)).view(torch.bfloat16)
+
+
+def u16(t):
+    return t.cpu().contiguous().view(torch.int16).numpy().view(np.uint16)
+
+
+def raw_candidates(c, parts):
+    """The candidates as the LM head leaves them: each row's raw (max, lowest index) in the last part."""
+    rows = c.x.shape[0]
+    lm = torch.empty(rows, parts, 2, dtype=torch.int32)
+    lm[:, :, 0], lm[:, :, 1] = NEG_INF_I32, lpr.NO_INDEX
+    for r in range(rows):
+        v = lpr.bits_f32(c.x[r])
+        lm[r, parts - 1, 0] = int(np.float32(v.max()).view(np.int32))
+        lm[r, parts - 1, 1] = int(np.flatnonzero(v == v.max())[0])
+    return lm
+
+
+def launch_named(c, counted, parts=0):
+    """One launch from fresh copies: rows in a strided buffer with a loud gap. -> (buffer, state, candidates, view)."""
+    v = c.vocab
+    buf = strided(bf16_of(c.x), v + GAP)
+    state = torch.from_numpy(c.state.view(np.int16).copy()).to(DEV)
+    lm = raw_candidates(c, parts).to(DEV) if parts else None
+    view = buf[:, :v]
+    assert view.stride(0) == v + GAP
+    ops.logit_process(view, torch.from_numpy(c.slot).to(DEV), state, torch.from_numpy(c.params).to(DEV),
+                      torch.from_numpy(c.bias_cnt).to(DEV), torch.from_numpy(c.bias_ids).to(DEV),
+                      torch.from_numpy(c.bias_vals).to(DEV),
+                      count_ids=torch.from_numpy(c.count_ids).to(DEV) if counted else None, lm_part=lm)
+    torch.cuda.synchronize()
+    return buf, state, lm, view
+
+
+def check_rows_and_state(c, buf, state, w_rows, w_state):
+    got = u16(buf)
+    v = c.vocab
+    assert np.array_equal(got[:, v:], u16(torch.full((c.x.shape[0], GAP), 1000.0, dtype=torch.bfloat16)))
+    for r in range(c.x.shape[0]):
+        bad = np.flatnonzero(got[r, :v] != w_rows[r])
+        assert bad.size == 0, (r, bad[:5].tolist(), got[r, bad[:5]].tolist(), w_rows[r, bad[:5]].tolist())
+    assert torch.equal(state.cpu(), torch.from_numpy(w_state.view(np.int16)))
+
+
+@pytest.mark.parametrize("counted", [True, False], ids=["count_ids", "no_count_ids"])
+@pytest.mark.parametrize("name", lpr.ROWS_CASE_NAMES)
+def test_named_case_rows_and_state_bit_for_bit(name, counted):
+    c = lpr.rows_case(name)
+    w_rows, w_state, _ = lpr.rows_expected(name, counted)
+    buf, state, _, _ = launch_named(c, counted)
+    check_rows_and_state(c, buf, state, w_rows, w_state)
+    buf2, state2, _, _ = launch_named(c, counted)                 # again from fresh copies: bit-identical
+    assert np.array_equal(u16(buf), u16(buf2)) and torch.equal(state.cpu(), state2.cpu())
+
+
+@pytest.mark.parametrize("parts", [1, 5])
+@pytest.mark.parametrize("name", lpr.ROWS_CASE_NAMES)
+def test_named_case_candidates_and_the_sampler(name, parts):
+    c = lpr.rows_case(name)
+    w_rows, w_state, w_cand = lpr.rows_expected(name, True)
+    buf, state, lm, view = launch_named(c, True, parts)
+    check_rows_and_state(c, buf, state, w_rows, w_state)
+    got = lm.cpu()
+    raw = raw_candidates(c, parts)
+    want_ids = []
+    for r in range(c.x.shape[0]):
+        if r in w_cand:       # candidate 0 holds the exact bits, the others (-inf, 0x7fffffff)
+            assert int(got[r, 0, 0]) & 0xffffffff == w_cand[r][0] and int(got[r, 0, 1]) == w_cand[r][1]
+            assert bool((got[r, 1:, 0] == NEG_INF_I32).all()) and bool((got[r, 1:, 1] == lpr.NO_INDEX).all())
+            want_ids.append(w_cand[r][1])
+        else:                 # an unprocessed row: the LM head's candidates were left alone
+            assert torch.equal(got[r], raw[r])
+            want_ids.append(int(raw[r, parts - 1, 1]))
+    assert ops.sample(view, lm_part=lm).cpu().tolist() == want_ids
+    assert ops.sample(view).cpu().tolist() == want_ids            # the sampler's own pass over the rewritten rows
+    lm2 = launch_named(c, True, parts)[2]
+    assert torch.equal(got, lm2.cpu())
+
+
+def test_launcher_rejects_a_vocabulary_past_the_bitmap_s_share_of_lds():
+    vocab = 393224
+    logits = torch.full((1, vocab), 1.5, dtype=torch.bfloat16, device=DEV)
+    state = torch.full((2, vocab), 3, dtype=torch.int16, device=DEV)
+    z = torch.zeros(2, dtype=torch.int32, device=DEV)
+    with pytest.raises(RuntimeError, match="HIP launch failed"):
+        ops.logit_process(logits, torch.ones(1, dtype=torch.int32, device=DEV), state,
+                          torch.ones(2, 4, device=DEV), z, torch.zeros(2, 300, dtype=torch.int32, device=DEV),
+                          torch.ones(2, 300, device=DEV), count_ids=torch.zeros(1, dtype=torch.long, device=DEV))
+    torch.cuda.synchronize()
+    assert bool((logits == 1.5).all()) and bool((state == 3).all())           # nothing was written
