@@ -47,6 +47,9 @@ class ModelConfig:
     max_num_batched_tokens: int = 16384
     gpu_memory_fraction: float = 0.90
     num_kv_blocks: Optional[int] = None  # override the HBM-derived block count
+    # "auto": the KV pool holds bf16; "fp8": OCP e4m3 bytes (twice the blocks in the same memory; one GPU, dense
+    # models, role "both": see LLMEngine)
+    kv_cache_dtype: str = "auto"
     enable_prefix_caching: bool = True
     use_cuda_graph: bool = True        # hipGraph capture of decode steps
     max_latency_ms: float = 10.0
@@ -79,6 +82,7 @@ class EngineConfig:
     max_latency_ms: float = 10.0       # admission wait bound (the reference Batcher knob)
     block_size: int = 16
     num_kv_blocks: Optional[int] = None
+    kv_cache_dtype: str = "auto"       # "auto" (bf16) | "fp8" (e4m3 pool, per-layer k / v scales)
     gpu_memory_fraction: float = 0.90
     enable_prefix_caching: bool = True
     kv_block_ttl_s: Optional[float] = None  # TTL for cached (unreferenced) KV blocks

@@ -40,6 +40,7 @@ def engine_config_from(config: ModelConfig) -> EngineConfig:
         max_latency_ms=config.max_latency_ms,
         block_size=config.kv_block_size,
         num_kv_blocks=config.num_kv_blocks,
+        kv_cache_dtype=config.kv_cache_dtype,
         gpu_memory_fraction=config.gpu_memory_fraction,
         enable_prefix_caching=config.enable_prefix_caching,
         kv_block_ttl_s=ov.get("kv_block_ttl_s"),
@@ -59,6 +60,11 @@ class LLMBackend:
         if str(device).startswith("cuda") and torch.device(device).index is not None:
             # model build, weight packing and graph capture run on this thread: on the serving GPU
             torch.cuda.set_device(torch.device(device))
+        if config.kv_cache_dtype == "fp8" and config.role != "both":
+            # the landing zone and its packets ship bf16 blocks
+            raise ValueError(f"kv_cache_dtype='fp8' is not available on a disaggregated {config.role} worker")
+        if config.kv_cache_dtype == "fp8" and config.tp_size > 1:
+            raise ValueError("kv_cache_dtype='fp8' is not available on a tensor-parallel engine")
         if engine is None:
             from src.models.loader import is_hf_checkpoint
 

@@ -38,12 +38,34 @@ from src.preproc import SamplingParams
 logger = logging.getLogger(__name__)
 
 
+def kv_dtype_bytes(cfg: EngineConfig) -> int:
+    """Bytes per element of the KV pool: 2 (bf16) or 1 (kv_cache_dtype="fp8", e4m3)."""
+    mode = getattr(cfg, "kv_cache_dtype", "auto")
+    if mode not in ("auto", "fp8"):
+        raise ValueError(f"kv_cache_dtype must be auto / fp8, not {mode!r}")
+    return 1 if mode == "fp8" else 2
+
+
+def check_kv_cache_dtype(cfg: EngineConfig, model: CausalLM) -> None:
+    """What the FP8 KV cache does not serve is refused when the engine is built."""
+    if kv_dtype_bytes(cfg) == 2:
+        return
+    if model.tp.enabled:
+        raise ValueError("kv_cache_dtype='fp8' is not available on a tensor-parallel engine")
+    if model.arch.is_moe:
+        raise ValueError("kv_cache_dtype='fp8' is not available on a MoE model: its decode needs the fused "
+                         "attention prologue, which has no FP8 form")
+    if model.head_dim != 128 or cfg.block_size != 16 or model.hq // model.hkv not in (1, 2, 4, 8):
+        raise ValueError("kv_cache_dtype='fp8' needs head_dim 128, block_size 16 and hq / hkv in {1, 2, 4, 8}")
+
+
 def plan_kv_blocks(arch: ArchConfig, model: CausalLM, cfg: EngineConfig, device: torch.device) -> int:
     if cfg.num_kv_blocks:
         return cfg.num_kv_blocks
-    per_block = KVPool.bytes_per_block(arch.num_layers, model.hkv, cfg.block_size, arch.head_dim)
+    per_block = KVPool.bytes_per_block(arch.num_layers, model.hkv, cfg.block_size, arch.head_dim,
+                                       kv_dtype_bytes(cfg))
     if device.type != "cuda":
-        return 512
+        return 512 * 2 // kv_dtype_bytes(cfg)
     free, total = torch.cuda.mem_get_info(device)
     h = arch.hidden_size
     inter = model.inter * (arch.top_k if arch.is_moe else 1)
@@ -132,14 +154,17 @@ class LLMEngine:
                         if self.decode_weight_layout == "tiled" else "one copy, HBM left to the KV pool")
         if hasattr(model, "pack_lm_head"):
             model.pack_lm_head()
+        check_kv_cache_dtype(cfg, model)
+        self.kv_fp8 = kv_dtype_bytes(cfg) == 1
         nblocks = plan_kv_blocks(self.arch, model, cfg, self.device)
         self.pool = KVPool(self.arch.num_layers, nblocks, model.hkv, cfg.block_size, self.arch.head_dim,
-                           self.device, dtype=model.dtype)
+                           self.device, dtype=torch.uint8 if self.kv_fp8 else model.dtype)
         self.blocks = KVBlockManager(nblocks, cfg.block_size, cfg.enable_prefix_caching, cfg.kv_block_ttl_s)
         self.runner = runner_cls(model, self.pool, cfg, self.max_model_len)
         # host swap space for preempted sequences (single-process runners only: a TP group would
         # have to mirror every swap on its followers, so it always recomputes)
-        per_block = KVPool.bytes_per_block(self.arch.num_layers, model.hkv, cfg.block_size, self.arch.head_dim)
+        per_block = KVPool.bytes_per_block(self.arch.num_layers, model.hkv, cfg.block_size, self.arch.head_dim,
+                                           kv_dtype_bytes(cfg))
         swap_blocks = 0
         if cfg.preemption_mode != "recompute" and getattr(self.runner, "supports_swap", False):
             swap_blocks = int(cfg.swap_space_gib * 2**30 // per_block)
@@ -209,6 +234,8 @@ class LLMEngine:
             # an out-of-range id would be an out-of-bounds embedding read on the GPU
             raise ValueError(f"prompt token id outside [0, {self.arch.vocab_size})")
         self._check_logit_processing(sampling)
+        if export_kv and self.kv_fp8:  # packets and landing zones hold bf16 blocks
+            raise ValueError("KV export is not supported with kv_cache_dtype='fp8'")
         guide = self._compile_guide(sampling)
         if sampling.prompt_logprobs is not None:
             # every prompt row's logits are computed (keep_rows=None), which TP followers do not mirror and a
@@ -317,6 +344,8 @@ class LLMEngine:
     def _add_imported(self, packet, sampling: SamplingParams, on_finish) -> Sequence:
         from src.parallel.kv_transfer import import_blocks
 
+        if self.kv_fp8:  # packets hold bf16 blocks
+            raise ValueError("KV import is not supported with kv_cache_dtype='fp8'")
         if packet.block_size != self.cfg.block_size:
             raise ValueError("block size mismatch between prefill and decode workers")
         self._check_logit_processing(sampling)

@@ -23,7 +23,7 @@ from __future__ import annotations
 import math
 import os
 from dataclasses import dataclass
-from typing import Callable, Dict, List, Optional
+from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -206,6 +206,9 @@ class CausalLM:
                 lw.down = self._param((h, self.inter), (h, big), lambda t: self.shard_cols(t, self.inter), ostd,
                                       gen, genf)
             self.layers.append(lw)
+        # FP8 KV cache: per-layer (k_scale, v_scale), a stored byte is e4m3(x / scale). 1.0 unless the checkpoint has
+        # `self_attn.k_scale` / `v_scale`; a bf16 pool ignores them
+        self.kv_scales: List[Tuple[float, float]] = [(1.0, 1.0)] * a.num_layers
         self.norm = torch.ones(h, dtype=self.dtype, device=self.device)
         self.lm_head = self._param((self.vocab_local, h), (a.vocab_size, h),
                                    lambda t: self.shard_rows(t, self.vocab_local), std, gen, genf)
@@ -306,6 +309,13 @@ class CausalLM:
                     put(lw.qkv[(hq + hkv) * d:], rows(t, kv_idx * d, hkv * d))
                 elif rest == "self_attn.o_proj.weight":
                     put(lw.o, t[:, r * hq * d:(r + 1) * hq * d])
+                elif rest in ("self_attn.k_scale", "self_attn.v_scale"):
+                    s = float(t.float().reshape(-1)[0])
+                    if not (s > 0 and s < float("inf")):
+                        raise ValueError(f"{name}: a KV scale must be finite and > 0, got {s}")
+                    ks, vs = self.kv_scales[li]
+                    self.kv_scales[li] = (s, vs) if rest.endswith("k_scale") else (ks, s)
+                    n -= 1
                 elif rest == "input_layernorm.weight":
                     put(lw.ln1, t)
                 elif rest == "post_attention_layernorm.weight":
@@ -477,7 +487,7 @@ class CausalLM:
         k_cache, v_cache = kv_pool[li, 0], kv_pool[li, 1]
         fuse_q = qkv.is_cuda
         ops.rope_and_cache(qkv, positions, self.cos_sin, meta.slot_mapping, k_cache, v_cache, hq, hkv, d,
-                           rot_q=not fuse_q, row_scale=rs)
+                           rot_q=not fuse_q, row_scale=rs, kv_scales=self.kv_scales[li])
         if meta.kv_hook is not None:
             meta.kv_hook(li)
         if n == 0:
@@ -489,7 +499,8 @@ class CausalLM:
         attn = ops.attn_prefill(q, k_cache, v_cache, meta.block_tables.index_select(0, seq),
                                 cu1, meta.ctx_lens.index_select(0, seq), 1, hq, hkv, self.scale,
                                 cos_sin=self.cos_sin if fuse_q else None,
-                                q_scale=rs.index_select(0, keep) if rs is not None else None)
+                                q_scale=rs.index_select(0, keep) if rs is not None else None,
+                                kv_scales=self.kv_scales[li])
         res = residual.index_select(0, keep)
         o = self.tp.all_reduce(ops.linear(attn, lw.o))
         x2 = ops.fused_add_rms_norm(o, res, lw.ln2, eps)
@@ -507,15 +518,15 @@ class CausalLM:
         # prefill on the GPU: q's RoPE happens in the attention kernel's Q load (no q round trip through HBM)
         fuse_q = meta.is_prefill and qkv.is_cuda
         ops.rope_and_cache(qkv, positions, self.cos_sin, meta.slot_mapping, k_cache, v_cache, hq, hkv, d,
-                           rot_q=not fuse_q, row_scale=rs)
+                           rot_q=not fuse_q, row_scale=rs, kv_scales=self.kv_scales[li])
         q = qkv[:, : hq * d]
         if meta.is_prefill:
             return ops.attn_prefill(q, k_cache, v_cache, meta.block_tables, meta.cu_q, meta.ctx_lens,
                                     meta.max_q_len, hq, hkv, self.scale, cos_sin=self.cos_sin if fuse_q else None,
-                                    q_scale=rs)
+                                    q_scale=rs, kv_scales=self.kv_scales[li])
         return ops.attn_decode(q, k_cache, v_cache, meta.block_tables, meta.ctx_lens, meta.max_ctx, hq, hkv,
                                self.scale, part_o=meta.part_o, part_ml=meta.part_ml, counters=meta.attn_cnt,
-                               kv_once=meta.kv_once)
+                               kv_once=meta.kv_once, kv_scales=self.kv_scales[li])
 
     def _mlp(self, lw: LayerWeights, x: torch.Tensor) -> torch.Tensor:
         """This rank's partial FFN / MoE output (summed over the TP group by the caller)."""
@@ -571,14 +582,14 @@ class CausalLM:
                 x = ops.fused_add_rms_norm_slab(slab, residual, lw.ln1, eps)
             k_cache, v_cache = kv_pool[li, 0], kv_pool[li, 1]
             q = ops.rope_and_cache_slab(ops.linear_slab(x, lw.qkv), positions, self.cos_sin, meta.slot_mapping,
-                                        k_cache, v_cache, hq, hkv, d)
+                                        k_cache, v_cache, hq, hkv, d, kv_scales=self.kv_scales[li])
             if meta.is_prefill:
                 attn = ops.attn_prefill(q, k_cache, v_cache, meta.block_tables, meta.cu_q, meta.ctx_lens,
-                                        meta.max_q_len, hq, hkv, self.scale)
+                                        meta.max_q_len, hq, hkv, self.scale, kv_scales=self.kv_scales[li])
             else:
                 attn = ops.attn_decode(q, k_cache, v_cache, meta.block_tables, meta.ctx_lens, meta.max_ctx, hq,
                                        hkv, self.scale, part_o=meta.part_o, part_ml=meta.part_ml,
-                                       counters=meta.attn_cnt, kv_once=meta.kv_once)
+                                       counters=meta.attn_cnt, kv_once=meta.kv_once, kv_scales=self.kv_scales[li])
             x = ops.fused_add_rms_norm_slab(ops.linear_slab(attn, lw.o), residual, lw.ln2, eps)
             slab = ops.linear_slab(ops.linear_silu_mul(x, lw.gate_up), lw.down)
         return ops.fused_add_rms_norm_slab(slab, residual, self.norm, eps)
@@ -830,7 +841,9 @@ class CausalLM:
     def _fused_decode_ok(self, kv_pool: torch.Tensor, m: int = 32) -> bool:
         g = self.hq // self.hkv
         sq = self.decode_plan(m)["qkv"][2]
+        # a one-byte (FP8) pool has no fused prologue: its decode steps take _forward_decode_slab
         return (self.norms_folded and self.head_dim == 128 and kv_pool.shape[4] == 16 and g in (1, 2, 4, 8)
+                and kv_pool.element_size() == 2
                 and ((sq * (g + 2) + 1) // 2) * 1024 + 2048 <= V3_MERGE_BYTES)
 
     def _forward_decode_fused(self, h: torch.Tensor, positions: torch.Tensor, meta: AttnMetadata,

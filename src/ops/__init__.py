@@ -8,7 +8,7 @@ which lets the engine's control flow run in CPU-only tests.
 
 from __future__ import annotations
 
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
@@ -29,8 +29,25 @@ except Exception as e:  # pragma: no cover - depends on build state
     _C_ERR = e
 
 
+# the FP8 KV-cache kernels live in a module of their own (csrc/bindings_kv8.cpp)
+_C_kv8 = None
+_C_KV8_ERR: Optional[BaseException] = None
+try:
+    from src import _C_kv8  # type: ignore  # noqa: F811
+except Exception as e:  # pragma: no cover - depends on build state
+    _C_KV8_ERR = e
+
+
 def native_available() -> bool:
     return _C is not None
+
+
+def _kern_kv8():
+    if _C_kv8 is None:
+        raise RuntimeError(
+            "HIP kernel extension src/_C_kv8 (FP8 KV cache) is not built or failed to load "
+            f"({_C_KV8_ERR!r}); run `python -m src._build` (hipcc --offload-arch=gfx950)")
+    return _C_kv8
 
 
 def _kern():
@@ -125,10 +142,15 @@ def rms_row_scale(resid: torch.Tensor, x: Optional[torch.Tensor], eps: float,
 
 
 def rope_and_cache(qkv, positions, cos_sin, slot_mapping, k_cache, v_cache, hq: int, hkv: int, head_dim: int,
-                   rot_q: bool = True, row_scale: Optional[torch.Tensor] = None) -> None:
+                   rot_q: bool = True, row_scale: Optional[torch.Tensor] = None,
+                   kv_scales: Tuple[float, float] = (1.0, 1.0)) -> None:
     """Rotate k (and q unless rot_q=False: prefill attention then rotates its Q rows on load, see
     attn_prefill's cos_sin) and write k / v into the paged cache. row_scale (fp32 [T], with rot_q=False):
-    k and v rows are scaled by the token's RMSNorm scale (:func:`rms_row_scale`); q is left to the attention."""
+    k and v rows are scaled by the token's RMSNorm scale (:func:`rms_row_scale`); q is left to the attention.
+    A one-byte cache is the FP8 pool (:func:`rope_and_cache_kv8`, kv_scales = (k_scale, v_scale))."""
+    if ref.is_kv8(k_cache):
+        return rope_and_cache_kv8(qkv, positions, cos_sin, slot_mapping, k_cache, v_cache, hq, hkv, head_dim,
+                                  kv_scales[0], kv_scales[1], rot_q=rot_q, row_scale=row_scale)
     if not qkv.is_cuda:
         assert rot_q and row_scale is None, "the CPU reference path rotates q here"
         ref.rope_and_cache(qkv, positions, cos_sin, slot_mapping, k_cache, v_cache, hq, hkv, head_dim)
@@ -140,10 +162,14 @@ def rope_and_cache(qkv, positions, cos_sin, slot_mapping, k_cache, v_cache, hq: 
 
 def attn_prefill(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, max_q_len: int, hq: int, hkv: int,
                  scale: float, out: Optional[torch.Tensor] = None, cos_sin: Optional[torch.Tensor] = None,
-                 q_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 q_scale: Optional[torch.Tensor] = None, kv_scales: Tuple[float, float] = (1.0, 1.0)) -> torch.Tensor:
     """Causal paged prefill attention. cos_sin ([max_pos, 128] fp32): q is NOT yet rotated, the kernel
     applies RoPE to each Q row as it loads it (token positions ctx - q_len + i). q_scale (fp32 [T], with
-    cos_sin): each Q row is also scaled by its token's RMSNorm scale (:func:`rms_row_scale`)."""
+    cos_sin): each Q row is also scaled by its token's RMSNorm scale (:func:`rms_row_scale`). A one-byte cache is
+    the FP8 pool (:func:`attn_prefill_kv8`)."""
+    if ref.is_kv8(k_cache):
+        return attn_prefill_kv8(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, max_q_len, hq, hkv, scale,
+                                kv_scales[0], kv_scales[1], out=out, cos_sin=cos_sin, q_scale=q_scale)
     if not q.is_cuda:
         assert cos_sin is None and q_scale is None, "the CPU reference path takes a rotated q"
         return ref.attention(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, hq, hkv, scale).reshape(q.shape[0], -1)
@@ -163,12 +189,19 @@ def decode_partials(max_ctx: int) -> int:
 def attn_decode(q, k_cache, v_cache, block_tables, ctx_lens, max_ctx: int, hq: int, hkv: int, scale: float,
                 part_o: Optional[torch.Tensor] = None, part_ml: Optional[torch.Tensor] = None,
                 out: Optional[torch.Tensor] = None, counters: Optional[torch.Tensor] = None,
-                merge_kernel: bool = False, kv_once: bool = True) -> torch.Tensor:
-    """Paged decode attention. `counters` (int32, >= num_seqs * hkv, zeroed once) are the
+                merge_kernel: bool = False, kv_once: bool = True,
+                kv_scales: Tuple[float, float] = (1.0, 1.0)) -> torch.Tensor:
+    """Paged decode attention (a one-byte cache: the FP8 pool, :func:`attn_decode_kv8`). `counters` (int32, >= num_seqs * hkv, zeroed once) are the
     per-(sequence, kv head) tickets of the self-merging kernel; they are re-armed by the kernel,
     so a runner allocates them once. merge_kernel=True forces the two-launch path. kv_once: the
     self-merging kernel streams K/V with the once-read (nt) cache policy (False: the default policy,
     for A/B; the result is the same bit for bit either way)."""
+    if ref.is_kv8(k_cache):
+        if merge_kernel:
+            raise ValueError("attn_decode: the FP8 cache has no two-launch path")
+        return attn_decode_kv8(q, k_cache, v_cache, block_tables, ctx_lens, max_ctx, hq, hkv, scale, kv_scales[0],
+                               kv_scales[1], part_o=part_o, part_ml=part_ml, out=out, counters=counters,
+                               kv_once=kv_once)
     if not q.is_cuda:
         n = ctx_lens.numel()
         cu = torch.arange(n + 1, dtype=torch.int32)
@@ -205,6 +238,89 @@ def attn_decode_fused(qkv_slab: torch.Tensor, ssp: torch.Tensor, positions: torc
     _kern().attn_decode_fused(out, part_o, part_ml, counters, qkv_slab, ssp, positions, cos_sin, slot_mapping,
                               k_cache, v_cache, block_tables, ctx_lens, max_ctx, hq, hkv, scale, eps, hidden,
                               kv_once)
+    return out
+
+
+# ---- FP8 (e4m3) KV cache (csrc/kernels/attention_kv8.hip). k_scale / v_scale: the layer's per-tensor scales; a stored
+# byte is e4m3(x / scale). A GPU call the kernels cannot serve raises (the binding's checks); CPU tensors take
+# src.ops.reference with the same cache semantics.
+def _kv8_dim(head_dim: int) -> None:
+    if head_dim != 128:
+        raise ValueError(f"the FP8 KV cache kernels need head_dim 128, got {head_dim}")
+
+
+def rope_and_cache_kv8(qkv, positions, cos_sin, slot_mapping, k_cache, v_cache, hq: int, hkv: int, head_dim: int,
+                       k_scale: float = 1.0, v_scale: float = 1.0, rot_q: bool = True,
+                       row_scale: Optional[torch.Tensor] = None) -> None:
+    """:func:`rope_and_cache` with an e4m3 cache: k / v are converted from the fp32 values the kernel holds after
+    the rotation and the row scale."""
+    if not qkv.is_cuda:
+        assert rot_q and row_scale is None, "the CPU reference path rotates q here"
+        ref.rope_and_cache_kv8(qkv, positions, cos_sin, slot_mapping, k_cache, v_cache, hq, hkv, head_dim, k_scale,
+                               v_scale)
+        return
+    _kv8_dim(head_dim)
+    assert row_scale is None or not rot_q, "a row scale is applied with the attention's Q rotation"
+    _kern_kv8().rope_and_cache_kv8(qkv, positions, cos_sin, slot_mapping, k_cache, v_cache, hq, hkv, float(k_scale),
+                                   float(v_scale), rot_q, row_scale if row_scale is not None else _empty(qkv.device))
+
+
+def rope_and_cache_slab_kv8(slab, positions, cos_sin, slot_mapping, k_cache, v_cache, hq: int, hkv: int, head_dim: int,
+                            k_scale: float = 1.0, v_scale: float = 1.0,
+                            q_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`rope_and_cache_slab` with an e4m3 cache; returns q [T, hq*D] (bf16)."""
+    _kv8_dim(head_dim)
+    if q_out is None:
+        q_out = torch.empty(slab.shape[1], hq * head_dim, dtype=torch.bfloat16, device=slab.device)
+    _kern_kv8().rope_and_cache_slab_kv8(q_out, slab, positions, cos_sin, slot_mapping, k_cache, v_cache, hq, hkv,
+                                        float(k_scale), float(v_scale))
+    return q_out
+
+
+def attn_decode_kv8_part_keys(num_seqs: int, hkv: int, max_ctx: int) -> int:
+    """Keys per part of :func:`attn_decode_kv8` at this launch shape (longer contexts are merged by ticket)."""
+    return int(_kern_kv8().decode_part_keys(num_seqs, hkv, max_ctx))
+
+
+def attn_decode_kv8(q, k_cache, v_cache, block_tables, ctx_lens, max_ctx: int, hq: int, hkv: int, scale: float,
+                    k_scale: float = 1.0, v_scale: float = 1.0, part_o: Optional[torch.Tensor] = None,
+                    part_ml: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                    counters: Optional[torch.Tensor] = None, kv_once: bool = True) -> torch.Tensor:
+    """Paged decode attention over an e4m3 cache (block_size 16, hq / hkv in {1, 2, 4, 8}); the buffers are
+    :func:`attn_decode`'s."""
+    n = ctx_lens.numel()
+    if not q.is_cuda:
+        cu = torch.arange(n + 1, dtype=torch.int32)
+        return ref.attention_kv8(q[:n], k_cache, v_cache, block_tables, cu, ctx_lens, hq, hkv, scale, k_scale,
+                                 v_scale).reshape(n, -1)
+    if out is None:
+        out = torch.empty(n, hq * 128, dtype=q.dtype, device=q.device)
+    if part_o is None or part_ml is None:
+        maxp = (max_ctx + 127) // 128
+        part_o = torch.empty(n * hq * maxp * 128, dtype=torch.float32, device=q.device)
+        part_ml = torch.empty(n * hq * maxp * 2, dtype=torch.float32, device=q.device)
+    if counters is None:
+        counters = torch.zeros(n * hkv, dtype=torch.int32, device=q.device)
+    _kern_kv8().attn_decode_kv8(out, part_o, part_ml, counters, q, k_cache, v_cache, block_tables, ctx_lens, max_ctx,
+                                hq, hkv, scale, float(k_scale), float(v_scale), kv_once)
+    return out
+
+
+def attn_prefill_kv8(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, max_q_len: int, hq: int, hkv: int,
+                     scale: float, k_scale: float = 1.0, v_scale: float = 1.0, out: Optional[torch.Tensor] = None,
+                     cos_sin: Optional[torch.Tensor] = None, q_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`attn_prefill` over an e4m3 cache."""
+    if not q.is_cuda:
+        assert cos_sin is None and q_scale is None, "the CPU reference path takes a rotated q"
+        return ref.attention_kv8(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, hq, hkv, scale, k_scale,
+                                 v_scale).reshape(q.shape[0], -1)
+    if out is None:
+        out = torch.empty(q.shape[0], hq * 128, dtype=q.dtype, device=q.device)
+    assert q_scale is None or cos_sin is not None, "the Q row scale is applied with the rotation"
+    e = _empty(q.device)
+    _kern_kv8().attn_prefill_kv8(out, q, k_cache, v_cache, block_tables, cu_q, ctx_lens, max_q_len, hq, hkv, scale,
+                                 float(k_scale), float(v_scale), cos_sin if cos_sin is not None else e,
+                                 q_scale if q_scale is not None else e)
     return out
 
 
@@ -454,13 +570,19 @@ def sample_advance(logits, temperature, top_k, top_p, seeds, steps, out, lm_part
     return out
 
 
+def _as_bf16(t: torch.Tensor) -> torch.Tensor:
+    """The FP8 pool (and its staging buffers) as the block movers see it: the same bytes, half as many bf16 elements
+    per row. The movers only copy whole (block, plane) slabs, so the element type does not matter to them."""
+    return t.view(torch.bfloat16) if t.element_size() == 1 else t
+
+
 def copy_blocks(pool: torch.Tensor, pairs: torch.Tensor) -> None:
     """pool viewed [planes, num_blocks, ...]; pairs [n, 2] int64 (src, dst)."""
     if not pool.is_cuda:
         for s, d in pairs.tolist():
             pool[:, d] = pool[:, s]
         return
-    _kern().copy_blocks(pool, pairs)
+    _kern().copy_blocks(_as_bf16(pool), pairs)
 
 
 def gather_blocks(pool: torch.Tensor, ids: torch.Tensor, buf: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -472,14 +594,14 @@ def gather_blocks(pool: torch.Tensor, ids: torch.Tensor, buf: Optional[torch.Ten
     if not pool.is_cuda:
         buf.copy_(pool.reshape(planes, nb, slab)[:, ids.long()].transpose(0, 1))
         return buf
-    _kern().move_blocks(pool, buf, ids, True)
+    _kern().move_blocks(_as_bf16(pool), _as_bf16(buf), ids, True)
     return buf
 
 
 def gather_blocks_rows(pool: torch.Tensor, ids: torch.Tensor, dst: torch.Tensor, plane0: int, nplanes: int) -> None:
     """Planes [plane0, plane0 + nplanes) of pool blocks ``ids`` into the packet rows at device addresses ``dst``
     (int64, one per block; each row [planes, slab]) — the overlapped disaggregated export (LayerGroupExporter)."""
-    _kern().gather_blocks_rows(pool, ids, dst, plane0, nplanes)
+    _kern().gather_blocks_rows(_as_bf16(pool), ids, dst, plane0, nplanes)
 
 
 def scatter_blocks(pool: torch.Tensor, ids: torch.Tensor, buf: torch.Tensor) -> None:
@@ -488,7 +610,7 @@ def scatter_blocks(pool: torch.Tensor, ids: torch.Tensor, buf: torch.Tensor) -> 
     if not pool.is_cuda:
         pool.view(planes, nb, slab)[:, ids.long()] = buf.view(ids.numel(), planes, slab).transpose(0, 1)
         return
-    _kern().move_blocks(pool, buf, ids, False)
+    _kern().move_blocks(_as_bf16(pool), _as_bf16(buf), ids, False)
 
 
 # expert-streaming grouped decode GEMM up to this many tokens (<= 128 rows per expert: 16/32/64/128-row
@@ -763,12 +885,16 @@ def fused_add_rms_norm_slab(slab: torch.Tensor, residual: torch.Tensor, w: torch
 
 
 def rope_and_cache_slab(slab, positions, cos_sin, slot_mapping, k_cache, v_cache, hq: int, hkv: int,
-                        head_dim: int, q_out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """Sum the QKV split-K slabs, rotate q/k, write k/v into the paged cache;
-    returns q [T, hq*D] (bf16)."""
+                        head_dim: int, q_out: Optional[torch.Tensor] = None,
+                        kv_scales: Tuple[float, float] = (1.0, 1.0)) -> torch.Tensor:
+    """Sum the QKV split-K slabs, rotate q/k, write k/v into the paged cache (a one-byte cache: the FP8 pool,
+    :func:`rope_and_cache_slab_kv8`); returns q [T, hq*D] (bf16)."""
     t = slab.shape[1]
     if q_out is None:
         q_out = torch.empty(t, hq * head_dim, dtype=torch.bfloat16, device=slab.device)
+    if ref.is_kv8(k_cache):
+        return rope_and_cache_slab_kv8(slab, positions, cos_sin, slot_mapping, k_cache, v_cache, hq, hkv, head_dim,
+                                       kv_scales[0], kv_scales[1], q_out=q_out)
     _kern().rope_and_cache_slab(q_out, slab, positions, cos_sin, slot_mapping, k_cache, v_cache, hq, hkv, head_dim)
     return q_out
 

@@ -115,6 +115,51 @@ def attention(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, hq, hkv, scale)
     return out
 
 
+# ---- FP8 (OCP e4m3) KV cache: a stored byte is e4m3(x / scale), nearest-even, saturated to +-448
+E4M3_MAX = 448.0
+
+
+def is_kv8(cache: torch.Tensor) -> bool:
+    return cache.element_size() == 1
+
+
+def quantize_kv8(x: torch.Tensor, scale: float) -> torch.Tensor:
+    """fp32 values -> e4m3 bytes (the CPU conversion is nearest-even and turns overflow into NaN: hence the clamp)."""
+    return (x.float() / scale).clamp(-E4M3_MAX, E4M3_MAX).to(torch.float8_e4m3fn)
+
+
+def dequantize_kv8(cache: torch.Tensor, scale: float) -> torch.Tensor:
+    """e4m3 bytes (uint8 or float8_e4m3fn storage) -> fp32 values."""
+    return cache.view(torch.float8_e4m3fn).float() * scale
+
+
+def rope_and_cache_kv8(qkv, positions, cos_sin, slot_mapping, k_cache, v_cache, hq, hkv, head_dim, k_scale=1.0,
+                       v_scale=1.0):
+    """rope_and_cache with an e4m3 cache: q is rotated in place (bf16); k / v are quantised from the fp32 values,
+    not through bf16."""
+    t = qkv.shape[0]
+    q = qkv[:, : hq * head_dim].view(t, hq, head_dim)
+    k = qkv[:, hq * head_dim:(hq + hkv) * head_dim].view(t, hkv, head_dim)
+    v = qkv[:, (hq + hkv) * head_dim:(hq + 2 * hkv) * head_dim].view(t, hkv, head_dim)
+    qkv[:, : hq * head_dim] = apply_rope(q, positions, cos_sin).reshape(t, -1)
+    kq = quantize_kv8(apply_rope(k.float(), positions, cos_sin), k_scale)
+    vq = quantize_kv8(v, v_scale)
+    bs = k_cache.shape[2]
+    kc, vc = k_cache.view(torch.float8_e4m3fn), v_cache.view(torch.float8_e4m3fn)
+    for i in range(t):
+        s = int(slot_mapping[i])
+        if s < 0:
+            continue
+        kc[s // bs, :, s % bs] = kq[i]
+        vc[s // bs, :, s % bs] = vq[i]
+
+
+def attention_kv8(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, hq, hkv, scale, k_scale=1.0, v_scale=1.0):
+    """Paged attention over an e4m3 cache: dequantise, then :func:`attention`."""
+    return attention(q, dequantize_kv8(k_cache, k_scale), dequantize_kv8(v_cache, v_scale), block_tables, cu_q,
+                     ctx_lens, hq, hkv, scale)
+
+
 def sample(logits, temperature=None, top_k=None, top_p=None, seeds=None, steps=None):
     """Greedy where temperature==0; otherwise a (non-bit-exact) torch sampler
     with the same filtering semantics (top-k, then top-p on the renormalised set)."""

@@ -411,6 +411,9 @@ def build_arg_parser():
     p.add_argument("--device", default=None, help="torch device for LLM backends (default cuda:0 / cpu)")
     p.add_argument("--num-kv-blocks", type=int, default=None)
     p.add_argument("--kv-block-ttl-s", type=float, default=None, help="TTL of cached (released) KV blocks")
+    p.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto",
+                   help="fp8: the KV pool holds e4m3 bytes, twice the blocks in the same memory (one GPU, dense "
+                        "models, role both)")
     p.add_argument("--kv-capacity-priority", action="store_true",
                    help="the KV pool is the constraint: decode weights in one layout (EngineConfig)")
     p.add_argument("--preproc-processes", type=int, default=0,
@@ -438,7 +441,8 @@ async def main(argv=None) -> None:
         model_name=args.model, model_path=args.model_path, batch_size=min(8, args.max_batch_size),
         max_batch_size=args.max_batch_size, arch=args.arch, preset=args.preset, tp_size=args.tp_size,
         role=args.role, max_model_len=args.max_model_len, max_latency_ms=args.max_latency_ms,
-        use_cuda_graph=not args.no_graph, num_kv_blocks=args.num_kv_blocks, overrides=overrides,
+        use_cuda_graph=not args.no_graph, num_kv_blocks=args.num_kv_blocks, kv_cache_dtype=args.kv_cache_dtype,
+        overrides=overrides,
         preproc_processes=args.preproc_processes,
     )
     worker = Worker(worker_id=args.worker_id or f"worker-{os.getpid()}", host=args.host, port=args.port,
