@@ -1,7 +1,8 @@
 """What kv_cache_dtype="fp8" costs and buys at the engine level: the same model (random weights), the same memory
 fraction and the same requests (batch x (prompt -> gen), greedy) on a bf16 pool and on an e4m3 pool. Prints per
-dtype the planned block count and the wall time of one wave after a warm-up wave; the FP8 engine's decode steps
-run _forward_decode_slab instead of the five-launch fused layer.
+dtype the planned block count and the wall time of one wave after a warm-up wave. Both engines decode on the
+five-launch fused layer (the FP8 one through attention_kv8.hip's fused prologue; before that kernel existed its
+decode steps ran _forward_decode_slab, which is what profiles/kv8_fused_decode_engine.jsonl compares against).
 python bench/kv8_engine_cost.py [preset] [batch] [prompt] [gen]"""
 import json
 import os

@@ -123,6 +123,53 @@ void attn_decode_kv8(Tensor out, Tensor part_o, Tensor part_ml, Tensor counters,
                                 cur_stream()));
 }
 
+// _C's attn_decode_fused over an e4m3 cache: q / the new K, V built from the qkv projection's fp32 split-K slabs
+// [sk, M, (hq + 2 hkv) * 128] (RMSNorm row scale from ssp [tiles, 128], RoPE from cos_sin [max_pos, 128] at position
+// ctx_len - 1); the new row goes to the paged cache at slot_mapping as e4m3(x / scale).
+void attn_decode_fused_kv8(Tensor out, Tensor part_o, Tensor part_ml, Tensor counters, Tensor slab, Tensor ssp,
+                           Tensor positions, Tensor cos_sin, Tensor slot_mapping, Tensor k_cache, Tensor v_cache,
+                           Tensor block_tables, Tensor ctx_lens, int64_t max_ctx, int64_t hq, int64_t hkv, double scale,
+                           double eps, int64_t hidden, double k_scale, double v_scale, bool kv_once) {
+  const Op a("attn_decode_fused_kv8", slab, "slab");
+  const int64_t D = HEAD_DIM;
+  TORCH_CHECK(hkv >= 1 && hq % hkv == 0, "attn_decode_fused_kv8: hq % hkv");
+  const int64_t G = hq / hkv;
+  TORCH_CHECK(G == 1 || G == 2 || G == 4 || G == 8, "attn_decode_fused_kv8: hq / hkv in {1, 2, 4, 8}, got ", G);
+  const int* ctx = a.dense<int>(ctx_lens, "ctx_lens", 0);
+  const int nseq = a.i32(ctx_lens.numel());
+  const Caches c = check_caches(a, k_cache, v_cache, hkv);
+  TORCH_CHECK(c.bs == 16, "attn_decode_fused_kv8: block_size 16, got ", c.bs);
+  const int* bt = a.dense<int>(block_tables, "block_tables", 0, {ge(nseq), ge(1)});
+  TORCH_CHECK(max_ctx >= 1 && block_tables.size(1) * c.bs >= max_ctx,
+              "attn_decode_fused_kv8: block table narrower than max_ctx");
+  const int64_t maxp = (a.i32(max_ctx) + 127) / 128;
+  float* po = a.dense<float>(part_o, "part_o", nseq * hq * maxp * D, {}, 16);
+  float* pm = a.dense<float>(part_ml, "part_ml", nseq * hq * maxp * 2, {}, 8);
+  int* cnt = a.dense<int>(counters, "counters", nseq * hkv);
+  die::AttnDecodeFuse fz;
+  fz.slab = a.dense<float>(slab, "slab", 0, {ge(1), ge(nseq), (hq + 2 * hkv) * D}, 16);
+  fz.sk = a.i32(slab.size(0));
+  fz.slab_stride = slab.size(1) * slab.size(2);
+  fz.width = a.i32(slab.size(2));
+  bf16_t* op = a.dense<bf16_t>(out, "out", nseq * hq * D, {}, 16);
+  fz.ssp = a.dense<float>(ssp, "ssp", 0, {ANY, die::DECODE_SSP_LD});
+  TORCH_CHECK(ssp.size(0) >= 1 && ssp.size(0) <= die::DECODE_SSP_MAX_TILES && nseq <= die::DECODE_SSP_LD,
+              "attn_decode_fused_kv8: ssp [tiles <= 256, 128], <= 128 sequences");
+  fz.ssp_tiles = a.i32(ssp.size(0));
+  TORCH_CHECK(hidden >= 1, "attn_decode_fused_kv8: hidden >= 1");
+  fz.inv_n = 1.f / (float)hidden;
+  fz.eps = (float)eps;
+  // decode: every sequence's new token sits at position ctx_len - 1 <= max_ctx - 1 (the kernel reads that table row)
+  const RopeIndex ix = check_rope_index(a, positions, slot_mapping, cos_sin, nseq);
+  TORCH_CHECK(cos_sin.size(0) >= max_ctx, "attn_decode_fused_kv8: cos_sin has fewer rows than max_ctx");
+  fz.cos_sin = ix.cos_sin;
+  fz.slot_mapping = ix.slots;
+  const Scales sc = check_scales(a, k_scale, v_scale);
+  LAUNCH(launch_attn_decode_fused_kv8(op, po, pm, cnt, c.k, c.v, bt, a.i32(block_tables.size(1)), ctx, nseq,
+                                      a.i32(max_ctx), a.i32(hq), a.i32(hkv), (int)D, c.bs, (float)scale, sc.k, sc.v,
+                                      &fz, kv_once, cur_stream()));
+}
+
 int64_t decode_part_keys(int64_t num_seqs, int64_t hkv, int64_t max_ctx) {
   return die::attn_decode_kv8_part_keys((int)num_seqs, (int)hkv, (int)max_ctx);
 }
@@ -161,6 +208,7 @@ PYBIND11_MODULE(_C_kv8, m) {
   m.def("rope_and_cache_kv8", &rope_and_cache_kv8);
   m.def("rope_and_cache_slab_kv8", &rope_and_cache_slab_kv8);
   m.def("attn_decode_kv8", &attn_decode_kv8);
+  m.def("attn_decode_fused_kv8", &attn_decode_fused_kv8);
   m.def("attn_prefill_kv8", &attn_prefill_kv8);
   m.def("decode_part_keys", &decode_part_keys);
   m.def("check_only", &check_only);

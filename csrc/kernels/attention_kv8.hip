@@ -36,6 +36,39 @@
 //    and receives column i of the 8 rows: with row j -> key 16 s2 + 4h + (j & 3) + 8 (j >> 2) that is exactly the
 //    key order of the P fragment (the S^T accumulator layout), one read per MFMA instead of the bf16 image's two.
 //
+// Fused prologue (attn_decode_kv8_kernel<G, FUSED = true>): the semantics of attn_decode_v3_kernel<G, true> with an
+// e4m3 cache. q and the step's new K / V row are not read from a rotated qkv tensor: they are built here from the qkv
+// projection's fp32 split-K slabs (summed in index order from +0, as v3's slab_sum, so the fp32 values are that
+// path's), scaled by rn = rsqrt(sum(statistics tiles) * inv_n + eps) and rotated at position ctx - 1. The q rows are
+// rounded to bf16 once into the q image; the new K / V are quantised from the fp32 values (sat + quant4, the writers'
+// rule: nothing goes through bf16), stored to the paged cache (slot < 0, a padded graph row: not stored) and patched
+// into this step's LDS image of the chunk that holds key ctx - 1, so the step attends to the bytes later steps read.
+// The RMSNorm and RoPE + KV-write launches and the bf16 q round trip of the slab path disappear. The design:
+//  * LDS plan. The staging (slab rows of 512 B: [split][q head], then [split][k, v]; behind them 1 KiB of statistics
+//    tiles and the RoPE row) gets an area of ITS OWN behind the q image: 27 KiB, v3's limit, so the qkv split-K plan
+//    and the engine's size clause are those of the bf16 pool; 115 + 27 = 142 KiB of 160. v3 has to overlay its
+//    staging on the merge area; here nothing else ever lives in it, which buys this at a task boundary: a wave that
+//    leaves a task's merge issues the next task's prologue DMA at once, BEFORE the barrier that hands over the ring
+//    and the merge area, while slower waves still read (m, l, O) or merge the parts. (Every wave's staging reads lie
+//    before the merge's first barrier, so the staging itself needs none.) The gain is unmeasured: at one task per
+//    workgroup, the flagship shape, there is no boundary.
+//  * DMA order and counted waits. Per wave: its share of the slab rows (two rows per instruction), wave 0 the tiles,
+//    wave 1 the RoPE row, then chunk c0 (8 instructions) and chunk c0 + 1 (8). The prologue waits on vmcnt(16) (8
+//    where the part has one chunk): the small operands have landed, both chunks stay in flight, and the chunk
+//    loop's 16 / 8 / 0 are unchanged. The prologue itself touches memory only through LDS (inline asm reads tied to
+//    their own lgkmcnt waits), so no ordinary vector load puts a vmcnt(0) in front of the chunk stream. v3 holds its
+//    second 64 KiB chunk back until the prologue is done; here BOTH 32 KiB chunks are issued ahead of the prologue:
+//    64 KiB per CU is what v3 has in flight at that point, and the small operands sit in front of them in the queue.
+//    That choice is UNMEASURED on the e4m3 kernel.
+//  * Who builds what: an item is 4 consecutive dims, a 16-byte LDS read per slab. Lanes [0, 16 G) of waves 0 - 1 each
+//    rotate 4 dims and their 4 partners of one q row (two 8-byte q-image stores); in wave 3, which has no q item at
+//    any G, 16 lanes do the same for the new key and 16 more take the same two groups of 4 value dims, unrotated
+//    (two dwords of e4m3 per lane; no byte-per-thread store anywhere). The dwords stay in
+//    registers until the last chunk of the part has landed (vmcnt(0), then a workgroup barrier: the row may be
+//    another wave's DMA); there each dword is ONE cache store and ONE LDS patch store, at 16-byte chunk
+//    (d >> 4) ^ ((rr >> 1) & 7), byte d & 15 of row rr = (ctx - 1) & 127. The cache stores come after the part's last
+//    counted wait, so they never sit in front of one. A part that does not hold key ctx - 1 stages only the q rows.
+//
 // Prefill (attn_prefill_kv8_kernel): attn_prefill_kernel's pipeline (register-staged double-buffered K/V stages, the
 // padded bf16 LDS image, lazy-rescale softmax, XCD remap, LDS-staged epilogue) with a new staging role: a key row
 // is 8 chunks of 16 B (8 lanes per row, 8 NW rows per pass), held as bytes in the two register sets (half the
@@ -248,6 +281,25 @@ constexpr int K8_MERGE = K8_ML + 4 * 8 * D * 4;   // + per-wave O of G <= 8: 17 
 constexpr int K8_QOFF = K8_RING * K8_CHUNK + K8_MERGE;  // q image: G <= 8 rows x 256 B
 constexpr int K8_LDS = K8_QOFF + 2048 + 16;
 static_assert(K8_LDS <= 160 * 1024, "one workgroup per CU");
+// FUSED: the prologue's staging, an area of its own behind the control words (v3's 27 KiB limit)
+constexpr int K8_STAGE = 27 * 1024;
+constexpr int K8_LDS_FUSED = K8_LDS + K8_STAGE;
+static_assert(K8_LDS % 16 == 0 && K8_LDS_FUSED <= 160 * 1024, "one fused workgroup per CU");
+
+// LDS traffic of the fused prologue, in inline asm as attn_common.h's merge-area helpers (and for their reason)
+__device__ __forceinline__ void lds_ld128x2(uint32_t a, uint32_t b, f32x4_t& x, f32x4_t& y) {
+  asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %3\n\ts_waitcnt lgkmcnt(0)"
+               : "=&v"(x), "=&v"(y)
+               : "v"(a), "v"(b)
+               : "memory");
+}
+__device__ __forceinline__ void lds_st64(uint32_t a, uint32_t lo, uint32_t hi) {
+  const u32x2_t v = {lo, hi};
+  asm volatile("ds_write_b64 %0, %1" ::"v"(a), "v"(v) : "memory");
+}
+__device__ __forceinline__ void lds_st32u(uint32_t a, uint32_t v) {
+  asm volatile("ds_write_b32 %0, %1" ::"v"(a), "v"(v) : "memory");
+}
 
 // S^T tile of this wave's 32 keys from the swizzled e4m3 K image; qf[2j + e] holds dims 32j + 16h + 8e + [0, 8).
 // The reads are inline asm retired by one wait tied to their results (as pv_lds_swz_v3: the compiler cannot tell
@@ -303,13 +355,16 @@ __device__ __forceinline__ void pv_kv8(const char* vimg, const f32x16_t& p, Stat
       st.o[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(widen8(t[db][s2][0], t[db][s2][1]), pf[s2], st.o[db], 0, 0, 0);
 }
 
-// grid = min(tasks, CUs); block = 256; dynamic LDS = K8_LDS. scale_log2 carries k_scale.
-template <int G, int KV_AUX>
+// grid = min(tasks, CUs); block = 256; dynamic LDS = K8_LDS (FUSED: K8_LDS_FUSED). scale_log2 carries k_scale.
+// FUSED (the file header): q / q_stride are unused; fz, slot_mapping, k_scale and the caches' writable aliases
+// kw / vw feed the prologue. Without it they are unused and the kernel is what it was.
+template <int G, bool FUSED, int KV_AUX>
 __global__ void __launch_bounds__(256, 1) attn_decode_kv8_kernel(
     const int* __restrict__ block_tables, const int* __restrict__ ctx_lens, int bt_stride, int num_seqs, int hkv,
     int maxp, int cpp, const uint8_t* __restrict__ k_cache, const uint8_t* __restrict__ v_cache, int hq,
     float scale_log2, float v_scale, const bf16_t* __restrict__ q, int64_t q_stride, bf16_t* __restrict__ out,
-    float* __restrict__ part_o, float* __restrict__ part_ml, int* __restrict__ counters) {
+    float* __restrict__ part_o, float* __restrict__ part_ml, int* __restrict__ counters, AttnDecodeFuse fz,
+    const int64_t* __restrict__ slot_mapping, float k_scale, uint8_t* kw, uint8_t* vw) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   float* ml = reinterpret_cast<float*>(smem + K8_RING * K8_CHUNK);
   float* ob = reinterpret_cast<float*>(smem + K8_RING * K8_CHUNK + K8_ML);
@@ -320,6 +375,13 @@ __global__ void __launch_bounds__(256, 1) attn_decode_kv8_kernel(
   const int C = cpp;  // chunks per part (host: launch_attn_decode_kv8)
   const int np = (maxp + C - 1) / C;
   const int n_tasks = pairs * np;
+  // FUSED staging: slab rows x 128 fp32, [split][q heads] then [split][k, v]; behind them the statistics tiles
+  // (1 KiB) and the RoPE row. A part without the step's new token stages only the q rows.
+  char* fa = smem + K8_LDS;
+  const int fsk = FUSED ? fz.sk : 0;
+  const int frows = fsk * (G + 2), qrows = fsk * G;
+  const int fs_off = ((frows + 1) / 2) * 1024;
+  bool ran = false;  // FUSED: a task of this workgroup has used the ring and the merge area
 
 #pragma unroll 1
   for (int t = blockIdx.x; t < n_tasks; t += gridDim.x) {
@@ -332,10 +394,39 @@ __global__ void __launch_bounds__(256, 1) attn_decode_kv8_kernel(
     if (c0 >= nch) continue;  // uniform
     const int c1 = min(c0 + C, nch);
     const int last_blk = (ctx - 1) >> 4;
+    const bool has_new = FUSED && c1 == nch;  // this part holds the step's new token (key ctx - 1)
 
-    // the G query rows (256 B each) go to the q image by LDS-DMA, ahead of the first chunk in the same queue, so
-    // no ordinary load sits in front of the counted chunk waits
-    if (wave == 0) {
+    if constexpr (FUSED) {
+      // the prologue's operands, ahead of the first chunk in the same queue
+      const float* srow = fz.slab + (int64_t)seq * fz.width;
+      const int nrows = has_new ? frows : qrows;
+      for (int i = wave; i < (nrows + 1) / 2; i += 4) {  // two rows per instruction (an odd count: the last twice)
+        const int ri = min(2 * i + (lane >> 5), nrows - 1);
+        int sl, j;
+        if (ri < qrows) {
+          sl = ri / G;
+          j = ri - sl * G;
+        } else {
+          sl = (ri - qrows) >> 1;
+          j = G + ((ri - qrows) & 1);
+        }
+        const int col = j < G ? (kvh * G + j) * D : (j == G ? (hq + kvh) * D : (hq + hkv + kvh) * D);
+        glds16(srow + sl * fz.slab_stride + col + (lane & 31) * 4, fa + i * 1024);
+      }
+      if (wave == 0) {  // the statistics tiles (<= 256: 4 x 64 lanes; the upper two only when present)
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+          if (i < 2 || 64 * i < fz.ssp_tiles)
+            glds4(fz.ssp + min(lane + 64 * i, fz.ssp_tiles - 1) * DECODE_SSP_LD + seq, fa + fs_off + i * 256);
+      }
+      if (wave == 1)  // decode: the new token sits at position ctx - 1
+        glds16(fz.cos_sin + (int64_t)(ctx - 1) * D + (lane & 31) * 4, fa + fs_off + 1024);
+      // the staging is nobody else's, so only now the hand-over of the ring and the merge area by the previous task
+      if (ran) lds_barrier();
+      ran = true;
+    } else if (wave == 0) {
+      // the G query rows (256 B each) go to the q image by LDS-DMA, ahead of the first chunk in the same queue, so
+      // no ordinary load sits in front of the counted chunk waits
       const bf16_t* qb = q + (int64_t)seq * q_stride + (int64_t)kvh * G * D;
 #pragma unroll
       for (int i = 0; i < QI; ++i) {
@@ -369,6 +460,72 @@ __global__ void __launch_bounds__(256, 1) attn_decode_kv8_kernel(
     bf16x8_t qf[8];
     issue(c0, 0);
     if (c0 + 1 < c1) issue(c0 + 1, 1);
+    uint32_t nk0 = 0, nk1 = 0;  // FUSED: this lane's two dwords of the new token's e4m3 K or V row
+    if constexpr (FUSED) {
+      // the prologue's operands have landed; the chunks issued behind them stay in flight
+      if (c0 + 1 < c1)
+        wait_vm<16>();
+      else
+        wait_vm<8>();
+      __builtin_amdgcn_s_barrier();
+      const uint32_t fb = lds_addr(fa), cs = fb + fs_off + 1024;
+      // rn = rsqrt(mean(h^2) + eps) of this sequence's row (v3's order of the sum)
+      float ssum = 0.f;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        ssum += lane + 64 * i < fz.ssp_tiles ? lds_ld32(fb + fs_off + 4 * (lane + 64 * i)) : 0.f;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) ssum += __shfl_xor(ssum, o, 64);
+      const float rn = rsqrtf(ssum * fz.inv_n + fz.eps);
+      // 4 dims d .. d + 3 and their rotation partners of staged row j (q head j < G, G: k, G + 1: v) of every
+      // split, summed in index order from +0 and scaled
+      auto sum4x2 = [&](int j, int d, float* a, float* bq) {
+        f32x4_t va = {0.f, 0.f, 0.f, 0.f}, vb = va;
+        for (int sl = 0; sl < fsk; ++sl) {
+          const uint32_t r = fb + (((j < G ? sl * G : qrows + 2 * sl - G) + j) * D + d) * 4;
+          f32x4_t x, y;
+          lds_ld128x2(r, r + 4 * HALF, x, y);
+          va += x;
+          vb += y;
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          a[e] = va[e] * rn;
+          bq[e] = vb[e] * rn;
+        }
+      };
+      auto rot4 = [&](int j, int d, float* ya, float* yb) {
+        float a[4], bq[4];
+        sum4x2(j, d, a, bq);
+        f32x4_t co, si;
+        lds_ld128x2(cs + 4 * d, cs + 4 * (d + HALF), co, si);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          ya[e] = a[e] * co[e] - bq[e] * si[e];
+          yb[e] = bq[e] * co[e] + a[e] * si[e];
+        }
+      };
+      if (tid < 16 * G) {  // the rotated query rows, rounded to bf16 once -> q image
+        const int j = tid >> 4, d = 4 * (tid & 15);
+        float ya[4], yb[4];
+        rot4(j, d, ya, yb);
+        const uint32_t qa = lds_addr(smem + K8_QOFF + j * 256);
+        lds_st64(qa + 2 * d, pack2(ya[0], ya[1]), pack2(ya[2], ya[3]));
+        lds_st64(qa + 2 * (d + HALF), pack2(yb[0], yb[1]), pack2(yb[2], yb[3]));
+      } else if (has_new && tid >= 192 && tid < 208) {  // the new key: e4m3 from the fp32 values
+        float ya[4], yb[4];
+        rot4(G, 4 * (tid - 192), ya, yb);
+        nk0 = quant4(ya, k_scale);
+        nk1 = quant4(yb, k_scale);
+      } else if (has_new && tid >= 208 && tid < 224) {  // the new value: the same two groups of 4 dims, unrotated
+        float f0[4], f1[4];
+        sum4x2(G + 1, 4 * (tid - 208), f0, f1);
+        nk0 = quant4(f0, v_scale);
+        nk1 = quant4(f1, v_scale);
+      }
+      // the q image is read after the first chunk's barrier below: retire this wave's LDS writes first
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    }
     int b = 0;
 #pragma unroll 1
     for (int c = c0; c < c1; ++c) {
@@ -381,10 +538,34 @@ __global__ void __launch_bounds__(256, 1) attn_decode_kv8_kernel(
       } else {
         wait_vm<0>();
       }
+      // a wave needs another wave's data at the first chunk (the q image: wave 0's DMA, or FUSED every thread's
+      // stores) and, FUSED, at the chunk that gets the new token's row patched in (the row may be another wave's DMA)
+      if (c == c0 || (FUSED && has_new && c + 1 == c1)) __builtin_amdgcn_s_barrier();
+      if constexpr (FUSED) {
+        if (has_new && c + 1 == c1) {
+          // the part's last chunk: vmcnt(0) above, so the cache stores sit in front of no counted wait. Each dword
+          // goes to the paged cache (for later steps; slot < 0: a padded graph row, not stored) and to the same
+          // row of this step's LDS image, at its swizzled place
+          const int rr = (ctx - 1) - c * DEC_KEYS, sw = (rr >> 1) & 7;
+          const int64_t slot = slot_mapping[seq];
+          const int64_t roff = (((slot >> 4) * hkv + kvh) * 16 + (slot & 15)) * K8_ROW;
+          if (tid >= 192 && tid < 224) {
+            const bool isv = tid >= 208;
+            const int d = 4 * (tid - (isv ? 208 : 192));
+            const uint32_t img = lds_addr(smem + b * K8_CHUNK) + (isv ? K8_IMG : 0) + rr * K8_ROW + (d & 15);
+            lds_st32u(img + 16 * ((d >> 4) ^ sw), nk0);
+            lds_st32u(img + 16 * (((d + HALF) >> 4) ^ sw), nk1);
+            if (slot >= 0) {
+              uint8_t* dst = (isv ? vw : kw) + roff + d;
+              *reinterpret_cast<uint32_t*>(dst) = nk0;
+              *reinterpret_cast<uint32_t*>(dst + HALF) = nk1;
+            }
+          }
+          lds_barrier();
+        }
+      }
       if (c == c0) {
-        // the q image is wave 0's DMA: the only point where a wave needs another wave's data. The fragments follow
-        // qk_kv8's contraction order: step 2j + e is 16-byte chunk 4j + 2h + e of the row
-        __builtin_amdgcn_s_barrier();
+        // the fragments follow qk_kv8's contraction order: step 2j + e is 16-byte chunk 4j + 2h + e of the row
 #pragma unroll
         for (int j = 0; j < 8; ++j)
           qf[j] = row < G ? __builtin_bit_cast(bf16x8_t, lds_ld128(lds_addr(smem + K8_QOFF + row * 256 +
@@ -508,7 +689,8 @@ __global__ void __launch_bounds__(256, 1) attn_decode_kv8_kernel(
         if (tid == 0) __hip_atomic_store(counters + pair, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
-    lds_barrier();  // merge area and ring are reused by the next task
+    // merge area and ring are reused by the next task (FUSED: the barrier follows that task's staging DMA, above)
+    if constexpr (!FUSED) lds_barrier();
   }
 }
 
@@ -526,31 +708,47 @@ int attn_decode_kv8_part_keys(int num_seqs, int hkv, int max_ctx) {
   return DEC_KEYS * kv8_chunks_per_part(num_seqs * hkv, maxp, nullptr);
 }
 
-hipError_t launch_attn_decode_kv8(bf16_t* out, float* part_o, float* part_ml, int* counters, const bf16_t* q,
-                                  int64_t q_stride, const uint8_t* k_cache, const uint8_t* v_cache,
-                                  const int* block_tables, int bt_stride, const int* ctx_lens, int num_seqs, int max_ctx,
-                                  int hq, int hkv, int head_dim, int block_size, float scale, float k_scale,
-                                  float v_scale, bool kv_once, hipStream_t s) {
+// both decode launchers; fz != nullptr: the fused prologue, kw / vw the caches' writable aliases
+static hipError_t decode_kv8(bf16_t* out, float* part_o, float* part_ml, int* counters, const bf16_t* q,
+                             int64_t q_stride, const uint8_t* k_cache, const uint8_t* v_cache, uint8_t* kw, uint8_t* vw,
+                             const int* block_tables, int bt_stride, const int* ctx_lens, int num_seqs, int max_ctx,
+                             int hq, int hkv, int head_dim, int block_size, float scale, float k_scale, float v_scale,
+                             const AttnDecodeFuse* fz, bool kv_once, hipStream_t s) {
   if (num_seqs == 0) return hipSuccess;
   if (head_dim != D || hkv < 1 || hq % hkv || block_size != 16 || counters == nullptr || max_ctx < 1 || bt_stride < 1)
     return hipErrorInvalidValue;
   const int G = hq / hkv;
   const int maxp = (max_ctx + DEC_KEYS - 1) / DEC_KEYS;
   if ((int64_t)num_seqs * hq * maxp * D * 4 >= ((int64_t)1 << 31)) return hipErrorInvalidValue;  // 32-bit buffer offsets
+  AttnDecodeFuse fzc{};
+  if (fz != nullptr) {
+    if (!(k_scale > 0.f) || !(v_scale > 0.f) || fz->slab == nullptr || fz->ssp == nullptr || fz->cos_sin == nullptr ||
+        fz->slot_mapping == nullptr || fz->sk < 1 || fz->ssp_tiles < 1 || fz->ssp_tiles > DECODE_SSP_MAX_TILES ||
+        num_seqs > DECODE_SSP_LD || fz->width != (hq + 2 * hkv) * D ||
+        ((fz->sk * (G + 2) + 1) / 2) * 1024 + 2048 > K8_STAGE)
+      return hipErrorInvalidValue;
+    fzc = *fz;
+    fzc.ts = nullptr;
+  }
+  const int64_t* slots = fzc.slot_mapping;
   const float sl2 = scale * 1.4426950408889634f * k_scale;
   int gridx = 1;
   const int cpp = kv8_chunks_per_part(num_seqs * hkv, maxp, &gridx);
   dim3 grid(gridx), block(256);
-#define K8_LAUNCH(GG, AUX)                                                                                          \
-  hipLaunchKernelGGL((attn_decode_kv8_kernel<GG, AUX>), grid, block, K8_LDS, s, block_tables, ctx_lens, bt_stride,   \
-                     num_seqs, hkv, maxp, cpp, k_cache, v_cache, hq, sl2, v_scale, q, q_stride, out, part_o, part_ml, \
-                     counters)
-#define K8_CASE(GG)                        \
-  case GG:                                 \
-    if (kv_once)                           \
-      K8_LAUNCH(GG, KV_AUX_ONCE);          \
-    else                                   \
-      K8_LAUNCH(GG, KV_AUX_DEFAULT);       \
+#define K8_LAUNCH(GG, FU, AUX)                                                                                     \
+  hipLaunchKernelGGL((attn_decode_kv8_kernel<GG, FU, AUX>), grid, block, FU ? K8_LDS_FUSED : K8_LDS, s, block_tables, \
+                     ctx_lens, bt_stride, num_seqs, hkv, maxp, cpp, k_cache, v_cache, hq, sl2, v_scale, q, q_stride, \
+                     out, part_o, part_ml, counters, fzc, slots, k_scale, kw, vw)
+#define K8_CASE(GG)                              \
+  case GG:                                       \
+    if (fz && kv_once)                           \
+      K8_LAUNCH(GG, true, KV_AUX_ONCE);          \
+    else if (fz)                                 \
+      K8_LAUNCH(GG, true, KV_AUX_DEFAULT);       \
+    else if (kv_once)                            \
+      K8_LAUNCH(GG, false, KV_AUX_ONCE);         \
+    else                                         \
+      K8_LAUNCH(GG, false, KV_AUX_DEFAULT);      \
     break;
   switch (G) {
     K8_CASE(1)
@@ -563,6 +761,27 @@ hipError_t launch_attn_decode_kv8(bf16_t* out, float* part_o, float* part_ml, in
 #undef K8_CASE
 #undef K8_LAUNCH
   return hipGetLastError();
+}
+
+hipError_t launch_attn_decode_kv8(bf16_t* out, float* part_o, float* part_ml, int* counters, const bf16_t* q,
+                                  int64_t q_stride, const uint8_t* k_cache, const uint8_t* v_cache,
+                                  const int* block_tables, int bt_stride, const int* ctx_lens, int num_seqs, int max_ctx,
+                                  int hq, int hkv, int head_dim, int block_size, float scale, float k_scale,
+                                  float v_scale, bool kv_once, hipStream_t s) {
+  return decode_kv8(out, part_o, part_ml, counters, q, q_stride, k_cache, v_cache, nullptr, nullptr, block_tables,
+                    bt_stride, ctx_lens, num_seqs, max_ctx, hq, hkv, head_dim, block_size, scale, k_scale, v_scale,
+                    nullptr, kv_once, s);
+}
+
+hipError_t launch_attn_decode_fused_kv8(bf16_t* out, float* part_o, float* part_ml, int* counters, uint8_t* k_cache,
+                                        uint8_t* v_cache, const int* block_tables, int bt_stride, const int* ctx_lens,
+                                        int num_seqs, int max_ctx, int hq, int hkv, int head_dim, int block_size,
+                                        float scale, float k_scale, float v_scale, const AttnDecodeFuse* fz,
+                                        bool kv_once, hipStream_t s) {
+  if (fz == nullptr) return hipErrorInvalidValue;
+  return decode_kv8(out, part_o, part_ml, counters, nullptr, 0, k_cache, v_cache, k_cache, v_cache, block_tables,
+                    bt_stride, ctx_lens, num_seqs, max_ctx, hq, hkv, head_dim, block_size, scale, k_scale, v_scale, fz,
+                    kv_once, s);
 }
 
 // ----------------------------------------------------------------------------------------------------- prefill

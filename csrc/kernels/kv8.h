@@ -28,7 +28,16 @@ hipError_t launch_attn_decode_kv8(bf16_t* out, float* part_o, float* part_ml, in
                                   const int* block_tables, int bt_stride, const int* ctx_lens, int num_seqs, int max_ctx,
                                   int hq, int hkv, int head_dim, int block_size, float scale, float k_scale,
                                   float v_scale, bool kv_once, hipStream_t s);
-// keys per part of the launch above (a context longer than this is cut into parts merged by ticket)
+// the same with the fused prologue (attn_decode_kv8_kernel<G, true>): q and the new token's K / V are built from the
+// operands of launch_attn_decode's AttnDecodeFuse (fz.ts is ignored), the new row is written to the cache as e4m3
+// bytes (slot_mapping < 0: not written) and attended to in this step. hipErrorInvalidValue when the slab staging,
+// ((sk (G + 2) + 1) / 2) * 1024 + 2048 bytes, does not fit its 27 KiB of LDS, or num_seqs > DECODE_SSP_LD.
+hipError_t launch_attn_decode_fused_kv8(bf16_t* out, float* part_o, float* part_ml, int* counters, uint8_t* k_cache,
+                                        uint8_t* v_cache, const int* block_tables, int bt_stride, const int* ctx_lens,
+                                        int num_seqs, int max_ctx, int hq, int hkv, int head_dim, int block_size,
+                                        float scale, float k_scale, float v_scale, const AttnDecodeFuse* fz,
+                                        bool kv_once, hipStream_t s);
+// keys per part of the launches above (a context longer than this is cut into parts merged by ticket)
 int attn_decode_kv8_part_keys(int num_seqs, int hkv, int max_ctx);
 // launch_attn_prefill over an e4m3 cache
 hipError_t launch_attn_prefill_kv8(bf16_t* out, const bf16_t* q, int64_t q_stride, const uint8_t* k_cache,

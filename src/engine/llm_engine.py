@@ -53,8 +53,8 @@ def check_kv_cache_dtype(cfg: EngineConfig, model: CausalLM) -> None:
     if model.tp.enabled:
         raise ValueError("kv_cache_dtype='fp8' is not available on a tensor-parallel engine")
     if model.arch.is_moe:
-        raise ValueError("kv_cache_dtype='fp8' is not available on a MoE model: its decode needs the fused "
-                         "attention prologue, which has no FP8 form")
+        raise ValueError("kv_cache_dtype='fp8' is not available on a MoE model: its decode takes the fused "
+                         "attention prologue, whose FP8 form is served for dense models only so far")
     if model.head_dim != 128 or cfg.block_size != 16 or model.hq // model.hkv not in (1, 2, 4, 8):
         raise ValueError("kv_cache_dtype='fp8' needs head_dim 128, block_size 16 and hq / hkv in {1, 2, 4, 8}")
 

@@ -841,9 +841,12 @@ class CausalLM:
     def _fused_decode_ok(self, kv_pool: torch.Tensor, m: int = 32) -> bool:
         g = self.hq // self.hkv
         sq = self.decode_plan(m)["qkv"][2]
-        # a one-byte (FP8) pool has no fused prologue: its decode steps take _forward_decode_slab
+        # a one-byte (FP8) pool takes the fused prologue of attention_kv8.hip (the same staging limit); a _C_kv8
+        # without that entry leaves its decode steps on _forward_decode_slab
+        if kv_pool.element_size() == 1 and not ops.fused_decode_kv8_available():
+            return False
         return (self.norms_folded and self.head_dim == 128 and kv_pool.shape[4] == 16 and g in (1, 2, 4, 8)
-                and kv_pool.element_size() == 2
+                and kv_pool.element_size() in (1, 2)
                 and ((sq * (g + 2) + 1) // 2) * 1024 + 2048 <= V3_MERGE_BYTES)
 
     def _forward_decode_fused(self, h: torch.Tensor, positions: torch.Tensor, meta: AttnMetadata,
@@ -877,7 +880,7 @@ class CausalLM:
             attn = ops.attn_decode_fused(slab, ssp_prev, positions, self.cos_sin, meta.slot_mapping,
                                          k_cache, v_cache, meta.block_tables, meta.ctx_lens, meta.max_ctx, hq, hkv,
                                          self.scale, eps, hid, meta.part_o, meta.part_ml, meta.attn_cnt,
-                                         kv_once=meta.kv_once)
+                                         kv_once=meta.kv_once, kv_scales=self.kv_scales[li])
             if a.is_moe:  # ln2 stays explicit (it also feeds the router); MoE output added back + statistics
                 if self.tp.enabled:
                     self.tp.all_reduce_residual(ops.linear(attn, lw.o), h, ssp_a)

@@ -50,6 +50,11 @@ def _kern_kv8():
     return _C_kv8
 
 
+def fused_decode_kv8_available() -> bool:
+    """src/_C_kv8 is loaded and has the fused-prologue decode attention over the FP8 pool."""
+    return hasattr(_C_kv8, "attn_decode_fused_kv8")
+
+
 def _kern():
     if _C is None:
         raise RuntimeError(
@@ -227,14 +232,20 @@ def attn_decode_fused(qkv_slab: torch.Tensor, ssp: torch.Tensor, positions: torc
                       block_tables: torch.Tensor, ctx_lens: torch.Tensor, max_ctx: int, hq: int, hkv: int,
                       scale: float, eps: float, hidden: int, part_o: torch.Tensor, part_ml: torch.Tensor,
                       counters: torch.Tensor, out: Optional[torch.Tensor] = None,
-                      kv_once: bool = True) -> torch.Tensor:
+                      kv_once: bool = True, kv_scales: Tuple[float, float] = (1.0, 1.0)) -> torch.Tensor:
     """Decode attention whose prologue does the input RMSNorm row scale (statistics ssp [T, 32],
     weight folded into Wqkv), the split-K reduction of the qkv slabs [sk, M, width], RoPE at
     position ctx-1 and the paged KV write of the new token (attention.hip, FUSED). kv_once as in
-    attn_decode."""
+    attn_decode. A one-byte cache is the FP8 pool: the same step from attention_kv8.hip's fused kernel, the new
+    row stored as e4m3(x / scale), kv_scales = (k_scale, v_scale)."""
     n = ctx_lens.numel()
     if out is None:
         out = torch.empty(n, hq * 128, dtype=torch.bfloat16, device=qkv_slab.device)
+    if ref.is_kv8(k_cache):
+        _kern_kv8().attn_decode_fused_kv8(out, part_o, part_ml, counters, qkv_slab, ssp, positions, cos_sin,
+                                          slot_mapping, k_cache, v_cache, block_tables, ctx_lens, max_ctx, hq, hkv,
+                                          scale, eps, hidden, float(kv_scales[0]), float(kv_scales[1]), kv_once)
+        return out
     _kern().attn_decode_fused(out, part_o, part_ml, counters, qkv_slab, ssp, positions, cos_sin, slot_mapping,
                               k_cache, v_cache, block_tables, ctx_lens, max_ctx, hq, hkv, scale, eps, hidden,
                               kv_once)
