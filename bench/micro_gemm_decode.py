@@ -64,6 +64,8 @@ def main():
         return main_moe(m)
     if len(sys.argv) > 2 and sys.argv[2] == "chain":
         return main_chain(m)
+    if "--w8" in sys.argv[2:]:
+        return main_w8(m)
     dev = torch.device("cuda:0")
     for name, (n, k, silu) in SHAPES.items():
         wrows = 2 * n if silu else n
@@ -91,6 +93,40 @@ def main():
             print(json.dumps({"shape": name, "M": m, "N": n, "K": k, "variant": v, "us": round(us, 2),
                               "GBps": round(wbytes / us / 1e3, 1)}), flush=True)
         del ws
+        torch.cuda.empty_cache()
+
+
+def main_w8(m):
+    """The W8A16 decode GEMM (FP8 weights, ops.gemm_decode_w8) against the bf16 kernel at its tuned tile: the same
+    shapes, cold weights (1.5 GiB of copies cycled), every W8 tile that divides the shape x its split counts."""
+    dev = torch.device("cuda:0")
+    for name, (n, k, silu) in SHAPES.items():
+        if name.startswith("lm_head"):
+            continue
+        mode = MODE_SILU if silu else MODE_SLAB
+        wr, kc, sk = ops.decode_tile(n, k, mode, 32)
+        wrows = 2 * n if silu else n
+        x = torch.randn(m, k, device=dev, dtype=torch.bfloat16)
+        copies = max(2, int(1.5 * 2**30 // (wrows * k * 2)) + 1)
+        ws = [torch.randn(wrows, k, device=dev, dtype=torch.bfloat16) / 64 for _ in range(copies)]
+        us = timeit(lambda w: ops.gemm_decode(x, w, mode, wr, sk, kc=kc), ws)
+        print(json.dumps({"bench": "w8_micro", "shape": name, "M": m, "kernel": "bf16", "wr": wr, "kc": kc, "sk": sk,
+                          "us": round(us, 2), "GBps": round(wrows * k * 2 / us / 1e3, 1)}), flush=True)
+        del ws
+        torch.cuda.empty_cache()
+        copies = max(2, int(1.5 * 2**30 // (wrows * k)) + 1)
+        qs = [torch.randint(0, 0x78, (wrows, k), device=dev, dtype=torch.uint8) for _ in range(copies)]  # any layout: timing only
+        sc = torch.ones(wrows, device=dev)
+        for wr8, kc8 in ops.W8_TILES:
+            if (n % (wr8 // 2 if silu else wr8)) or k % kc8:
+                continue
+            for sk8 in ((1,) if silu else (1, 2, 4, 8)):
+                if sk8 > k // kc8:
+                    continue
+                us = timeit(lambda q: ops.gemm_decode_w8(x, q, sc, ops.W8_SILU if silu else ops.W8_SLAB, wr8, kc8, sk8), qs)
+                print(json.dumps({"bench": "w8_micro", "shape": name, "M": m, "kernel": "w8", "wr": wr8, "kc": kc8,
+                                  "sk": sk8, "us": round(us, 2), "GBps": round(wrows * k / us / 1e3, 1)}), flush=True)
+        del qs
         torch.cuda.empty_cache()
 
 

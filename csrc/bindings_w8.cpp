@@ -1,0 +1,71 @@
+// Torch bindings of the W8A16 decode GEMM (module `src._C_w8`, csrc/kernels/gemm_decode_w8.hip). A third module next
+// to `_C` and `_C_kv8` with the same rules (bindings.cpp): every argument is validated through the vocabulary of
+// arg_check.h before anything is launched on the current stream, and no tensor is asked for its address here.
+#include <torch/extension.h>
+#include <c10/hip/HIPStream.h>
+
+#include "arg_check.h"
+#include "kernels/gd_w8.h"
+#include "kernels/gd_w8_launch.h"
+
+using torch::Tensor;
+using chk::Op;
+using die::bf16_t;
+
+namespace {
+
+namespace w8 = die::gd::w8;
+
+inline hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
+
+void check_only(bool on) { chk::g_check_only = on; }
+
+bool tile_exists(int64_t wr, int64_t kc) {
+#define GD_W8_TILE(WR, KC) \
+  if (wr == WR && kc == KC) return true;
+  GD_W8_TILES(GD_W8_TILE)
+#undef GD_W8_TILE
+  return false;
+}
+
+// out: mode 0 bf16 [M, N]; mode 1 bf16 [M, N / 2]; mode 2 fp32 [sk, M, N]. wq: [N, K] e4m3 bytes (uint8 or
+// float8_e4m3fn) packed by gd_pack_weights_w8 for (wr, kc); scales: [N] fp32.
+void gemm_decode_w8(Tensor out, Tensor x, Tensor wq, Tensor scales, int64_t mode, int64_t wr, int64_t kc, int64_t sk) {
+  const Op a("gemm_decode_w8", x, "x");
+  const auto xr = a.rows(x, "x");
+  const int M = a.i32(x.size(0)), K = a.i32(x.size(1));
+  TORCH_CHECK(M <= w8::MAX_M, "gemm_decode_w8: at most ", w8::MAX_M, " rows, got ", M);
+  TORCH_CHECK(mode == 0 || mode == 1 || mode == 2, "gemm_decode_w8: mode 0 (bf16), 1 (SiLU) or 2 (slab), got ", mode);
+  TORCH_CHECK(tile_exists(wr, kc), "gemm_decode_w8: no W8 tile (", wr, ", ", kc, ")");
+  TORCH_CHECK(wq.scalar_type() == at::kByte || wq.scalar_type() == at::kFloat8_e4m3fn,
+              "gemm_decode_w8: wq must be uint8 or float8_e4m3fn, got ", wq.scalar_type());
+  const uint8_t* wp = static_cast<const uint8_t*>(a.dense<void>(wq, "wq", 0, {chk::ge(1), K}, 16));
+  const int N = a.i32(wq.size(0));
+  TORCH_CHECK(mode != 1 || N % 2 == 0, "gemm_decode_w8: the SiLU form takes [gate; up], an even row count");
+  const int64_t n_out = mode == 1 ? N / 2 : N, cols = mode == 1 ? wr / 2 : wr;
+  TORCH_CHECK(K >= kc && K % kc == 0, "gemm_decode_w8: K = ", K, " must be a multiple of kc = ", kc);
+  TORCH_CHECK(n_out % cols == 0, "gemm_decode_w8: ", n_out, " output columns are no multiple of the tile's ", cols);
+  TORCH_CHECK(sk >= 1 && sk <= K / kc && (mode == 2 || sk == 1), "gemm_decode_w8: sk = ", sk,
+              " must be in [1, K / kc] and 1 unless mode 2");
+  const float* sp = a.dense<float>(scales, "scales", N, {N}, 16);
+  if (mode == 2) {
+    float* op = a.dense<float>(out, "out", 0, {sk, M, n_out}, 16);
+    LAUNCH(launch_gemm_decode_w8(op, n_out, xr.p, xr.ld, wp, sp, M, N, K, (int)mode, (int)wr, (int)kc, (int)sk,
+                                 cur_stream()));
+  } else {
+    const auto o = a.rows(out, "out", M, n_out);
+    LAUNCH(launch_gemm_decode_w8(o.p, o.ld, xr.p, xr.ld, wp, sp, M, N, K, (int)mode, (int)wr, (int)kc, 1,
+                                 cur_stream()));
+  }
+}
+
+int64_t ring_slots(int64_t wr, int64_t kc, int64_t xr) { return w8::ring_slots((int)wr, (int)xr, (int)kc); }
+
+}  // namespace
+
+PYBIND11_MODULE(_C_w8, m) {
+  m.doc() = "gfx950 HIP kernel of the W8A16 (FP8 e4m3 weights) decode GEMM";
+  m.def("gemm_decode_w8", &gemm_decode_w8);
+  m.def("ring_slots", &ring_slots);
+  m.def("check_only", &check_only);
+}

@@ -1,0 +1,23 @@
+// Host launcher of the W8A16 decode GEMM (gemm_decode_w8.hip). As launchers.h: raw pointers and an explicit stream,
+// no allocation, no synchronisation.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "launchers.h"
+
+namespace die {
+
+// Y = (X · q^T) ⊙ s for M <= 32 rows. Wq: the e4m3 bytes of q [N, K] packed for the (wr, kc) tile of gd_w8.h
+// (src/ops/w8.py gd_pack_weights_w8; mode 1: with silu=True); scales: [N] fp32 in q's row order, 16-byte aligned.
+// mode 0: bf16 Y [M, N] (ldy % 4 == 0, 8-byte aligned); mode 1: bf16 Y [M, N / 2] = silu(gate) * up, q = [gate; up];
+// mode 2: fp32 slabs Y [sk, M, N] (ldy = N, 16-byte aligned), slice by of sk over the K-chunks
+// [by tch / sk, (by + 1) tch / sk). sk = 1 unless mode 2; sk <= K / kc.
+// hipErrorInvalidValue (nothing launched) for M > 32, a (wr, kc) that is no GD_W8_TILES tile, K % kc, or N (mode 1:
+// N / 2) no multiple of the tile's columns.
+hipError_t launch_gemm_decode_w8(void* Y, int64_t ldy, const bf16_t* X, int64_t ldx, const uint8_t* Wq,
+                                 const float* scales, int M, int N, int K, int mode, int wr, int kc, int sk,
+                                 hipStream_t s);
+
+}  // namespace die

@@ -7,7 +7,8 @@ kernels and the torch bindings into ``src/_C*.so`` and the host runtime
     python -m src._build --force
 
 The kernels are compiled once here with ``hipcc --offload-arch=gfx950`` and the
-``.so`` files (``_C``, ``_C_kv8``: the FP8 KV-cache kernels, and ``_runtime``) travel with the repo snapshot to the GPU box.
+``.so`` files (``_C``, ``_C_kv8``: the FP8 KV-cache kernels, ``_C_w8``: the FP8-weight decode GEMM, and ``_runtime``)
+travel with the repo snapshot to the GPU box.
 """
 
 from __future__ import annotations
@@ -41,6 +42,13 @@ PRELOAD_FLAGS = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 # to the host pass too, which does not know it and says so in a note per compile: harmless.
 KV8_KERNELS = ["attention_kv8"]
 KV8_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
+# the W8A16 decode GEMM (FP8 e4m3 weights): a third module (src/_C_w8*.so), built like the KV8 kernels (no packed
+# fp32 forms) and, as the bf16 decode GEMM, with multiply-adds fused per source expression only
+W8_KERNELS = ["gemm_decode_w8"]
+CONTRACT_ON |= set(W8_KERNELS)
+# module -> (kernels, bindings source, extra hipcc flags)
+MODULES = {"_C": (KERNELS, "bindings", []), "_C_kv8": (KV8_KERNELS, "bindings_kv8", KV8_FLAGS),
+           "_C_w8": (W8_KERNELS, "bindings_w8", KV8_FLAGS)}
 
 
 def _torch_paths():
@@ -69,10 +77,9 @@ def _headers(d: str):
 
 
 def build_kernels(force: bool = False, jobs: int = 8, verbose: bool = False, module: str = "_C") -> str:
-    """Compile one extension module: `_C` (KERNELS + bindings.cpp) or `_C_kv8` (KV8_KERNELS + bindings_kv8.cpp)."""
+    """Compile one extension module of MODULES: `_C`, `_C_kv8` or `_C_w8` (its kernels + its bindings source)."""
     os.makedirs(OBJ, exist_ok=True)
-    kv8 = module == "_C_kv8"
-    kernels, bname = (KV8_KERNELS, "bindings_kv8") if kv8 else (KERNELS, "bindings")
+    kernels, bname, extra = MODULES[module]
     out = os.path.join(ROOT, "src", module + EXT_SUFFIX)
     kdir = os.path.join(CSRC, "kernels")
     hdrs = _headers(kdir)
@@ -87,7 +94,6 @@ def build_kernels(force: bool = False, jobs: int = 8, verbose: bool = False, mod
             # the decode kernels fuse multiply-adds per source expression only (not across statements)
             contract = ["-ffp-contract=on"] if k in CONTRACT_ON else []
             preload = PRELOAD_FLAGS if k in PRELOAD_ON else []
-            extra = KV8_FLAGS if kv8 else []
             jobs_list.append([HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", *contract, *preload, *extra,
                               "-I", CSRC, "-c", src, "-o", obj])
     bsrc = os.path.join(CSRC, bname + ".cpp")
@@ -131,6 +137,7 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
     build_runtime(force)
     build_kernels(force, verbose=verbose)
     build_kernels(force, verbose=verbose, module="_C_kv8")
+    build_kernels(force, verbose=verbose, module="_C_w8")
 
 
 def main(argv=None) -> int:
@@ -143,6 +150,7 @@ def main(argv=None) -> int:
     if not a.runtime_only:
         print(build_kernels(a.force, verbose=a.verbose))
         print(build_kernels(a.force, verbose=a.verbose, module="_C_kv8"))
+        print(build_kernels(a.force, verbose=a.verbose, module="_C_w8"))
     return 0
 
 

@@ -50,6 +50,9 @@ class ModelConfig:
     # "auto": the KV pool holds bf16; "fp8": OCP e4m3 bytes (twice the blocks in the same memory; one GPU, dense
     # models, role "both": see LLMEngine)
     kv_cache_dtype: str = "auto"
+    # "auto": bf16 weights; "fp8": the layers' projections quantised to OCP e4m3 with per-row scales, decode steps of
+    # <= 32 rows stream the one-byte copies (one GPU, dense models: see LLMEngine)
+    weight_dtype: str = "auto"
     enable_prefix_caching: bool = True
     use_cuda_graph: bool = True        # hipGraph capture of decode steps
     max_latency_ms: float = 10.0
@@ -83,6 +86,7 @@ class EngineConfig:
     block_size: int = 16
     num_kv_blocks: Optional[int] = None
     kv_cache_dtype: str = "auto"       # "auto" (bf16) | "fp8" (e4m3 pool, per-layer k / v scales)
+    weight_dtype: str = "auto"         # "auto" (bf16) | "fp8" (e4m3 projections, per-row scales, W8A16 decode GEMM)
     gpu_memory_fraction: float = 0.90
     enable_prefix_caching: bool = True
     kv_block_ttl_s: Optional[float] = None  # TTL for cached (unreferenced) KV blocks

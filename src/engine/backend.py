@@ -41,6 +41,7 @@ def engine_config_from(config: ModelConfig) -> EngineConfig:
         block_size=config.kv_block_size,
         num_kv_blocks=config.num_kv_blocks,
         kv_cache_dtype=config.kv_cache_dtype,
+        weight_dtype=config.weight_dtype,
         gpu_memory_fraction=config.gpu_memory_fraction,
         enable_prefix_caching=config.enable_prefix_caching,
         kv_block_ttl_s=ov.get("kv_block_ttl_s"),
@@ -65,6 +66,10 @@ class LLMBackend:
             raise ValueError(f"kv_cache_dtype='fp8' is not available on a disaggregated {config.role} worker")
         if config.kv_cache_dtype == "fp8" and config.tp_size > 1:
             raise ValueError("kv_cache_dtype='fp8' is not available on a tensor-parallel engine")
+        if config.weight_dtype not in ("auto", "fp8"):
+            raise ValueError(f"weight_dtype must be auto / fp8, not {config.weight_dtype!r}")
+        if config.weight_dtype == "fp8" and config.tp_size > 1:
+            raise ValueError("weight_dtype='fp8' is not available on a tensor-parallel engine")
         if engine is None:
             from src.models.loader import is_hf_checkpoint
 

@@ -59,6 +59,21 @@ def check_kv_cache_dtype(cfg: EngineConfig, model: CausalLM) -> None:
         raise ValueError("kv_cache_dtype='fp8' needs head_dim 128, block_size 16 and hq / hkv in {1, 2, 4, 8}")
 
 
+def check_weight_dtype(cfg: EngineConfig, model: CausalLM) -> bool:
+    """Whether the engine serves FP8 weights (weight_dtype="fp8"); what they do not serve is refused when the
+    engine is built."""
+    mode = getattr(cfg, "weight_dtype", "auto")
+    if mode not in ("auto", "fp8"):
+        raise ValueError(f"weight_dtype must be auto / fp8, not {mode!r}")
+    if mode == "auto":
+        return False
+    if model.tp.enabled:
+        raise ValueError("weight_dtype='fp8' is not available on a tensor-parallel engine")
+    if model.arch.is_moe:
+        raise ValueError("weight_dtype='fp8' is not available on a MoE model: the W8 decode GEMM has no grouped form")
+    return True
+
+
 def plan_kv_blocks(arch: ArchConfig, model: CausalLM, cfg: EngineConfig, device: torch.device) -> int:
     if cfg.num_kv_blocks:
         return cfg.num_kv_blocks
@@ -137,7 +152,18 @@ class LLMEngine:
 
             enable_prefill_gemm_table(self.device)
         self.decode_weight_layout = "row-major"
-        if hasattr(model, "pack_decode_weights") and hasattr(model, "decode_buckets"):
+        self.weight_fp8 = check_weight_dtype(cfg, model)
+        if self.weight_fp8:
+            # quantised before anything else is packed and before the KV pool takes the free HBM: the projections
+            # become dequantised e4m3 values, decode steps of <= 32 rows stream the FP8 copies
+            if getattr(model, "weight_dtype", "auto") != "fp8":
+                model.quantize_weights_fp8()
+            self.decode_weight_layout = "fp8" if model.w8_plan is not None else "row-major"
+            logger.info("FP8 weights: %d tensors quantised (e4m3, per-row scales), %s, +%.2f GiB of FP8 copies",
+                        model.w8_stats["quantized"],
+                        "W8 decode GEMM" if model.w8_plan is not None else "no W8 tile divides the shapes: bf16 paths",
+                        model.decode_copy_bytes(()) / 2**30)
+        elif hasattr(model, "pack_decode_weights") and hasattr(model, "decode_buckets"):
             # the decode GEMMs' tile-order weight copies are made before the KV pool takes the free HBM — unless
             # the KV pool is the constraint (EngineConfig.decode_weight_layout)
             buckets = model.decode_buckets(cfg.max_num_seqs)
@@ -793,6 +819,8 @@ class LLMEngine:
         # decode weight tensors streamed in the lossless 13-bit layout / kept in tile order (outside its window)
         p13 = getattr(self.model, "p13_stats", None) or {"packed": 0, "raw": 0}
         s["p13_tensors_packed"], s["p13_tensors_raw"] = p13["packed"], p13["raw"]
+        s["weight_dtype"] = "fp8" if self.weight_fp8 else "auto"
+        s["fp8_tensors_quantized"] = (getattr(self.model, "w8_stats", None) or {"quantized": 0})["quantized"]
         s["logprob_launches"] = getattr(self.runner, "logprob_launches", 0)  # ops.token_logprobs launches
         s["logit_process_launches"] = getattr(self.runner, "logit_process_launches", 0)  # ops.logit_process
         s["token_guide_launches"] = getattr(self.runner, "token_guide_launches", 0)  # ops.token_guide

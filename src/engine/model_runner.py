@@ -18,6 +18,8 @@ from __future__ import annotations
 
 import bisect
 import collections
+import contextlib
+import gc
 import logging
 import os
 from typing import Dict, List, Optional, Sequence as Seq
@@ -35,6 +37,23 @@ from src.guided import (GUIDE_MAX_TOKEN_BYTES, Automaton, ByteGuide, FirstFit, J
 from src.models.llama import AttnMetadata, CausalLM
 
 logger = logging.getLogger(__name__)
+
+
+@contextlib.contextmanager
+def _no_gc_while_capturing():
+    """Collect dead cycles now and keep the cyclic collector off until the captures are done. torch.cuda.graph no
+    longer collects on entry, and a capture puts the device in global capture mode, where the calls that finalisers
+    of GPU objects make (freeing a dead engine's graphs, pinned buffers and events) are errors raised inside a
+    destructor: the process aborts. A collection can start at any allocation, and a decode step that allocates its
+    slabs (the slab paths) allocates often; dead engines are cycles, so only the collector frees them."""
+    gc.collect()
+    on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if on:
+            gc.enable()
 
 
 class KVPool:
@@ -1088,6 +1107,13 @@ class ModelRunner:
     def capture_graphs(self) -> None:
         if not self.is_cuda or not self.cfg.use_cuda_graph:
             return
+        # an FP8-weight model decodes on the slab sequence, which allocates its slabs in every step; every other
+        # engine captures exactly as before
+        fp8 = getattr(self.model, "weight_dtype", "auto") == "fp8"
+        with _no_gc_while_capturing() if fp8 else contextlib.nullcontext():
+            self._capture_graphs()
+
+    def _capture_graphs(self) -> None:
         sizes = sorted({min(b, self.max_seqs) for b in self.cfg.graph_batch_sizes} | {self.max_seqs})
         self._graph_pool = torch.cuda.graph_pool_handle()
         # warm up (hipBLASLt heuristics, kernel loads) outside capture

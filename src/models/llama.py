@@ -63,12 +63,14 @@ class AttnMetadata:
 
 class LayerWeights:
     # tiled: decode-GEMM tile-order copies {(projection, wr, kc): tensor} (CausalLM.pack_decode_weights)
-    __slots__ = ("ln1", "ln2", "qkv", "o", "gate_up", "down", "router", "w13", "w2", "tiled")
+    # w8: FP8 decode copies {projection: (packed e4m3 bytes, scales [N] fp32)} (CausalLM.quantize_weights_fp8)
+    __slots__ = ("ln1", "ln2", "qkv", "o", "gate_up", "down", "router", "w13", "w2", "tiled", "w8")
 
     def __init__(self):
         for s in self.__slots__:
             setattr(self, s, None)
         self.tiled = {}
+        self.w8 = {}
 
 
 # LDS staging area of the fused decode attention's prologue (csrc/kernels/attention.hip V3_MERGE)
@@ -127,6 +129,11 @@ class CausalLM:
         self.p13_weights = os.environ.get("DIE_P13", "1") != "0"
         self.p13_stats = {"packed": 0, "raw": 0}  # tensors packed / kept in tile order (outside the window)
         self.prefill_gemm_residual = True  # TP=1 prefill: o / down add into the residual in the GEMM (beta = 1)
+        # "fp8" once quantize_weights_fp8 has run: the projections hold dequantised e4m3 values and decode steps of
+        # <= 32 rows stream the FP8 copies (lw.w8) where w8_plan has a tile for every projection
+        self.weight_dtype = "auto"
+        self.w8_plan: Optional[dict] = None
+        self.w8_stats = {"quantized": 0}
         self.layers: List[LayerWeights] = []
         self._init_random(seed, init_std)
         self.cos_sin = rope_cos_sin(self.max_position, a.head_dim, a.rope_theta, self.device, a.rope_scaling)
@@ -235,6 +242,55 @@ class CausalLM:
                 lw.gate_up.mul_(lw.ln2.to(lw.gate_up.dtype)[None, :])
                 lw.ln2.fill_(1)
         self.norms_folded = True
+        if self.weight_dtype == "fp8":  # FP8 weights are quantised after the fold: the folded layers only
+            self.quantize_weights_fp8(layers)
+
+    W8_PROJECTIONS = ("qkv", "o", "gate_up", "down")
+
+    def decode_plan_w8(self) -> Optional[dict]:
+        """{projection: (wr, kc, sk)} of the W8 decode GEMM (ops.decode_tile_w8: the grid closest to 256 workgroups,
+        split-K for the slab projections qkv, o and down; W8_TILE_CFG's measured tile where one exists), or None
+        when a projection's shape has no W8 tile."""
+        lw = self.layers[0]
+        plan = {}
+        for name in self.W8_PROJECTIONS:
+            rows, k = getattr(lw, name).shape
+            silu = name == "gate_up"
+            plan[name] = ops.decode_tile_w8(rows // 2 if silu else rows, k, silu=silu, split=not silu)
+            if plan[name] is None:
+                return None
+        return plan
+
+    @torch.inference_mode()
+    def quantize_weights_fp8(self, layers: Optional[List[int]] = None) -> int:
+        """Make this an FP8-weight model: qkv, o, gate_up and down of every layer are quantised to e4m3 with one
+        power-of-two scale per output row (ops.quantize_weights_fp8; after the norm weights are folded in), the bf16
+        tensors are overwritten with the dequantised values - exactly the numbers the FP8 copies hold, so prefill,
+        steps above 32 rows and every fallback compute the same model - and the FP8 bytes are kept in the W8
+        kernel's order for the plan's tile with their scales (lw.w8). The LM head and the embeddings stay bf16. No
+        tile-order or P13 copies of these projections are made. ``layers``: only those (a streaming fold; quantising
+        quantised values again changes nothing). Returns the number of tensors quantised so far."""
+        if self.arch.is_moe or self.tp.enabled:
+            raise ValueError("weight_dtype='fp8' is not available on a MoE model or a tensor-parallel engine")
+        self.weight_dtype = "fp8"
+        self.w8_plan = self.decode_plan_w8()
+        todo = set(range(len(self.layers)) if layers is None else layers)
+        for i in sorted(todo):
+            lw = self.layers[i]
+            lw.tiled, lw.w8 = {}, {}
+            for name in self.W8_PROJECTIONS:
+                w = getattr(lw, name)
+                q, sc = ops.quantize_weights_fp8(w)
+                w.copy_(ops.dequantize_weights_fp8(q, sc).to(w.dtype))
+                if self.w8_plan is not None:
+                    wr, kc, _ = self.w8_plan[name]
+                    lw.w8[name] = (ops.gd_pack_weights_w8(q, wr, kc, silu=name == "gate_up"), sc.contiguous())
+        if layers is not None:
+            todo |= self.w8_stats.get("layers", set())
+        self.w8_stats = {"quantized": len(self.W8_PROJECTIONS) * len(todo), "layers": todo}
+        if self.device.type == "cuda":
+            torch.cuda.empty_cache()  # the packing transients, before the KV pool is sized
+        return self.w8_stats["quantized"]
 
     def pack_lm_head(self) -> bool:
         """Re-lay the LM head IN PLACE in the decode GEMM's tile order (one copy: its only consumer is the
@@ -268,7 +324,8 @@ class CausalLM:
         False while streaming several files, then call :meth:`fold_norm_weights` once)."""
         for lw in self.layers:  # decode tile-order copies go stale: re-packed by alloc_decode_scratch
             lw.tiled = {}
-        self.p13_stats = {"packed": 0, "raw": 0}
+            lw.w8 = {}  # the FP8 copies too: re-made by fold_norm_weights
+        self.p13_stats, self.w8_stats = {"packed": 0, "raw": 0}, {"quantized": 0}
         if self.lm_head_tile is not None:  # back to row-major for the checkpoint's rows (re-packed likewise)
             self.lm_head.copy_(self.lm_head_rows())
             self.lm_head_tile = None
@@ -362,6 +419,7 @@ class CausalLM:
         m.__dict__.update({k: v for k, v in self.__dict__.items()
                            if k not in ("layers", "embed", "norm", "lm_head", "cos_sin")})
         m.device, m.dtype = torch.device(device), dtype
+        m.weight_dtype, m.w8_plan = "auto", None  # the (dequantised) values are carried over, not the FP8 copies
 
         def conv(t):
             return None if t is None else t.detach().to(device=device, dtype=dtype)
@@ -384,7 +442,12 @@ class CausalLM:
                 t = getattr(lw, s)
                 if isinstance(t, torch.Tensor):
                     tot += t.numel()
-        return tot * self.embed.element_size()
+        return tot * self.embed.element_size() + self._w8_bytes()
+
+    def _w8_bytes(self) -> int:
+        """HBM of the FP8 decode copies and their scales."""
+        return sum(q.numel() * q.element_size() + sc.numel() * sc.element_size()
+                   for lw in self.layers for q, sc in lw.w8.values())
 
     # --------------------------------------------------------------- forward
     def forward(self, input_ids: torch.Tensor, positions: torch.Tensor, meta: AttnMetadata,
@@ -392,7 +455,8 @@ class CausalLM:
         """Returns the final-norm hidden states [T, H]. ``kv_pool`` is
         [layers, 2, num_blocks, hkv, block_size, head_dim]."""
         eps = self.arch.rms_eps
-        if (self._slab_path(input_ids) and meta.scratch is not None and not meta.is_prefill
+        if (not self._w8_path(input_ids, meta) and self._slab_path(input_ids) and meta.scratch is not None
+                and not meta.is_prefill
                 and self._fused_decode_ok(kv_pool, input_ids.shape[0])):
             if meta.pre_embedded and "h_in" in meta.scratch:
                 residual, ssp0 = meta.scratch["h_in"][: input_ids.shape[0]], meta.scratch["ssp0"]
@@ -400,6 +464,8 @@ class CausalLM:
                 residual, ssp0 = ops.embed_sumsq(input_ids, self.embed, meta.scratch["ssp0"])
             return self._forward_decode_fused(residual, positions, meta, kv_pool, ssp0=ssp0)
         residual = F.embedding(input_ids, self.embed)
+        if self._w8_path(input_ids, meta):
+            return self._forward_decode_slab_w8(residual, positions, meta, kv_pool)
         if self._slab_path(input_ids):
             if not self.tp.enabled and not self.arch.is_moe:  # the slab fallback is dense-only
                 return self._forward_decode_slab(residual, positions, meta, kv_pool)
@@ -594,6 +660,34 @@ class CausalLM:
             slab = ops.linear_slab(ops.linear_silu_mul(x, lw.gate_up), lw.down)
         return ops.fused_add_rms_norm_slab(slab, residual, self.norm, eps)
 
+    def _w8_path(self, input_ids: torch.Tensor, meta: AttnMetadata) -> bool:
+        """Decode steps of <= 32 rows of an FP8-weight model stream the FP8 copies (the slab sequence on the W8
+        GEMM); everything else runs the bf16 paths on the dequantised weights."""
+        return (self.weight_dtype == "fp8" and self.w8_plan is not None and not meta.is_prefill
+                and input_ids.shape[0] <= ops.W8_MAX_M and bool(self.layers[0].w8) and self._slab_path(input_ids))
+
+    def _forward_decode_slab_w8(self, residual, positions, meta: AttnMetadata, kv_pool):
+        """:meth:`_forward_decode_slab`'s sequence with the W8 GEMM in place of linear_slab / linear_silu_mul: four
+        FP8 weight streams per layer, the slab consumers unchanged (a one-byte KV pool included)."""
+        eps, d = self.arch.rms_eps, self.head_dim
+        hq, hkv, plan = self.hq, self.hkv, self.w8_plan
+        x = ops.rms_norm(residual, self.layers[0].ln1, eps)
+        slab = None
+        for li, lw in enumerate(self.layers):
+            if li > 0:
+                x = ops.fused_add_rms_norm_slab(slab, residual, lw.ln1, eps)
+            k_cache, v_cache = kv_pool[li, 0], kv_pool[li, 1]
+            q = ops.rope_and_cache_slab(ops.linear_slab_w8(x, *lw.w8["qkv"], *plan["qkv"]), positions, self.cos_sin,
+                                        meta.slot_mapping, k_cache, v_cache, hq, hkv, d,
+                                        kv_scales=self.kv_scales[li])
+            attn = ops.attn_decode(q, k_cache, v_cache, meta.block_tables, meta.ctx_lens, meta.max_ctx, hq, hkv,
+                                   self.scale, part_o=meta.part_o, part_ml=meta.part_ml, counters=meta.attn_cnt,
+                                   kv_once=meta.kv_once, kv_scales=self.kv_scales[li])
+            x = ops.fused_add_rms_norm_slab(ops.linear_slab_w8(attn, *lw.w8["o"], *plan["o"]), residual, lw.ln2, eps)
+            act = ops.linear_silu_mul_w8(x, *lw.w8["gate_up"], *plan["gate_up"][:2])
+            slab = ops.linear_slab_w8(act, *lw.w8["down"], *plan["down"])
+        return ops.fused_add_rms_norm_slab(slab, residual, self.norm, eps)
+
     # ----------------------------------------- fused decode path (norms folded, M <= 128)
     decode_bucket = staticmethod(ops.decode_bucket)
 
@@ -737,6 +831,8 @@ class CausalLM:
         weights (4 % slower bench, profiles/r5_decode_weight_layout_ab.txt)."""
         if not self.tiled_decode_weights or self.arch.is_moe or not self.norms_folded:
             return False
+        if self.weight_dtype == "fp8":  # decode streams the FP8 copies; larger steps read the row-major weights
+            return False
         if not (self.device.type == "cuda" and ops.native_available()):
             return False
         need, extra = self._decode_copy_plan(buckets)
@@ -791,7 +887,10 @@ class CausalLM:
         return need, extra
 
     def decode_copy_bytes(self, buckets) -> int:
-        """HBM the tile-order decode weight copies would take (0 where none are made)."""
+        """HBM the decode weight copies take: the tile-order copies (0 where none are made), or an FP8-weight
+        model's e4m3 copies and scales."""
+        if self.weight_dtype == "fp8":
+            return self._w8_bytes()
         if not self.tiled_decode_weights or self.arch.is_moe or not self.norms_folded:
             return 0
         return self._decode_copy_plan(buckets)[1]

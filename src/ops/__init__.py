@@ -20,6 +20,9 @@ from .decode_tiles import (DECODE_GEMM_MAX_M, DECODE_TILE_CFG, HALF_RING, MODE_B
                            gd_tile, gd_tile_valid, moe_decode_tiles)
 # the lossless 13-bit weight layout of the (128, 128) tile: packer and exact inverse (pure torch)
 from .p13 import P13_DEN, P13_NUM, P13_TILE, gd_pack_weights_p13, gd_unpack_weights_p13, p13_base7
+# FP8 (e4m3) weights of the W8A16 decode GEMM: tiles, packer, tile choice, quantiser (pure torch)
+from .w8 import (W8_BF16, W8_MAX_M, W8_SILU, W8_SLAB, W8_TILES, decode_tile_w8, dequantize_weights_fp8,
+                 gd_pack_weights_w8, gd_unpack_weights_w8, quantize_weights_fp8, ring_slots_w8, w8_tile_valid)
 
 _C = None
 _C_ERR: Optional[BaseException] = None
@@ -38,8 +41,25 @@ except Exception as e:  # pragma: no cover - depends on build state
     _C_KV8_ERR = e
 
 
+# the W8A16 decode GEMM (FP8 weights) likewise (csrc/bindings_w8.cpp)
+_C_w8 = None
+_C_W8_ERR: Optional[BaseException] = None
+try:
+    from src import _C_w8  # type: ignore  # noqa: F811
+except Exception as e:  # pragma: no cover - depends on build state
+    _C_W8_ERR = e
+
+
 def native_available() -> bool:
     return _C is not None
+
+
+def _kern_w8():
+    if _C_w8 is None:
+        raise RuntimeError(
+            "HIP kernel extension src/_C_w8 (FP8 weights) is not built or failed to load "
+            f"({_C_W8_ERR!r}); run `python -m src._build` (hipcc --offload-arch=gfx950)")
+    return _C_w8
 
 
 def _kern_kv8():
@@ -882,6 +902,38 @@ def linear_silu_mul(x: torch.Tensor, w_gate_up: torch.Tensor) -> torch.Tensor:
         wr, kc, _ = decode_tile(w_gate_up.shape[0] // 2, x.shape[1], MODE_SILU, decode_bucket(x.shape[0]))
         return gemm_decode(x, w_gate_up, MODE_SILU, wr, 1, kc=kc)
     return silu_and_mul(torch.nn.functional.linear(x, w_gate_up))
+
+
+def gemm_decode_w8(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor, mode: int, wr: int, kc: int, sk: int = 1,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Raw access to the W8A16 decode GEMM (csrc/kernels/gemm_decode_w8.hip): (x @ q^T) * scales for x [M <= 32, K]
+    bf16, ``wq`` the e4m3 bytes of q [N, K] packed by gd_pack_weights_w8 for the (wr, kc) tile (W8_SILU: with
+    silu=True) and ``scales`` [N] fp32. ``mode``: W8_BF16 (bf16 [M, N]), W8_SILU (bf16 silu(gate) * up [M, N / 2],
+    q = [gate; up]) or W8_SLAB (fp32 split-K slabs [sk, M, N]). A missing kernel or a refused shape raises."""
+    m, n = x.shape[0], wq.shape[0]
+    if out is None:
+        if mode == W8_SLAB:
+            out = torch.empty(sk, m, n, dtype=torch.float32, device=x.device)
+        else:
+            out = torch.empty(m, n // 2 if mode == W8_SILU else n, dtype=x.dtype, device=x.device)
+    _kern_w8().gemm_decode_w8(out, x, wq, scales, mode, wr, kc, sk)
+    return out
+
+
+def linear_w8(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor, wr: int, kc: int) -> torch.Tensor:
+    """bf16 (x @ q^T) * scales on FP8 weights packed for (wr, kc) (decode sizes, <= 32 rows)."""
+    return gemm_decode_w8(x, wq, scales, W8_BF16, wr, kc)
+
+
+def linear_silu_mul_w8(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor, wr: int, kc: int) -> torch.Tensor:
+    """bf16 silu(g) * u with (g, u) = (x @ q^T) * scales, q = [gate; up] packed with silu=True for (wr, kc)."""
+    return gemm_decode_w8(x, wq, scales, W8_SILU, wr, kc)
+
+
+def linear_slab_w8(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor, wr: int, kc: int,
+                   sk: int = 1) -> torch.Tensor:
+    """fp32 split-K slabs [sk, M, N] of (x @ q^T) * scales; the consumers of :func:`linear_slab` reduce them."""
+    return gemm_decode_w8(x, wq, scales, W8_SLAB, wr, kc, sk)
 
 
 def fused_add_rms_norm_slab(slab: torch.Tensor, residual: torch.Tensor, w: torch.Tensor, eps: float,

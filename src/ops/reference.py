@@ -160,6 +160,45 @@ def attention_kv8(q, k_cache, v_cache, block_tables, cu_q, ctx_lens, hq, hkv, sc
                      ctx_lens, hq, hkv, scale)
 
 
+# ---- FP8 (OCP e4m3) weights: W[n, k] = q[n, k] * s[n], q e4m3fn, s one fp32 power of two per output row
+W8_MIN_EXP = -124   # smallest scale exponent: q's grid is 2^-9, so q * s stays on bf16's grid (2^-133) and is exact
+
+
+def quantize_weights_fp8(w: torch.Tensor):
+    """(q [N, K] float8_e4m3fn, s [N] fp32) of a [N, K] weight: per row the smallest power of two s = 2^j with
+    amax / s <= 448 (1.0 for an all-zero row; j >= W8_MIN_EXP), q = e4m3(w / s) nearest-even and saturating as
+    :func:`quantize_kv8`. The division is exact, so q never saturates in fact and holds no 0x7f / 0xff byte, and
+    bf16(q * s) is exact: :func:`dequantize_weights_fp8` to bf16 gives exactly the numbers the FP8 copy holds."""
+    wf = w.float()
+    m, e = torch.frexp(wf.abs().amax(dim=1))             # amax = m 2^e, m in [0.5, 1); 448 = 0.875 * 2^9
+    j = (e - 9 + (m > 0.875).to(e.dtype)).clamp_min(W8_MIN_EXP)
+    s = torch.where(m > 0, torch.ldexp(torch.ones_like(m), j), torch.ones_like(m))
+    return quantize_kv8(wf / s[:, None], 1.0), s
+
+
+def dequantize_weights_fp8(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """fp32 q * s of e4m3 bytes (uint8 or float8_e4m3fn storage) and per-row scales."""
+    return q.view(torch.float8_e4m3fn).float() * s.float()[:, None]
+
+
+def linear_w8(x: torch.Tensor, q: torch.Tensor, s: torch.Tensor, mode: str = "bf16", sk: int = 1, kc: int = 256):
+    """The W8A16 decode GEMM's semantics in fp32: (x @ q^T) * s, then ``mode``: "bf16" the bf16 result; "silu" bf16
+    silu(g) * u with q = [gate; up]; "slab" the fp32 split-K partials [sk, M, N] (slice by takes the K-chunks
+    [by * tch // sk, (by + 1) * tch // sk) of kc columns), each scaled."""
+    xf, qf, sf = x.float(), q.view(torch.float8_e4m3fn).float(), s.float()
+    if mode == "slab":
+        tch = x.shape[1] // kc
+        cuts = [(by * tch // sk) * kc for by in range(sk + 1)]
+        return torch.stack([(xf[:, lo:hi] @ qf[:, lo:hi].T) * sf for lo, hi in zip(cuts, cuts[1:])])
+    y = (xf @ qf.T) * sf
+    if mode == "silu":
+        n = y.shape[1] // 2
+        return (torch.nn.functional.silu(y[:, :n]) * y[:, n:]).to(x.dtype)
+    if mode != "bf16":
+        raise ValueError(f"linear_w8: mode must be bf16 / silu / slab, not {mode!r}")
+    return y.to(x.dtype)
+
+
 def sample(logits, temperature=None, top_k=None, top_p=None, seeds=None, steps=None):
     """Greedy where temperature==0; otherwise a (non-bit-exact) torch sampler
     with the same filtering semantics (top-k, then top-p on the renormalised set)."""

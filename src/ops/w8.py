@@ -1,0 +1,151 @@
+"""
+"W8": FP8 (OCP e4m3fn) weights for the W8A16 decode GEMM (csrc/kernels/gemm_decode_w8.hip). A quantised
+projection is ``W[n, k] = q[n, k] * s[n]``: q one e4m3 byte, s one fp32 scale per output row. This module has the
+kernel's tiles and their geometry (a mirror of csrc/kernels/gd_w8.h, compared with it by tests/test_w8_cpu.py), the
+packer into the kernel's fragment order with its exact inverse, and the tile choice. The quantiser and the CPU
+semantics are in :mod:`src.ops.reference`. Pure torch.
+"""
+
+from __future__ import annotations
+
+import math
+from typing import Optional, Tuple
+
+import torch
+
+from .reference import dequantize_weights_fp8, quantize_weights_fp8  # noqa: F401  (re-exported)
+
+# the decode GEMM's W8 modes (_C_w8.gemm_decode_w8)
+W8_BF16, W8_SILU, W8_SLAB = 0, 1, 2
+# The instantiated (wr, kc) tiles, in the order of gd_w8.h's GD_W8_TILES: weight rows per workgroup and K columns
+# per LDS ring slot.
+W8_TILES = ((32, 256), (64, 256), (128, 256))
+W8_MAX_M = 32            # activation images of 16 and 32 rows
+W8_IMAGES = (16, 32)
+RING_BYTES = 147456      # LDS for the ring (144 KiB)
+MAX_SLOTS = 8
+
+
+def w8_image(m: int) -> int:
+    """The activation image of a launch of m rows."""
+    return 16 if m <= 16 else 32
+
+
+def slot_bytes(wr: int, kc: int, xr: int) -> int:
+    """A ring slot: the chunk's wr x kc weight bytes, then the bf16 activation image."""
+    return wr * kc + xr * kc * 2
+
+
+def ring_slots_w8(wr: int, kc: int, xr: int) -> int:
+    """LDS ring depth: the deepest that fits RING_BYTES, MAX_SLOTS and the 6-bit vmcnt."""
+    per_wave = slot_bytes(wr, kc, xr) // 1024 // 4
+    s = min(MAX_SLOTS, RING_BYTES // slot_bytes(wr, kc, xr))
+    while s > 2 and (s - 1) * per_wave > 63:
+        s -= 1
+    return s
+
+
+def lds_bytes_w8(wr: int, kc: int, xr: int) -> int:
+    """LDS bytes of one launch: the ring; the fp32 partials [4, 32, wr] reuse it after the loop."""
+    return max(ring_slots_w8(wr, kc, xr) * slot_bytes(wr, kc, xr), 4 * 32 * wr * 4)
+
+
+def w8_tile_valid(wr: int, kc: int, xr: int) -> bool:
+    """A (wr, kc) tile has an xr-row form (mirror of gd_w8.h valid)."""
+    return (wr % 32 == 0 and kc % 128 == 0 and xr in W8_IMAGES and (wr * kc // 1024) % 4 == 0
+            and (xr * kc * 2 // 1024) % 4 == 0 and ring_slots_w8(wr, kc, xr) >= 2
+            and lds_bytes_w8(wr, kc, xr) <= RING_BYTES)
+
+
+def w8_byte_off(wr: int, kc: int, r: torch.Tensor, k: torch.Tensor) -> torch.Tensor:
+    """Byte offset in its chunk of the weight at image row r, chunk column k (gd_w8.h byte_off): wave k // (kc / 4),
+    k-step of 32, tile pair, lane (k group of 8, row in the 16-row tile), tile of the pair, byte."""
+    w, step, kg, nt = k // (kc // 4), (k % (kc // 4)) // 32, (k % 32) // 8, r // 16
+    group = (w * (kc // 128) + step) * (wr // 32) + nt // 2
+    return (group * 64 + kg * 16 + r % 16) * 16 + (nt & 1) * 8 + k % 8
+
+
+def _tile_rows(rows: int, wr: int, silu: bool, device) -> torch.Tensor:
+    """Weight row of every (tile, image row): a tile is wr rows, or wr / 2 gate rows then the matching up rows."""
+    no = wr // 2 if silu else wr
+    n_out = rows // 2 if silu else rows
+    t = torch.arange(n_out // no, device=device).view(-1, 1) * no
+    j = torch.arange(no, device=device).view(1, no)
+    return (torch.cat([t + j, n_out + t + j], 1) if silu else t + j).reshape(-1)
+
+
+def _chunk_index(wr: int, kc: int, device) -> torch.Tensor:
+    """[wr * kc] position in the packed chunk of element (r, k) of the row-major chunk."""
+    r = torch.arange(wr, device=device).view(wr, 1)
+    k = torch.arange(kc, device=device).view(1, kc)
+    return w8_byte_off(wr, kc, r, k).reshape(-1)
+
+
+def gd_pack_weights_w8(q: torch.Tensor, wr: int, kc: int = 256, silu: bool = False) -> torch.Tensor:
+    """Re-lay the e4m3 bytes q [rows, K] (uint8 or float8_e4m3fn) in the W8 kernel's order: column tile, then
+    K-chunk, then the chunk's wr x kc bytes in fragment order (gd_w8.h), so that every 1-KiB LDS-DMA piece is one
+    linear read. silu: q = [gate; up] and a tile holds wr / 2 gate rows then the matching up rows. The result is a
+    uint8 tensor of q's shape; the scales stay a separate [rows] tensor in q's row order."""
+    assert (wr, kc) in W8_TILES and q.dim() == 2 and q.element_size() == 1
+    rows, k = q.shape
+    no = wr // 2 if silu else wr
+    assert (rows // 2 if silu else rows) % no == 0 and k % kc == 0 and (not silu or rows % 2 == 0)
+    nt, nch = rows // wr, k // kc
+    b = q.contiguous().view(torch.uint8)[_tile_rows(rows, wr, silu, q.device)]
+    b = b.view(nt, wr, nch, kc).permute(0, 2, 1, 3).reshape(nt, nch, wr * kc)
+    out = torch.empty_like(b)
+    out[:, :, _chunk_index(wr, kc, q.device)] = b
+    return out.view(rows, k)
+
+
+def gd_unpack_weights_w8(packed: torch.Tensor, wr: int, kc: int = 256, silu: bool = False) -> torch.Tensor:
+    """Exact inverse of :func:`gd_pack_weights_w8`: the row-major [rows, K] bytes (uint8)."""
+    assert (wr, kc) in W8_TILES and packed.dtype == torch.uint8
+    rows, k = packed.shape
+    nt, nch = rows // wr, k // kc
+    b = packed.contiguous().view(nt, nch, wr * kc)[:, :, _chunk_index(wr, kc, packed.device)]
+    b = b.view(nt, nch, wr, kc).permute(0, 2, 1, 3).reshape(rows, k)
+    q = torch.empty_like(b)
+    q[_tile_rows(rows, wr, silu, packed.device)] = b
+    return q
+
+
+# (N, K, silu) -> (wr, kc, sk): the measured W8 tiles (MI355X, 32 rows, cold weights: bench/micro_gemm_decode.py 32
+# --w8, profiles/w8_micro_and_engine.jsonl; us, against the bf16 kernel's tuned tile). Thin evidence: ONE sweep of
+# every tile x split in one session on one card, the best of three replays each, never repeated; entries within a
+# few per cent of their runner-up may flip on another day. A second sweep should confirm the table before anyone
+# tunes on top of it; the 70B rows serve no engine yet (a tensor-parallel FP8 engine is refused).
+W8_TILE_CFG = {
+    (6144, 4096, False): (128, 256, 4),    # Llama-3-8B qkv      10.96 vs bf16 11.28 (the rule's (32, 256, 1): 16.17)
+    (4096, 4096, False): (64, 256, 4),     # 8B o                 7.78 vs 9.00
+    (14336, 4096, True): (128, 256, 1),    # 8B gate/up + SiLU   35.24 vs 46.61
+    (4096, 14336, False): (128, 256, 8),   # 8B down             18.31 vs 22.24
+    (1280, 8192, False): (64, 256, 8),     # 70B TP=8 qkv         6.96 vs 7.75
+    (8192, 1024, False): (64, 256, 2),     # 70B TP=8 o           5.10 vs 6.26
+    (3584, 8192, True): (32, 256, 1),      # 70B TP=8 gate/up    31.44 vs 26.35: loses
+    (8192, 3584, False): (64, 256, 2),     # 70B TP=8 down       11.47 vs 13.29
+}
+
+
+def decode_tile_w8(n: int, k: int, silu: bool = False, split: bool = False,
+                   max_sk: int = 8) -> Optional[Tuple[int, int, int]]:
+    """(wr, kc, sk) of the W8 decode GEMM for an [n, k] projection (silu: n (gate, up) pairs; split: the slab mode,
+    split-K allowed): W8_TILE_CFG's measured entry, else the tile of W8_TILES x sk in (1, 2, 4, 8) that divides the
+    shape and brings the grid closest (in log2) to 256 workgroups, one per CU; the wider tile wins a tie (the
+    activation image is re-read once per column tile: at wr = 32 it is twice the weight bytes). None when no tile
+    divides. The rule is not a measurement: on the shapes of the table it chose tiles up to 50 % slower than the best."""
+    c = W8_TILE_CFG.get((n, k, silu))
+    if c is not None and (split or c[2] == 1) and c[2] <= max_sk:
+        return c
+    best, score = None, 1e9
+    for wr, kc in reversed(W8_TILES):
+        cols = wr // 2 if silu else wr
+        if n % cols or k % kc:
+            continue
+        for sk in ((1, 2, 4, 8) if split else (1,)):
+            if sk > max_sk or sk > k // kc:
+                continue
+            sc = abs(math.log2((n // cols) * sk / 256.0))
+            if sc < score - 1e-9:
+                best, score = (wr, kc, sk), sc
+    return best

@@ -414,6 +414,9 @@ def build_arg_parser():
     p.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto",
                    help="fp8: the KV pool holds e4m3 bytes, twice the blocks in the same memory (one GPU, dense "
                         "models, role both)")
+    p.add_argument("--weight-dtype", choices=["auto", "fp8"], default="auto",
+                   help="fp8: the layers' projections are quantised to e4m3 with per-row scales and decode steps "
+                        "stream the one-byte weights (one GPU, dense models)")
     p.add_argument("--kv-capacity-priority", action="store_true",
                    help="the KV pool is the constraint: decode weights in one layout (EngineConfig)")
     p.add_argument("--preproc-processes", type=int, default=0,
@@ -442,6 +445,7 @@ async def main(argv=None) -> None:
         max_batch_size=args.max_batch_size, arch=args.arch, preset=args.preset, tp_size=args.tp_size,
         role=args.role, max_model_len=args.max_model_len, max_latency_ms=args.max_latency_ms,
         use_cuda_graph=not args.no_graph, num_kv_blocks=args.num_kv_blocks, kv_cache_dtype=args.kv_cache_dtype,
+        weight_dtype=args.weight_dtype,
         overrides=overrides,
         preproc_processes=args.preproc_processes,
     )
