@@ -61,7 +61,7 @@ def main():
     if len(sys.argv) > 2 and sys.argv[2] == "deep":
         return main_deep(m)
     if len(sys.argv) > 2 and sys.argv[2] == "moe":
-        return main_moe(m)
+        return main_moe_w8(m) if "--w8" in sys.argv[3:] else main_moe(m)
     if len(sys.argv) > 2 and sys.argv[2] == "chain":
         return main_chain(m)
     if "--w8" in sys.argv[2:]:
@@ -262,6 +262,70 @@ def main_moe(m):
         wbytes = ws[0].numel() * 2
         print(json.dumps({"shape": nm, "M": m, "rows_per_expert": (offsets[1:] - offsets[:-1]).tolist(),
                           "xr16": xr16, "us": round(us, 2), "GBps": round(wbytes / us / 1e3, 1)}), flush=True)
+
+
+def main_moe_w8(m, reps=5, seed=0):
+    """`M moe --w8`: Mixtral-8x7B's grouped expert GEMMs at m tokens (top-2 of 8, routing drawn from `seed`), the
+    grouped W8 launch (ops.gemm_decode_w8_grouped, every W8 tile) against the grouped bf16 launch at its tuned tile.
+    Cold weights: two copies of each stacked tensor are cycled (>= 0.9 GiB each, beyond the Infinity Cache). All
+    variants of a shape are captured first and then replayed in turn, `reps` rounds: the line of a variant carries the
+    best, the median and the worst round. W8 bytes are random codes (no NaN): the time does not depend on the layout,
+    so one pair of copies serves the three tiles. gate/up gathers its rows from the token order in both kernels."""
+    dev = torch.device("cuda:0")
+    g = torch.Generator(device=dev).manual_seed(seed)
+    e, h, inter, k = 8, 4096, 14336, 2
+    ids = torch.stack([torch.randperm(e, device=dev, generator=g)[:k] for _ in range(m)]).to(torch.int32)
+    offsets, sorted_idx, pos = ops.moe_align(ids, e)
+    x = torch.randn(m, h, device=dev, dtype=torch.bfloat16)
+    a = torch.randn(k * m, inter, device=dev, dtype=torch.bfloat16)
+    out13 = torch.empty(k * m, inter, device=dev, dtype=torch.bfloat16)
+    ys = torch.empty(k * m, h, device=dev, dtype=torch.bfloat16)
+    kern, none = ops._kern(), torch.empty(0, dtype=torch.int32, device=dev)
+    t1, t2 = ops.moe_decode_tiles(h, inter, m)
+    for nm, rows, kk, silu in (("moe_w13", 2 * inter, h, True), ("moe_w2", h, inter, False)):
+        ws = [torch.randn(e, rows, kk, device=dev, dtype=torch.bfloat16) / 64 for _ in range(2)]
+        qs = [torch.randint(0, 0x78, (e, rows, kk), device=dev, dtype=torch.uint8) for _ in range(2)]
+        sc = torch.full((e, rows), 2.0 ** -8, device=dev)
+        if silu:
+            variants = [("bf16", t1, ws, lambda w: kern.gemm_decode_grouped(out13, x, w, offsets, MODE_SILU, *t1,
+                                                                            sorted_idx, k, m, 1))]
+            variants += [("w8", t, qs, lambda q, t=t: ops.gemm_decode_w8_grouped(x, q, sc, offsets, ops.W8_SILU, *t,
+                                                                                 rows=sorted_idx, k=k, max_rows=m,
+                                                                                 out=out13)) for t in ops.W8_TILES]
+        else:
+            variants = [("bf16", t2, ws, lambda w: kern.gemm_decode_grouped(ys, a, w, offsets, MODE_BF16, *t2, none, 1,
+                                                                            m, 1))]
+            variants += [("w8", t, qs, lambda q, t=t: ops.gemm_decode_w8_grouped(a, q, sc, offsets, ops.W8_BF16, *t,
+                                                                                 max_rows=m, out=ys))
+                         for t in ops.W8_TILES]
+        graphs, iters = [], 8
+        for _, _, bufs, fn in variants:
+            for i in range(3):
+                fn(bufs[i % 2])
+            torch.cuda.synchronize()
+            gr = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(gr):
+                for i in range(iters):
+                    fn(bufs[i % 2])
+            graphs.append(gr)
+        torch.cuda.synchronize()
+        times = [[] for _ in variants]
+        s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        for _ in range(reps):
+            for i, gr in enumerate(graphs):
+                s0.record()
+                gr.replay()
+                s1.record()
+                torch.cuda.synchronize()
+                times[i].append(s0.elapsed_time(s1) * 1e3 / iters)
+        for (kernel, t, bufs, _), ts in zip(variants, times):
+            ts = sorted(ts)
+            wbytes = bufs[0].numel() * bufs[0].element_size()
+            print(json.dumps({"bench": "w8_moe_micro", "shape": nm, "M": m, "seed": seed, "kernel": kernel, "wr": t[0],
+                              "kc": t[1], "rows_per_expert": (offsets[1:] - offsets[:-1]).tolist(),
+                              "us_best": round(ts[0], 2), "us_median": round(ts[len(ts) // 2], 2),
+                              "us_worst": round(ts[-1], 2), "weight_GBps": round(wbytes / ts[0] / 1e3, 1)}), flush=True)
+        del ws, qs, graphs
 
 
 def main_chain(m):

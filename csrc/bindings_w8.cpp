@@ -1,4 +1,5 @@
-// Torch bindings of the W8A16 decode GEMM (module `src._C_w8`, csrc/kernels/gemm_decode_w8.hip). A third module next
+// Torch bindings of the W8A16 decode GEMM and its grouped (MoE) form (module `src._C_w8`,
+// csrc/kernels/gemm_decode_w8.hip and gemm_decode_w8_grouped.hip). A third module next
 // to `_C` and `_C_kv8` with the same rules (bindings.cpp): every argument is validated through the vocabulary of
 // arg_check.h before anything is launched on the current stream, and no tensor is asked for its address here.
 #include <torch/extension.h>
@@ -59,13 +60,51 @@ void gemm_decode_w8(Tensor out, Tensor x, Tensor wq, Tensor scales, int64_t mode
   }
 }
 
+// The grouped (MoE) form: y [R, N] (mode 1: [R, N / 2]) bf16, group e = rows [offsets[e], offsets[e + 1]) of y, at most
+// max_rows (<= 32) of them; wq [E, N, K] e4m3 bytes, each expert packed by gd_pack_weights_w8 for (wr, kc) (mode 1:
+// silu=True); scales [E, N] fp32. rows (int32 [R], numel 0 = no gather): x is [T, K] in token order with T k == R and
+// the group's row j is x[rows[offsets[e] + j] / k]; without it x is [R, K] in the sorted order.
+void gemm_decode_w8_grouped(Tensor y, Tensor x, Tensor wq, Tensor scales, Tensor offsets, int64_t mode, int64_t wr,
+                            int64_t kc, Tensor rows, int64_t k, int64_t max_rows) {
+  const Op a("gemm_decode_w8_grouped", x, "x");
+  const auto xr = a.rows(x, "x");
+  const int T = a.i32(x.size(0)), K = a.i32(x.size(1));
+  TORCH_CHECK(mode == 0 || mode == 1, "gemm_decode_w8_grouped: mode 0 (bf16) or 1 (SiLU), got ", mode);
+  TORCH_CHECK(tile_exists(wr, kc), "gemm_decode_w8_grouped: no W8 tile (", wr, ", ", kc, ")");
+  TORCH_CHECK(max_rows >= 1 && max_rows <= w8::MAX_M, "gemm_decode_w8_grouped: 1 <= max_rows <= ", w8::MAX_M, ", got ",
+              max_rows);
+  TORCH_CHECK(wq.scalar_type() == at::kByte || wq.scalar_type() == at::kFloat8_e4m3fn,
+              "gemm_decode_w8_grouped: wq must be uint8 or float8_e4m3fn, got ", wq.scalar_type());
+  const uint8_t* wp = static_cast<const uint8_t*>(a.dense<void>(wq, "wq", 0, {chk::ge(1), chk::ge(1), K}, 16));
+  const int E = a.i32(wq.size(0)), N = a.i32(wq.size(1));
+  TORCH_CHECK(E <= 65535, "gemm_decode_w8_grouped: at most 65535 groups");
+  TORCH_CHECK(mode != 1 || N % 2 == 0, "gemm_decode_w8_grouped: the SiLU form takes [gate; up], an even row count");
+  const int64_t n_out = mode == 1 ? N / 2 : N, cols = mode == 1 ? wr / 2 : wr;
+  TORCH_CHECK(K >= kc && K % kc == 0, "gemm_decode_w8_grouped: K = ", K, " must be a multiple of kc = ", kc);
+  TORCH_CHECK(n_out % cols == 0, "gemm_decode_w8_grouped: ", n_out, " output columns are no multiple of the tile's ",
+              cols);
+  const float* sp = a.dense<float>(scales, "scales", (int64_t)E * N, {E, N}, 16);
+  const int* op = a.dense<int>(offsets, "offsets", E + 1, {E + 1});
+  const auto yr = a.rows(y, "y", chk::ge(1), n_out);
+  const int R = a.i32(y.size(0));
+  const int* rp = a.dense_opt<int>(rows, "rows", R, {R});
+  if (rp) {
+    TORCH_CHECK(k >= 1 && (int64_t)T * k == R, "gemm_decode_w8_grouped: a gather takes rows [T k] and y [T k, N]");
+  } else {
+    TORCH_CHECK(T == R, "gemm_decode_w8_grouped: without rows, x and y have the same rows");
+  }
+  LAUNCH(launch_gemm_decode_w8_grouped(yr.p, yr.ld, xr.p, xr.ld, wp, sp, op, rp, rp ? (int)k : 1, E, T, R, N, K,
+                                       (int)mode, (int)wr, (int)kc, (int)max_rows, cur_stream()));
+}
+
 int64_t ring_slots(int64_t wr, int64_t kc, int64_t xr) { return w8::ring_slots((int)wr, (int)xr, (int)kc); }
 
 }  // namespace
 
 PYBIND11_MODULE(_C_w8, m) {
-  m.doc() = "gfx950 HIP kernel of the W8A16 (FP8 e4m3 weights) decode GEMM";
+  m.doc() = "gfx950 HIP kernels of the W8A16 (FP8 e4m3 weights) decode GEMM, dense and grouped";
   m.def("gemm_decode_w8", &gemm_decode_w8);
+  m.def("gemm_decode_w8_grouped", &gemm_decode_w8_grouped);
   m.def("ring_slots", &ring_slots);
   m.def("check_only", &check_only);
 }

@@ -20,4 +20,16 @@ hipError_t launch_gemm_decode_w8(void* Y, int64_t ldy, const bf16_t* X, int64_t 
                                  const float* scales, int M, int N, int K, int mode, int wr, int kc, int sk,
                                  hipStream_t s);
 
+// The grouped (MoE) form (gemm_decode_w8_grouped.hip): Y[off[e] : off[e + 1]] = (Xrows · q[e]^T) ⊙ s[e] for the E
+// groups of offsets [E + 1] (int32, ascending, at most max_rows <= 32 rows each; an empty group reads nothing).
+// Wq: [E, N, K] e4m3 bytes, every expert's [N, K] packed for (wr, kc) as above; scales: [E, N] fp32. Y: bf16 [R, N]
+// (mode 0) or [R, N / 2] = silu(gate) * up (mode 1). rows null: X is [R, K], image row j of group e is
+// X[off[e] + j]; rows [R] int32: X is [T, K] in token order and the row is X[rows[off[e] + j] / k]. The kernel chooses
+// the 16- or 32-row image per group; indices read from offsets / rows are clamped to [0, R] / [0, T).
+// hipErrorInvalidValue (nothing launched) for max_rows outside [1, 32], a (wr, kc) that is no GD_W8_TILES tile, K % kc,
+// or N (mode 1: N / 2) no multiple of the tile's columns.
+hipError_t launch_gemm_decode_w8_grouped(bf16_t* Y, int64_t ldy, const bf16_t* X, int64_t ldx, const uint8_t* Wq,
+                                         const float* scales, const int* offsets, const int* rows, int k, int E, int T,
+                                         int R, int N, int K, int mode, int wr, int kc, int max_rows, hipStream_t s);
+
 }  // namespace die

@@ -51,7 +51,8 @@ class ModelConfig:
     # models, role "both": see LLMEngine)
     kv_cache_dtype: str = "auto"
     # "auto": bf16 weights; "fp8": the layers' projections quantised to OCP e4m3 with per-row scales, decode steps of
-    # <= 32 rows stream the one-byte copies (one GPU, dense models: see LLMEngine)
+    # <= 32 rows stream the one-byte copies (one GPU, dense models: see LLMEngine); "fp8_experts": a MoE model's expert
+    # weights likewise, through the grouped W8A16 decode GEMM (one GPU; qkv, o and the router stay bf16)
     weight_dtype: str = "auto"
     enable_prefix_caching: bool = True
     use_cuda_graph: bool = True        # hipGraph capture of decode steps
@@ -86,7 +87,8 @@ class EngineConfig:
     block_size: int = 16
     num_kv_blocks: Optional[int] = None
     kv_cache_dtype: str = "auto"       # "auto" (bf16) | "fp8" (e4m3 pool, per-layer k / v scales)
-    weight_dtype: str = "auto"         # "auto" (bf16) | "fp8" (e4m3 projections, per-row scales, W8A16 decode GEMM)
+    # "auto" (bf16) | "fp8" (e4m3 projections, per-row scales, W8A16 decode GEMM) | "fp8_experts" (MoE: e4m3 experts)
+    weight_dtype: str = "auto"
     gpu_memory_fraction: float = 0.90
     enable_prefix_caching: bool = True
     kv_block_ttl_s: Optional[float] = None  # TTL for cached (unreferenced) KV blocks

@@ -60,17 +60,25 @@ def check_kv_cache_dtype(cfg: EngineConfig, model: CausalLM) -> None:
 
 
 def check_weight_dtype(cfg: EngineConfig, model: CausalLM) -> bool:
-    """Whether the engine serves FP8 weights (weight_dtype="fp8"); what they do not serve is refused when the
-    engine is built."""
+    """Whether the engine serves FP8 weights (weight_dtype="fp8": a dense model's qkv, o, gate/up and down;
+    "fp8_experts": a MoE model's expert weights); what they do not serve is refused when the engine is built."""
     mode = getattr(cfg, "weight_dtype", "auto")
-    if mode not in ("auto", "fp8"):
-        raise ValueError(f"weight_dtype must be auto / fp8, not {mode!r}")
+    if mode not in ("auto", "fp8", "fp8_experts"):
+        raise ValueError(f"weight_dtype must be auto / fp8 / fp8_experts, not {mode!r}")
     if mode == "auto":
         return False
     if model.tp.enabled:
-        raise ValueError("weight_dtype='fp8' is not available on a tensor-parallel engine")
-    if model.arch.is_moe:
-        raise ValueError("weight_dtype='fp8' is not available on a MoE model: the W8 decode GEMM has no grouped form")
+        raise ValueError(f"weight_dtype={mode!r} is not available on a tensor-parallel engine")
+    if mode == "fp8" and model.arch.is_moe:
+        raise ValueError("weight_dtype='fp8' (qkv, o, gate/up and down) is not available on a MoE model: "
+                         "weight_dtype='fp8_experts' serves its expert weights in FP8")
+    if mode == "fp8_experts":
+        if not model.arch.is_moe:
+            raise ValueError("weight_dtype='fp8_experts' is not available on a dense model: it has no experts "
+                             "(weight_dtype='fp8' serves its projections in FP8)")
+        if getattr(cfg, "kv_cache_dtype", "auto") == "fp8":
+            raise ValueError("weight_dtype='fp8_experts' is not available with kv_cache_dtype='fp8': the FP8 KV "
+                             "cache is not available on a MoE model")
     return True
 
 
@@ -153,7 +161,18 @@ class LLMEngine:
             enable_prefill_gemm_table(self.device)
         self.decode_weight_layout = "row-major"
         self.weight_fp8 = check_weight_dtype(cfg, model)
-        if self.weight_fp8:
+        self.weight_dtype = cfg.weight_dtype if self.weight_fp8 else "auto"
+        if self.weight_dtype == "fp8_experts":
+            # as below: the experts' FP8 copies are made before the KV pool takes the free HBM
+            if getattr(model, "weight_dtype", "auto") != "fp8_experts":
+                model.quantize_expert_weights_fp8()
+            tiles = model.w8_moe_tiles
+            self.decode_weight_layout = "fp8_experts" if tiles is not None else "row-major"
+            logger.info("FP8 expert weights: %d tensors quantised (e4m3, per-row scales per expert), %s, +%.2f GiB of "
+                        "FP8 copies", model.w8_stats["quantized"],
+                        "grouped W8 decode GEMM" if tiles is not None else "no W8 tile divides the experts: bf16 paths",
+                        model.decode_copy_bytes(()) / 2**30)
+        elif self.weight_fp8:
             # quantised before anything else is packed and before the KV pool takes the free HBM: the projections
             # become dequantised e4m3 values, decode steps of <= 32 rows stream the FP8 copies
             if getattr(model, "weight_dtype", "auto") != "fp8":
@@ -819,7 +838,7 @@ class LLMEngine:
         # decode weight tensors streamed in the lossless 13-bit layout / kept in tile order (outside its window)
         p13 = getattr(self.model, "p13_stats", None) or {"packed": 0, "raw": 0}
         s["p13_tensors_packed"], s["p13_tensors_raw"] = p13["packed"], p13["raw"]
-        s["weight_dtype"] = "fp8" if self.weight_fp8 else "auto"
+        s["weight_dtype"] = self.weight_dtype
         s["fp8_tensors_quantized"] = (getattr(self.model, "w8_stats", None) or {"quantized": 0})["quantized"]
         s["logprob_launches"] = getattr(self.runner, "logprob_launches", 0)  # ops.token_logprobs launches
         s["logit_process_launches"] = getattr(self.runner, "logit_process_launches", 0)  # ops.logit_process

@@ -1107,10 +1107,10 @@ class ModelRunner:
     def capture_graphs(self) -> None:
         if not self.is_cuda or not self.cfg.use_cuda_graph:
             return
-        # an FP8-weight model decodes on the slab sequence, which allocates its slabs in every step; every other
-        # engine captures exactly as before
-        fp8 = getattr(self.model, "weight_dtype", "auto") == "fp8"
-        with _no_gc_while_capturing() if fp8 else contextlib.nullcontext():
+        # every captured step allocates (the slab paths their slabs, the fused layer its o / down slabs, the MoE block
+        # its sorted rows): a cyclic collection that starts inside a capture while a dead engine is pending aborts
+        # the process, whichever engine is capturing, so no engine captures with the collector on
+        with _no_gc_while_capturing():
             self._capture_graphs()
 
     def _capture_graphs(self) -> None:

@@ -63,7 +63,8 @@ class AttnMetadata:
 
 class LayerWeights:
     # tiled: decode-GEMM tile-order copies {(projection, wr, kc): tensor} (CausalLM.pack_decode_weights)
-    # w8: FP8 decode copies {projection: (packed e4m3 bytes, scales [N] fp32)} (CausalLM.quantize_weights_fp8)
+    # w8: FP8 decode copies {projection: (packed e4m3 bytes, scales [N] fp32)} (CausalLM.quantize_weights_fp8), or of
+    # a MoE layer {"w13" / "w2": (packed bytes [E, rows, K], scales [E, rows])} (CausalLM.quantize_expert_weights_fp8)
     __slots__ = ("ln1", "ln2", "qkv", "o", "gate_up", "down", "router", "w13", "w2", "tiled", "w8")
 
     def __init__(self):
@@ -132,7 +133,10 @@ class CausalLM:
         # "fp8" once quantize_weights_fp8 has run: the projections hold dequantised e4m3 values and decode steps of
         # <= 32 rows stream the FP8 copies (lw.w8) where w8_plan has a tile for every projection
         self.weight_dtype = "auto"
+        # "fp8_experts" once quantize_expert_weights_fp8 has run (MoE): w13 / w2 hold dequantised e4m3 values and
+        # decode steps of <= 32 tokens stream their FP8 copies on w8_moe_tiles; qkv, o and the router stay bf16
         self.w8_plan: Optional[dict] = None
+        self.w8_moe_tiles = None
         self.w8_stats = {"quantized": 0}
         self.layers: List[LayerWeights] = []
         self._init_random(seed, init_std)
@@ -244,6 +248,8 @@ class CausalLM:
         self.norms_folded = True
         if self.weight_dtype == "fp8":  # FP8 weights are quantised after the fold: the folded layers only
             self.quantize_weights_fp8(layers)
+        elif self.weight_dtype == "fp8_experts":  # the fold leaves w13 / w2 alone; the copies are re-made all the same
+            self.quantize_expert_weights_fp8(layers)
 
     W8_PROJECTIONS = ("qkv", "o", "gate_up", "down")
 
@@ -291,6 +297,45 @@ class CausalLM:
         if self.device.type == "cuda":
             torch.cuda.empty_cache()  # the packing transients, before the KV pool is sized
         return self.w8_stats["quantized"]
+
+    @torch.inference_mode()
+    def quantize_expert_weights_fp8(self, layers: Optional[List[int]] = None) -> int:
+        """Make this MoE model one with FP8 expert weights: w13 and w2 of every layer are quantised to e4m3 with one
+        power-of-two fp32 scale per output row per expert (ops.quantize_weights_fp8 on the [E * rows, K] view), the
+        bf16 tensors are overwritten with the dequantised values - exactly the numbers the FP8 copies hold, so
+        prefill, steps above 32 tokens and every fallback compute the same model - and the FP8 bytes are kept per
+        expert in the grouped W8 kernel's order for ops.moe_decode_tiles_w8's tiles with their scales (lw.w8["w13"],
+        lw.w8["w2"]). qkv, o and the router stay bf16 (about 3 % of Mixtral's bytes) and the layer keeps its fused qkv
+        -> attention -> o launches. ``layers``: only those (quantising quantised values again changes nothing).
+        Returns the number of tensors quantised so far."""
+        if not self.arch.is_moe or self.tp.enabled:
+            raise ValueError("weight_dtype='fp8_experts' is for a MoE model on one GPU")
+        e, rows13, h = self.layers[0].w13.shape
+        self.weight_dtype = "fp8_experts"
+        self.w8_moe_tiles = ops.moe_decode_tiles_w8(h, rows13 // 2, min(e, ops.w8.MOE_ACTIVE_EXPERTS))
+        todo = set(range(len(self.layers)) if layers is None else layers)
+        for i in sorted(todo):
+            lw = self.layers[i]
+            lw.w8 = {}
+            for name, ti, silu in (("w13", 0, True), ("w2", 1, False)):
+                w = getattr(lw, name)
+                q, sc = ops.quantize_weights_fp8(w.view(-1, w.shape[2]))
+                w.copy_(ops.dequantize_weights_fp8(q, sc).to(w.dtype).view(w.shape))
+                if self.w8_moe_tiles is not None:
+                    lw.w8[name] = (ops.gd_pack_experts_w8(q.view(w.shape), *self.w8_moe_tiles[ti], silu=silu),
+                                   sc.view(w.shape[:2]).contiguous())
+        if layers is not None:
+            todo |= self.w8_stats.get("layers", set())
+        self.w8_stats = {"quantized": 2 * len(todo), "layers": todo}
+        if self.device.type == "cuda":
+            torch.cuda.empty_cache()  # the packing transients, before the KV pool is sized
+        return self.w8_stats["quantized"]
+
+    def _moe_w8(self, lw: LayerWeights):
+        """ops.moe_apply's ``w8`` of a layer: its FP8 expert copies and their tiles, or None where it has none."""
+        if self.weight_dtype != "fp8_experts" or "w13" not in lw.w8:
+            return None
+        return lw.w8["w13"], lw.w8["w2"], self.w8_moe_tiles
 
     def pack_lm_head(self) -> bool:
         """Re-lay the LM head IN PLACE in the decode GEMM's tile order (one copy: its only consumer is the
@@ -419,7 +464,8 @@ class CausalLM:
         m.__dict__.update({k: v for k, v in self.__dict__.items()
                            if k not in ("layers", "embed", "norm", "lm_head", "cos_sin")})
         m.device, m.dtype = torch.device(device), dtype
-        m.weight_dtype, m.w8_plan = "auto", None  # the (dequantised) values are carried over, not the FP8 copies
+        # the (dequantised) values are carried over, not the FP8 copies
+        m.weight_dtype, m.w8_plan, m.w8_moe_tiles = "auto", None, None
 
         def conv(t):
             return None if t is None else t.detach().to(device=device, dtype=dtype)
@@ -599,7 +645,8 @@ class CausalLM:
         a = self.arch
         if a.is_moe:
             w, ids = ops.moe_route(x, lw.router, a.top_k)  # one fused launch at decode sizes
-            return ops.moe_forward_routed(x, lw.w13, lw.w2, w, ids, expert0=self.expert0 if self.ep else None)
+            return ops.moe_forward_routed(x, lw.w13, lw.w2, w, ids, expert0=self.expert0 if self.ep else None,
+                                          w8=self._moe_w8(lw))
         return ops.linear(ops.linear_silu_mul(x, lw.gate_up), lw.down)
 
     def _forward_sp(self, residual_full: torch.Tensor, positions: torch.Tensor, meta: AttnMetadata,
@@ -889,7 +936,7 @@ class CausalLM:
     def decode_copy_bytes(self, buckets) -> int:
         """HBM the decode weight copies take: the tile-order copies (0 where none are made), or an FP8-weight
         model's e4m3 copies and scales."""
-        if self.weight_dtype == "fp8":
+        if self.weight_dtype in ("fp8", "fp8_experts"):
             return self._w8_bytes()
         if not self.tiled_decode_weights or self.arch.is_moe or not self.norms_folded:
             return 0
@@ -990,7 +1037,7 @@ class CausalLM:
                     self.tp.all_reduce_residual(self._mlp(lw, x), h, ssp_b)
                 else:  # combine + residual add + statistics in one launch
                     wr_, ids_ = ops.moe_route(x, lw.router, a.top_k)
-                    ops.moe_forward_routed(x, lw.w13, lw.w2, wr_, ids_, residual=h, ssp=ssp_b)
+                    ops.moe_forward_routed(x, lw.w13, lw.w2, wr_, ids_, residual=h, ssp=ssp_b, w8=self._moe_w8(lw))
             else:
                 wg, kg = plan["gate_up"]
                 gsk = plan.get("gate_up_sk", 1)

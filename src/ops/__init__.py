@@ -22,7 +22,8 @@ from .decode_tiles import (DECODE_GEMM_MAX_M, DECODE_TILE_CFG, HALF_RING, MODE_B
 from .p13 import P13_DEN, P13_NUM, P13_TILE, gd_pack_weights_p13, gd_unpack_weights_p13, p13_base7
 # FP8 (e4m3) weights of the W8A16 decode GEMM: tiles, packer, tile choice, quantiser (pure torch)
 from .w8 import (W8_BF16, W8_MAX_M, W8_SILU, W8_SLAB, W8_TILES, decode_tile_w8, dequantize_weights_fp8,
-                 gd_pack_weights_w8, gd_unpack_weights_w8, quantize_weights_fp8, ring_slots_w8, w8_tile_valid)
+                 gd_pack_experts_w8, gd_pack_weights_w8, gd_unpack_experts_w8, gd_unpack_weights_w8,
+                 moe_decode_tiles_w8, quantize_weights_fp8, ring_slots_w8, w8_tile_valid)
 
 _C = None
 _C_ERR: Optional[BaseException] = None
@@ -936,6 +937,23 @@ def linear_slab_w8(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor, wr: 
     return gemm_decode_w8(x, wq, scales, W8_SLAB, wr, kc, sk)
 
 
+def gemm_decode_w8_grouped(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor, offsets: torch.Tensor, mode: int,
+                           wr: int, kc: int, rows: Optional[torch.Tensor] = None, k: int = 1,
+                           max_rows: int = W8_MAX_M, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Raw access to the grouped (MoE) W8A16 decode GEMM (csrc/kernels/gemm_decode_w8_grouped.hip): for every group e
+    of ``offsets`` [E + 1] (int32; at most ``max_rows`` <= 32 rows each) out[off[e]:off[e + 1]] = (xrows @ q[e]^T) *
+    scales[e], with ``wq`` [E, N, K] the experts' e4m3 bytes packed by gd_pack_experts_w8 for (wr, kc) (W8_SILU: with
+    silu=True) and ``scales`` [E, N] fp32. ``rows`` (int32 [T k], moe_align's sorted order): x is in token order and
+    the kernel gathers row rows[j] // k; without it x is in the sorted order. ``mode``: W8_BF16 or W8_SILU (bf16
+    silu(gate) * up, [., N / 2]). A missing kernel or a refused shape raises."""
+    r = x.shape[0] if rows is None else rows.numel()
+    if out is None:
+        out = torch.empty(r, wq.shape[1] // 2 if mode == W8_SILU else wq.shape[1], dtype=x.dtype, device=x.device)
+    _kern_w8().gemm_decode_w8_grouped(out, x, wq, scales, offsets, mode, wr, kc,
+                                      rows if rows is not None else _NO_ROWS(x.device), k, max_rows)
+    return out
+
+
 def fused_add_rms_norm_slab(slab: torch.Tensor, residual: torch.Tensor, w: torch.Tensor, eps: float,
                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """residual += slab.sum(0) (bf16, in place); returns rms_norm(residual) * w."""
@@ -1014,14 +1032,15 @@ def moe_route(x: torch.Tensor, router: torch.Tensor, k: int, renorm: bool = True
 
 def moe_forward_routed(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, w: torch.Tensor, ids: torch.Tensor,
                        expert0: Optional[int] = None, residual: Optional[torch.Tensor] = None,
-                       ssp: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       ssp: Optional[torch.Tensor] = None, w8=None) -> torch.Tensor:
     """:func:`moe_forward` after routing (``w``, ``ids`` [T, k] over ALL routed experts). With
-    ``residual``/``ssp``: residual += output and ssp[0, :T] = its row sums of squares (returns residual)."""
+    ``residual``/``ssp``: residual += output and ssp[0, :T] = its row sums of squares (returns residual).
+    ``w8``: the experts' FP8 copies (:func:`moe_apply`; not with ``expert0``)."""
     e = w13.shape[0]
     if expert0 is not None:
         w, ids = expert_parallel_local(w, ids, expert0, e)
         return moe_apply(x, w13, w2, w, ids, e + 1, residual, ssp)
-    return moe_apply(x, w13, w2, w, ids, e, residual, ssp)
+    return moe_apply(x, w13, w2, w, ids, e, residual, ssp, w8)
 
 
 def moe_forward(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, gating: torch.Tensor, k: int,
@@ -1036,14 +1055,23 @@ def moe_forward(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, gating: to
 
 
 def moe_apply(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, w: torch.Tensor, ids: torch.Tensor,
-              groups: int, residual: Optional[torch.Tensor] = None, ssp: Optional[torch.Tensor] = None) -> torch.Tensor:
+              groups: int, residual: Optional[torch.Tensor] = None, ssp: Optional[torch.Tensor] = None,
+              w8=None) -> torch.Tensor:
     """out[t] = sum_j w[t, j] * expert_{ids[t, j]}(x[t]) for given routing (w [T, k] fp32, ids [T, k]
     int32). ``groups`` may exceed the number of local experts ``w13.shape[0]``: assignments to those
-    extra groups are not computed (their weight must be 0)."""
+    extra groups are not computed (their weight must be 0).
+    ``w8`` = ((q13, s13), (q2, s2), ((wr, kc), (wr, kc))): the experts' FP8 copies (q [E, rows, K] packed by
+    gd_pack_experts_w8 for its tile, s [E, rows] fp32) of which ``w13`` / ``w2`` hold the dequantised values. GPU steps
+    of <= W8_MAX_M tokens run the two grouped W8 launches on them in place of the two bf16 ones; every other case
+    reads ``w13`` / ``w2`` as without it (on the CPU: ref.moe_experts on the dequantised copies, the same numbers)."""
     e = w13.shape[0]
     if residual is not None and not (x.is_cuda and x.shape[0] <= MOE_DECODE_MAX_T):
-        return residual_add_sumsq(residual, moe_apply(x, w13, w2, w, ids, groups), ssp)
+        return residual_add_sumsq(residual, moe_apply(x, w13, w2, w, ids, groups, w8=w8), ssp)
     if not x.is_cuda:
+        if w8 is not None:
+            (q13, s13), (q2, s2), ((wr1, kc1), (wr2, kc2)) = w8
+            w13 = dequantize_weights_fp8(gd_unpack_experts_w8(q13, wr1, kc1, silu=True), s13).to(w13.dtype)
+            w2 = dequantize_weights_fp8(gd_unpack_experts_w8(q2, wr2, kc2), s2).to(w2.dtype)
         return ref.moe_experts(x, w13, w2, w, ids)
     kern = _kern()
     t, hdim = x.shape
@@ -1055,6 +1083,19 @@ def moe_apply(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, w: torch.Ten
     # rows of the extra groups are never computed: zero them so that weight 0 x row stays 0
     ys = (torch.zeros if groups > e else torch.empty)(t * k, hdim, dtype=x.dtype, device=x.device)
     x = x.contiguous()
+    if w8 is not None and t <= W8_MAX_M and groups == e:
+        # decode on FP8 expert weights: the same two launches, one byte streamed per weight; each workgroup picks
+        # its group's 16- or 32-row image itself
+        (q13, s13), (q2, s2), ((wr1, kc1), (wr2, kc2)) = w8
+        a = torch.empty(t * k, inter, dtype=x.dtype, device=x.device)
+        gemm_decode_w8_grouped(x, q13, s13, offsets, W8_SILU, wr1, kc1, rows=sorted_idx, k=k, max_rows=t, out=a)
+        gemm_decode_w8_grouped(a, q2, s2, offsets, W8_BF16, wr2, kc2, max_rows=t, out=ys)
+        if residual is not None:
+            kern.moe_combine_residual(ssp, residual, ys, pos, w)
+            return residual
+        out = torch.empty_like(x)
+        kern.moe_combine(out, ys, pos, w)
+        return out
     tiles = moe_decode_tiles(hdim, inter, t)
     if tiles is not None and t <= MOE_DECODE_MAX_T:
         # decode: every expert's weights streamed once by the weight-streaming kernel, its routed

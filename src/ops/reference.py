@@ -177,8 +177,8 @@ def quantize_weights_fp8(w: torch.Tensor):
 
 
 def dequantize_weights_fp8(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
-    """fp32 q * s of e4m3 bytes (uint8 or float8_e4m3fn storage) and per-row scales."""
-    return q.view(torch.float8_e4m3fn).float() * s.float()[:, None]
+    """fp32 q * s of e4m3 bytes (uint8 or float8_e4m3fn storage) [..., N, K] and per-row scales [..., N]."""
+    return q.view(torch.float8_e4m3fn).float() * s.float()[..., None]
 
 
 def linear_w8(x: torch.Tensor, q: torch.Tensor, s: torch.Tensor, mode: str = "bf16", sk: int = 1, kc: int = 256):

@@ -127,6 +127,55 @@ W8_TILE_CFG = {
 }
 
 
+def gd_pack_experts_w8(q: torch.Tensor, wr: int, kc: int = 256, silu: bool = False) -> torch.Tensor:
+    """:func:`gd_pack_weights_w8` per expert: q [E, rows, K] -> the stacked packed images [E, rows, K] (uint8) that
+    the grouped W8 GEMM reads, expert e's image at byte e * rows * K."""
+    return torch.stack([gd_pack_weights_w8(q[e], wr, kc, silu=silu) for e in range(q.shape[0])])
+
+
+def gd_unpack_experts_w8(packed: torch.Tensor, wr: int, kc: int = 256, silu: bool = False) -> torch.Tensor:
+    """Exact inverse of :func:`gd_pack_experts_w8`."""
+    return torch.stack([gd_unpack_weights_w8(packed[e], wr, kc, silu=silu) for e in range(packed.shape[0])])
+
+
+# (hidden, inter) -> ((wr, kc) of the grouped gate/up + SiLU GEMM, (wr, kc) of the grouped down GEMM): the measured
+# tiles of the grouped W8 GEMM (MI355X, cold weights, top-2 of 8 routing from seed 0: bench/micro_gemm_decode.py M moe
+# --w8, profiles/w8_moe_micro_and_engine.jsonl; us at 32 / 8 tokens, against the grouped bf16 kernel's tuned tile).
+# Thin evidence: ONE sweep of the three tiles in one session on one card, one routing draw per token count, the best
+# of five alternating replays each, never repeated. Here the widest tile won by 25 % and more at both token counts,
+# so it should not flip; a second sweep should still confirm it before anyone tunes on top of it.
+W8_MOE_TILE_CFG = {
+    # Mixtral-8x7B: gate/up 188.7 / 181.6 vs bf16 308.6 / 271.7 ((64, 256): 241.5 / 220.8, (32, 256): 352.5 / 308.6);
+    #               down     100.0 /  98.4 vs bf16 155.8 / 137.1 ((64, 256): 127.4 / 121.9, (32, 256): 184.8 / 179.4)
+    (4096, 14336): ((128, 256), (128, 256)),
+}
+MOE_ACTIVE_EXPERTS = 8   # groups with rows in a decode step, as the rule counts them (Mixtral at batch 32: all 8)
+
+
+def moe_decode_tiles_w8(hdim: int, inter: int, experts: int = MOE_ACTIVE_EXPERTS):
+    """((wr, kc) of the grouped W8 gate/up GEMM, (wr, kc) of the down one) for experts of [2 inter, hdim] and
+    [hdim, inter], or None when no W8 tile divides one of them: W8_MOE_TILE_CFG's measured entry, else
+    :func:`decode_tile_w8`'s rule (the grid closest in log2 to 256 workgroups, the wider tile on a tie) with the
+    grid multiplied by the ``experts`` expected to have rows."""
+    c = W8_MOE_TILE_CFG.get((hdim, inter))
+    if c is not None:
+        return c
+
+    def rule(n, k, silu):
+        best, score = None, 1e9
+        for wr, kc in reversed(W8_TILES):
+            cols = wr // 2 if silu else wr
+            if n % cols or k % kc:
+                continue
+            sc = abs(math.log2((n // cols) * max(1, experts) / 256.0))
+            if sc < score - 1e-9:
+                best, score = (wr, kc), sc
+        return best
+
+    t13, t2 = rule(inter, hdim, True), rule(hdim, inter, False)
+    return None if t13 is None or t2 is None else (t13, t2)
+
+
 def decode_tile_w8(n: int, k: int, silu: bool = False, split: bool = False,
                    max_sk: int = 8) -> Optional[Tuple[int, int, int]]:
     """(wr, kc, sk) of the W8 decode GEMM for an [n, k] projection (silu: n (gate, up) pairs; split: the slab mode,
