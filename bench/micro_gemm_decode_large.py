@@ -7,10 +7,12 @@ Cold-cache protocol as bench/micro_gemm_decode.py (>= 1.5 GiB of distinct weight
 hipGraph). One JSON line per (shape, M, variant): us per call and effective weight GB/s.
 
     python bench/micro_gemm_decode_large.py [M ...]
+    python bench/micro_gemm_decode_large.py [M ...] --w8    # M in 33 .. 128: the wide W8A16 GEMM against the bf16 one
 """
 
 import json
 import os
+import statistics
 import sys
 
 import torch
@@ -45,7 +47,67 @@ def splits(n, k, mode, wr, kc):
     return out
 
 
+def capture(fn, ws):
+    """A hipGraph of one call of fn per weight copy (cold weights: the copies exceed every cache), and its call count."""
+    for w in ws[:2]:
+        fn(w)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for w in ws:
+            fn(w)
+    torch.cuda.synchronize()
+    return g, len(ws)
+
+
+def main_w8(ms, rounds=7):
+    """`--w8`: the wide W8A16 decode GEMM (ops.gemm_decode_w8_wide) at every W8 tile that divides the shape x its split
+    counts against the bf16 decode GEMM as an FP8-weight engine runs it above 32 rows without the wide kernel
+    (ops.linear_slab / ops.linear_silu_mul on the row-major weights, the bucket's tuned tile). Cold weights; every
+    variant is captured first, then the graphs are replayed in turn, `rounds` times: best, median and worst us per
+    call, and the weight bytes per second of the median."""
+    dev = torch.device("cuda:0")
+    for name, (n, k, mode) in SHAPES.items():
+        silu = mode == 4
+        rows = 2 * n if silu else n
+        copies = max(2, int(1.5 * 2**30 // (rows * k * 2)) + 1)
+        ws = [torch.randn(rows, k, device=dev, dtype=torch.bfloat16) / 64 for _ in range(copies)]
+        qs = [torch.randint(0, 0x78, (rows, k), device=dev, dtype=torch.uint8) for _ in range(2 * copies)]  # timing only
+        sc = torch.ones(rows, device=dev)
+        for m in ms:
+            x = torch.randn(m, k, device=dev, dtype=torch.bfloat16)
+            wr, kc, sk = ops.decode_tile(n, k, ops.MODE_SILU if silu else ops.MODE_SLAB, ops.decode_bucket(m))
+            runs = [("bf16", wr, kc, sk, 2) + capture((lambda w: ops.linear_silu_mul(x, w)) if silu else
+                                                      (lambda w: ops.linear_slab(x, w)), ws)]
+            for wr8, kc8 in ops.W8_TILES:
+                if n % (wr8 // 2 if silu else wr8) or k % kc8:
+                    continue
+                for sk8 in ((1,) if silu else (1, 2, 4, 8)):
+                    fn = lambda q, t=(wr8, kc8, sk8): ops.gemm_decode_w8_wide(  # noqa: E731
+                        x, q, sc, ops.W8_SILU if silu else ops.W8_SLAB, *t)
+                    runs.append(("w8_wide", wr8, kc8, sk8, 1) + capture(fn, qs))
+            us = [[] for _ in runs]
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            for _ in range(rounds):
+                for i, r in enumerate(runs):
+                    s.record()
+                    r[5].replay()
+                    e.record()
+                    torch.cuda.synchronize()
+                    us[i].append(s.elapsed_time(e) * 1e3 / r[6])
+            for (kernel, w_, k_, s_, bpw, _, _), t in zip(runs, us):
+                print(json.dumps({"bench": "w8_wide_micro", "shape": name, "M": m, "kernel": kernel, "wr": w_, "kc": k_,
+                                  "sk": s_, "us_best": round(min(t), 2), "us_median": round(statistics.median(t), 2),
+                                  "us_worst": round(max(t), 2),
+                                  "weight_GBps": round(rows * k * bpw / statistics.median(t) / 1e3, 1)}), flush=True)
+            del runs
+        del ws, qs
+        torch.cuda.empty_cache()
+
+
 def main():
+    if "--w8" in sys.argv[1:]:
+        return main_w8([int(a) for a in sys.argv[1:] if a != "--w8"] or [64, 128])
     ms = [int(a) for a in sys.argv[1:]] or [32, 64, 128]
     dev = torch.device("cuda:0")
     for name, (n, k, mode) in SHAPES.items():

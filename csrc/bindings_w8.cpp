@@ -1,5 +1,5 @@
-// Torch bindings of the W8A16 decode GEMM and its grouped (MoE) form (module `src._C_w8`,
-// csrc/kernels/gemm_decode_w8.hip and gemm_decode_w8_grouped.hip). A third module next
+// Torch bindings of the W8A16 decode GEMM, its wide (33 to 128 rows) and its grouped (MoE) form (module `src._C_w8`,
+// csrc/kernels/gemm_decode_w8.hip, gemm_decode_w8_wide.hip and gemm_decode_w8_grouped.hip). A third module next
 // to `_C` and `_C_kv8` with the same rules (bindings.cpp): every argument is validated through the vocabulary of
 // arg_check.h before anything is launched on the current stream, and no tensor is asked for its address here.
 #include <torch/extension.h>
@@ -8,6 +8,7 @@
 #include "arg_check.h"
 #include "kernels/gd_w8.h"
 #include "kernels/gd_w8_launch.h"
+#include "kernels/gd_w8_wide.h"
 
 using torch::Tensor;
 using chk::Op;
@@ -60,6 +61,40 @@ void gemm_decode_w8(Tensor out, Tensor x, Tensor wq, Tensor scales, int64_t mode
   }
 }
 
+// The wide form (gemm_decode_w8_wide.hip): the same arguments, checks and packed bytes on 33 <= M <= 128 rows.
+void gemm_decode_w8_wide(Tensor out, Tensor x, Tensor wq, Tensor scales, int64_t mode, int64_t wr, int64_t kc,
+                         int64_t sk) {
+  const Op a("gemm_decode_w8_wide", x, "x");
+  const auto xr = a.rows(x, "x");
+  const int M = a.i32(x.size(0)), K = a.i32(x.size(1));
+  TORCH_CHECK(M >= w8::wide::MIN_M && M <= w8::wide::MAX_M, "gemm_decode_w8_wide: ", w8::wide::MIN_M, " to ",
+              w8::wide::MAX_M, " rows (up to ", w8::MAX_M, ": gemm_decode_w8), got ", M);
+  TORCH_CHECK(mode == 0 || mode == 1 || mode == 2, "gemm_decode_w8_wide: mode 0 (bf16), 1 (SiLU) or 2 (slab), got ",
+              mode);
+  TORCH_CHECK(tile_exists(wr, kc), "gemm_decode_w8_wide: no W8 tile (", wr, ", ", kc, ")");
+  TORCH_CHECK(wq.scalar_type() == at::kByte || wq.scalar_type() == at::kFloat8_e4m3fn,
+              "gemm_decode_w8_wide: wq must be uint8 or float8_e4m3fn, got ", wq.scalar_type());
+  const uint8_t* wp = static_cast<const uint8_t*>(a.dense<void>(wq, "wq", 0, {chk::ge(1), K}, 16));
+  const int N = a.i32(wq.size(0));
+  TORCH_CHECK(mode != 1 || N % 2 == 0, "gemm_decode_w8_wide: the SiLU form takes [gate; up], an even row count");
+  const int64_t n_out = mode == 1 ? N / 2 : N, cols = mode == 1 ? wr / 2 : wr;
+  TORCH_CHECK(K >= kc && K % kc == 0, "gemm_decode_w8_wide: K = ", K, " must be a multiple of kc = ", kc);
+  TORCH_CHECK(n_out % cols == 0, "gemm_decode_w8_wide: ", n_out, " output columns are no multiple of the tile's ",
+              cols);
+  TORCH_CHECK(sk >= 1 && sk <= K / kc && (mode == 2 || sk == 1), "gemm_decode_w8_wide: sk = ", sk,
+              " must be in [1, K / kc] and 1 unless mode 2");
+  const float* sp = a.dense<float>(scales, "scales", N, {N}, 16);
+  if (mode == 2) {
+    float* op = a.dense<float>(out, "out", 0, {sk, M, n_out}, 16);
+    LAUNCH(launch_gemm_decode_w8_wide(op, n_out, xr.p, xr.ld, wp, sp, M, N, K, (int)mode, (int)wr, (int)kc, (int)sk,
+                                      cur_stream()));
+  } else {
+    const auto o = a.rows(out, "out", M, n_out);
+    LAUNCH(launch_gemm_decode_w8_wide(o.p, o.ld, xr.p, xr.ld, wp, sp, M, N, K, (int)mode, (int)wr, (int)kc, 1,
+                                      cur_stream()));
+  }
+}
+
 // The grouped (MoE) form: y [R, N] (mode 1: [R, N / 2]) bf16, group e = rows [offsets[e], offsets[e + 1]) of y, at most
 // max_rows (<= 32) of them; wq [E, N, K] e4m3 bytes, each expert packed by gd_pack_weights_w8 for (wr, kc) (mode 1:
 // silu=True); scales [E, N] fp32. rows (int32 [R], numel 0 = no gather): x is [T, K] in token order with T k == R and
@@ -104,6 +139,7 @@ int64_t ring_slots(int64_t wr, int64_t kc, int64_t xr) { return w8::ring_slots((
 PYBIND11_MODULE(_C_w8, m) {
   m.doc() = "gfx950 HIP kernels of the W8A16 (FP8 e4m3 weights) decode GEMM, dense and grouped";
   m.def("gemm_decode_w8", &gemm_decode_w8);
+  m.def("gemm_decode_w8_wide", &gemm_decode_w8_wide);
   m.def("gemm_decode_w8_grouped", &gemm_decode_w8_grouped);
   m.def("ring_slots", &ring_slots);
   m.def("check_only", &check_only);

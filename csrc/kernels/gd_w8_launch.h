@@ -1,4 +1,4 @@
-// Host launcher of the W8A16 decode GEMM (gemm_decode_w8.hip). As launchers.h: raw pointers and an explicit stream,
+// Host launchers of the W8A16 decode GEMMs (gemm_decode_w8.hip, its wide and its grouped form). As launchers.h: raw pointers and an explicit stream,
 // no allocation, no synchronisation.
 #pragma once
 
@@ -19,6 +19,13 @@ namespace die {
 hipError_t launch_gemm_decode_w8(void* Y, int64_t ldy, const bf16_t* X, int64_t ldx, const uint8_t* Wq,
                                  const float* scales, int M, int N, int K, int mode, int wr, int kc, int sk,
                                  hipStream_t s);
+
+// The wide form (gemm_decode_w8_wide.hip): the same product, operands, packed bytes, modes and split-K rule for
+// 33 <= M <= 128 rows (activation images of 64 and 128 rows; geometry in gd_w8_wide.h).
+// hipErrorInvalidValue (nothing launched) for M outside [33, 128] and for everything launch_gemm_decode_w8 refuses.
+hipError_t launch_gemm_decode_w8_wide(void* Y, int64_t ldy, const bf16_t* X, int64_t ldx, const uint8_t* Wq,
+                                      const float* scales, int M, int N, int K, int mode, int wr, int kc, int sk,
+                                      hipStream_t s);
 
 // The grouped (MoE) form (gemm_decode_w8_grouped.hip): Y[off[e] : off[e + 1]] = (Xrows · q[e]^T) ⊙ s[e] for the E
 // groups of offsets [E + 1] (int32, ascending, at most max_rows <= 32 rows each; an empty group reads nothing).

@@ -131,11 +131,12 @@ class CausalLM:
         self.p13_stats = {"packed": 0, "raw": 0}  # tensors packed / kept in tile order (outside the window)
         self.prefill_gemm_residual = True  # TP=1 prefill: o / down add into the residual in the GEMM (beta = 1)
         # "fp8" once quantize_weights_fp8 has run: the projections hold dequantised e4m3 values and decode steps of
-        # <= 32 rows stream the FP8 copies (lw.w8) where w8_plan has a tile for every projection
+        # <= 128 rows stream the FP8 copies (lw.w8) where w8_plan has a tile for every projection
         self.weight_dtype = "auto"
         # "fp8_experts" once quantize_expert_weights_fp8 has run (MoE): w13 / w2 hold dequantised e4m3 values and
         # decode steps of <= 32 tokens stream their FP8 copies on w8_moe_tiles; qkv, o and the router stay bf16
         self.w8_plan: Optional[dict] = None
+        self._w8_bucket_plans: dict = {}  # row bucket above 32 -> w8_plan with that bucket's split-K (_w8_step_plan)
         self.w8_moe_tiles = None
         self.w8_stats = {"quantized": 0}
         self.layers: List[LayerWeights] = []
@@ -267,6 +268,21 @@ class CausalLM:
                 return None
         return plan
 
+    def _w8_step_plan(self, m: int) -> dict:
+        """w8_plan for a step of m rows: the tiles are the packed copies', only the slab projections' split-K follows
+        the row bucket (ops.decode_sk_w8; up to 32 rows the plan as it is)."""
+        b = ops.decode_bucket(m)
+        if b <= ops.W8_MAX_M:
+            return self.w8_plan
+        plan = self._w8_bucket_plans.get(b)
+        if plan is None:
+            plan = {}
+            for name, (wr, kc, sk) in self.w8_plan.items():
+                n, k = getattr(self.layers[0], name).shape
+                plan[name] = (wr, kc, sk if name == "gate_up" else ops.decode_sk_w8(n, k, wr, kc, sk, b))
+            self._w8_bucket_plans[b] = plan
+        return plan
+
     @torch.inference_mode()
     def quantize_weights_fp8(self, layers: Optional[List[int]] = None) -> int:
         """Make this an FP8-weight model: qkv, o, gate_up and down of every layer are quantised to e4m3 with one
@@ -279,7 +295,7 @@ class CausalLM:
         if self.arch.is_moe or self.tp.enabled:
             raise ValueError("weight_dtype='fp8' is not available on a MoE model or a tensor-parallel engine")
         self.weight_dtype = "fp8"
-        self.w8_plan = self.decode_plan_w8()
+        self.w8_plan, self._w8_bucket_plans = self.decode_plan_w8(), {}
         todo = set(range(len(self.layers)) if layers is None else layers)
         for i in sorted(todo):
             lw = self.layers[i]
@@ -708,16 +724,20 @@ class CausalLM:
         return ops.fused_add_rms_norm_slab(slab, residual, self.norm, eps)
 
     def _w8_path(self, input_ids: torch.Tensor, meta: AttnMetadata) -> bool:
-        """Decode steps of <= 32 rows of an FP8-weight model stream the FP8 copies (the slab sequence on the W8
-        GEMM); everything else runs the bf16 paths on the dequantised weights."""
+        """Decode steps of an FP8-weight model stream the FP8 copies (the slab sequence on the W8 GEMMs): up to 32 rows
+        always, above in the row buckets of ops.W8_WIDE_BUCKETS; everything else runs the bf16 paths on the
+        dequantised weights."""
+        m = input_ids.shape[0]
         return (self.weight_dtype == "fp8" and self.w8_plan is not None and not meta.is_prefill
-                and input_ids.shape[0] <= ops.W8_MAX_M and bool(self.layers[0].w8) and self._slab_path(input_ids))
+                and (m <= ops.W8_MAX_M or (m <= ops.W8_WIDE_MAX_M and ops.decode_bucket(m) in ops.W8_WIDE_BUCKETS))
+                and bool(self.layers[0].w8) and self._slab_path(input_ids))
 
     def _forward_decode_slab_w8(self, residual, positions, meta: AttnMetadata, kv_pool):
         """:meth:`_forward_decode_slab`'s sequence with the W8 GEMM in place of linear_slab / linear_silu_mul: four
-        FP8 weight streams per layer, the slab consumers unchanged (a one-byte KV pool included)."""
+        FP8 weight streams per layer, the slab consumers unchanged (a one-byte KV pool included). The three
+        linear_*_w8 ops choose the kernel by the row count."""
         eps, d = self.arch.rms_eps, self.head_dim
-        hq, hkv, plan = self.hq, self.hkv, self.w8_plan
+        hq, hkv, plan = self.hq, self.hkv, self._w8_step_plan(residual.shape[0])
         x = ops.rms_norm(residual, self.layers[0].ln1, eps)
         slab = None
         for li, lw in enumerate(self.layers):

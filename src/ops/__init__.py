@@ -21,9 +21,10 @@ from .decode_tiles import (DECODE_GEMM_MAX_M, DECODE_TILE_CFG, HALF_RING, MODE_B
 # the lossless 13-bit weight layout of the (128, 128) tile: packer and exact inverse (pure torch)
 from .p13 import P13_DEN, P13_NUM, P13_TILE, gd_pack_weights_p13, gd_unpack_weights_p13, p13_base7
 # FP8 (e4m3) weights of the W8A16 decode GEMM: tiles, packer, tile choice, quantiser (pure torch)
-from .w8 import (W8_BF16, W8_MAX_M, W8_SILU, W8_SLAB, W8_TILES, decode_tile_w8, dequantize_weights_fp8,
-                 gd_pack_experts_w8, gd_pack_weights_w8, gd_unpack_experts_w8, gd_unpack_weights_w8,
-                 moe_decode_tiles_w8, quantize_weights_fp8, ring_slots_w8, w8_tile_valid)
+from .w8 import (W8_BF16, W8_MAX_M, W8_SILU, W8_SLAB, W8_TILES, W8_WIDE_BUCKETS, W8_WIDE_MAX_M, decode_sk_w8,
+                 decode_tile_w8, dequantize_weights_fp8, gd_pack_experts_w8, gd_pack_weights_w8, gd_unpack_experts_w8,
+                 gd_unpack_weights_w8, moe_decode_tiles_w8, quantize_weights_fp8, ring_slots_w8, ring_slots_w8_wide,
+                 w8_tile_valid)
 
 _C = None
 _C_ERR: Optional[BaseException] = None
@@ -921,20 +922,39 @@ def gemm_decode_w8(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor, mode
     return out
 
 
+def gemm_decode_w8_wide(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor, mode: int, wr: int, kc: int,
+                        sk: int = 1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`gemm_decode_w8` for x of 33 to 128 rows (csrc/kernels/gemm_decode_w8_wide.hip): the same operands, the
+    same packed bytes, the same modes. A missing kernel or a refused shape raises."""
+    m, n = x.shape[0], wq.shape[0]
+    if out is None:
+        if mode == W8_SLAB:
+            out = torch.empty(sk, m, n, dtype=torch.float32, device=x.device)
+        else:
+            out = torch.empty(m, n // 2 if mode == W8_SILU else n, dtype=x.dtype, device=x.device)
+    _kern_w8().gemm_decode_w8_wide(out, x, wq, scales, mode, wr, kc, sk)
+    return out
+
+
+def _gemm_w8(x: torch.Tensor):
+    """The W8 decode GEMM of x's row count: up to W8_MAX_M rows the 32-row kernel, above it the wide one."""
+    return gemm_decode_w8 if x.shape[0] <= W8_MAX_M else gemm_decode_w8_wide
+
+
 def linear_w8(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor, wr: int, kc: int) -> torch.Tensor:
-    """bf16 (x @ q^T) * scales on FP8 weights packed for (wr, kc) (decode sizes, <= 32 rows)."""
-    return gemm_decode_w8(x, wq, scales, W8_BF16, wr, kc)
+    """bf16 (x @ q^T) * scales on FP8 weights packed for (wr, kc) (decode sizes, <= 128 rows)."""
+    return _gemm_w8(x)(x, wq, scales, W8_BF16, wr, kc)
 
 
 def linear_silu_mul_w8(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor, wr: int, kc: int) -> torch.Tensor:
     """bf16 silu(g) * u with (g, u) = (x @ q^T) * scales, q = [gate; up] packed with silu=True for (wr, kc)."""
-    return gemm_decode_w8(x, wq, scales, W8_SILU, wr, kc)
+    return _gemm_w8(x)(x, wq, scales, W8_SILU, wr, kc)
 
 
 def linear_slab_w8(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor, wr: int, kc: int,
                    sk: int = 1) -> torch.Tensor:
     """fp32 split-K slabs [sk, M, N] of (x @ q^T) * scales; the consumers of :func:`linear_slab` reduce them."""
-    return gemm_decode_w8(x, wq, scales, W8_SLAB, wr, kc, sk)
+    return _gemm_w8(x)(x, wq, scales, W8_SLAB, wr, kc, sk)
 
 
 def gemm_decode_w8_grouped(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor, offsets: torch.Tensor, mode: int,

@@ -127,6 +127,59 @@ W8_TILE_CFG = {
 }
 
 
+# The wide W8 decode GEMM (csrc/kernels/gemm_decode_w8_wide.hip, geometry in gd_w8_wide.h): 33 to W8_WIDE_MAX_M rows
+# on the same packed bytes and tiles, activation images of 64 and 128 rows, ring slots of half a chunk (128 columns).
+W8_WIDE_MAX_M = 128
+W8_WIDE_IMAGES = (64, 128)
+W8_WIDE_GRAIN = 128
+# The row buckets above 32 at which an FP8-weight engine runs the wide kernel (CausalLM._w8_path); a bucket not listed
+# runs the bf16 kernels on the dequantised weights, as every step above 32 rows did before the wide kernel existed.
+# EMPTY, because both buckets measured slower in the engine (MI355X, Llama-3-8B shapes, one wave of batch x (512 -> 128),
+# bench/w8_wide_engine_cost.py, profiles/w8_wide_micro_and_engine.jsonl; two engines each, alternating, two waves each):
+# batch 64: 0.954 - 0.960 s with the bucket on against 0.898 - 0.919 s with it off (bf16 engine 0.878);
+# batch 128: 1.565 - 1.571 s against 1.470 - 1.485 s (bf16 engine 1.465 - 1.471).
+# Thin evidence (one session, one card), but the smallest gap (0.035 s, 0.080 s) exceeds the largest spread seen between
+# like engines (0.021 s, 0.015 s). (64, 128) switches both on.
+W8_WIDE_BUCKETS: tuple = ()
+
+
+def ring_slots_w8_wide(wr: int, xr: int) -> int:
+    """LDS ring depth of the wide kernel, in slots of W8_WIDE_GRAIN columns (mirror of gd_w8_wide.h ring_slots, whose
+    static_asserts pin the six values)."""
+    slot = wr * W8_WIDE_GRAIN + xr * W8_WIDE_GRAIN * 2
+    s = min(MAX_SLOTS, RING_BYTES // slot)
+    while s > 2 and (s - 1) * (slot // 1024 // 4) > 63:
+        s -= 1
+    return s
+
+
+# (N, K, row bucket) -> sk of the wide kernel's slab launches where a measurement replaced decode_sk_w8's rule. Empty:
+# on the Llama-3-8B shapes at the plan's tiles the rule's sk was also the fastest of (1, 2, 4, 8) at 64 and at 128 rows
+# (qkv (128, 256) sk 4, o (64, 256) sk 4, down (128, 256) sk 8; one sweep, bench/micro_gemm_decode_large.py --w8).
+W8_WIDE_SK_CFG: dict = {}
+
+
+def decode_sk_w8(n: int, k: int, wr: int, kc: int, sk: int, bucket: int, max_sk: int = 8) -> int:
+    """Split-K of a slab projection [n, k] of an FP8 plan at steps of ``bucket`` rows. The plan's tile (wr, kc) is fixed
+    (the bytes are packed for it); sk is a launch parameter. Up to 32 rows: the plan's own ``sk``. Above:
+    W8_WIDE_SK_CFG's measured entry, else :func:`decode_tile_w8`'s rule on that tile - the sk of (1, 2, 4, 8) that
+    brings the grid closest (in log2) to 256 workgroups, the smaller on a tie (a slab is bucket x n fp32 per slice,
+    written and read once: it grows with the rows where the weight stream does not)."""
+    if bucket <= W8_MAX_M:
+        return sk
+    c = W8_WIDE_SK_CFG.get((n, k, bucket))
+    if c is not None and c <= max_sk:
+        return c
+    best, score = 1, 1e9
+    for cand in (1, 2, 4, 8):
+        if cand > max_sk or cand > k // kc:
+            continue
+        sc = abs(math.log2((n // wr) * cand / 256.0))
+        if sc < score - 1e-9:
+            best, score = cand, sc
+    return best
+
+
 def gd_pack_experts_w8(q: torch.Tensor, wr: int, kc: int = 256, silu: bool = False) -> torch.Tensor:
     """:func:`gd_pack_weights_w8` per expert: q [E, rows, K] -> the stacked packed images [E, rows, K] (uint8) that
     the grouped W8 GEMM reads, expert e's image at byte e * rows * K."""
