@@ -266,7 +266,8 @@ def main_moe(m):
 
 def main_moe_w8(m, reps=5, seed=0):
     """`M moe --w8`: Mixtral-8x7B's grouped expert GEMMs at m tokens (top-2 of 8, routing drawn from `seed`), the
-    grouped W8 launch (ops.gemm_decode_w8_grouped, every W8 tile) against the grouped bf16 launch at its tuned tile.
+    grouped W8 launch (ops.gemm_decode_w8_grouped up to 32 tokens, ops.gemm_decode_w8_grouped_wide above, up to 128;
+    every W8 tile) against the grouped bf16 launch at its tuned tile.
     Cold weights: two copies of each stacked tensor are cycled (>= 0.9 GiB each, beyond the Infinity Cache). All
     variants of a shape are captured first and then replayed in turn, `reps` rounds: the line of a variant carries the
     best, the median and the worst round. W8 bytes are random codes (no NaN): the time does not depend on the layout,
@@ -282,6 +283,7 @@ def main_moe_w8(m, reps=5, seed=0):
     ys = torch.empty(k * m, h, device=dev, dtype=torch.bfloat16)
     kern, none = ops._kern(), torch.empty(0, dtype=torch.int32, device=dev)
     t1, t2 = ops.moe_decode_tiles(h, inter, m)
+    gw8 = ops.gemm_decode_w8_grouped if m <= ops.W8_MAX_M else ops.gemm_decode_w8_grouped_wide
     for nm, rows, kk, silu in (("moe_w13", 2 * inter, h, True), ("moe_w2", h, inter, False)):
         ws = [torch.randn(e, rows, kk, device=dev, dtype=torch.bfloat16) / 64 for _ in range(2)]
         qs = [torch.randint(0, 0x78, (e, rows, kk), device=dev, dtype=torch.uint8) for _ in range(2)]
@@ -289,14 +291,12 @@ def main_moe_w8(m, reps=5, seed=0):
         if silu:
             variants = [("bf16", t1, ws, lambda w: kern.gemm_decode_grouped(out13, x, w, offsets, MODE_SILU, *t1,
                                                                             sorted_idx, k, m, 1))]
-            variants += [("w8", t, qs, lambda q, t=t: ops.gemm_decode_w8_grouped(x, q, sc, offsets, ops.W8_SILU, *t,
-                                                                                 rows=sorted_idx, k=k, max_rows=m,
-                                                                                 out=out13)) for t in ops.W8_TILES]
+            variants += [("w8", t, qs, lambda q, t=t: gw8(x, q, sc, offsets, ops.W8_SILU, *t, rows=sorted_idx, k=k,
+                                                          max_rows=m, out=out13)) for t in ops.W8_TILES]
         else:
             variants = [("bf16", t2, ws, lambda w: kern.gemm_decode_grouped(ys, a, w, offsets, MODE_BF16, *t2, none, 1,
                                                                             m, 1))]
-            variants += [("w8", t, qs, lambda q, t=t: ops.gemm_decode_w8_grouped(a, q, sc, offsets, ops.W8_BF16, *t,
-                                                                                 max_rows=m, out=ys))
+            variants += [("w8", t, qs, lambda q, t=t: gw8(a, q, sc, offsets, ops.W8_BF16, *t, max_rows=m, out=ys))
                          for t in ops.W8_TILES]
         graphs, iters = [], 8
         for _, _, bufs, fn in variants:

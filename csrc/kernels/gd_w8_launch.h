@@ -1,4 +1,4 @@
-// Host launchers of the W8A16 decode GEMMs (gemm_decode_w8.hip, its wide and its grouped form). As launchers.h: raw pointers and an explicit stream,
+// Host launchers of the W8A16 decode GEMMs (gemm_decode_w8.hip, its wide, its grouped and its wide grouped form). As launchers.h: raw pointers and an explicit stream,
 // no allocation, no synchronisation.
 #pragma once
 
@@ -38,5 +38,15 @@ hipError_t launch_gemm_decode_w8_wide(void* Y, int64_t ldy, const bf16_t* X, int
 hipError_t launch_gemm_decode_w8_grouped(bf16_t* Y, int64_t ldy, const bf16_t* X, int64_t ldx, const uint8_t* Wq,
                                          const float* scales, const int* offsets, const int* rows, int k, int E, int T,
                                          int R, int N, int K, int mode, int wr, int kc, int max_rows, hipStream_t s);
+
+// The wide grouped form (gemm_decode_w8_grouped_wide.hip): the same product, operands, packed bytes, gather and modes
+// for groups of at most max_rows <= 128 rows each. The kernel chooses the 16-, 32-, 64- or 128-row image per group
+// (up to 32 rows: the grouped kernel's own body; above: half-chunk slots on gd_w8_wide.h's geometry).
+// hipErrorInvalidValue (nothing launched) for max_rows outside [1, 128] and for everything else
+// launch_gemm_decode_w8_grouped refuses.
+hipError_t launch_gemm_decode_w8_grouped_wide(bf16_t* Y, int64_t ldy, const bf16_t* X, int64_t ldx, const uint8_t* Wq,
+                                              const float* scales, const int* offsets, const int* rows, int k, int E,
+                                              int T, int R, int N, int K, int mode, int wr, int kc, int max_rows,
+                                              hipStream_t s);
 
 }  // namespace die

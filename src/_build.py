@@ -44,7 +44,7 @@ KV8_KERNELS = ["attention_kv8"]
 KV8_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # the W8A16 decode GEMM (FP8 e4m3 weights) and its grouped (MoE) form: a third module (src/_C_w8*.so), built like the KV8 kernels (no packed
 # fp32 forms) and, as the bf16 decode GEMM, with multiply-adds fused per source expression only
-W8_KERNELS = ["gemm_decode_w8", "gemm_decode_w8_wide", "gemm_decode_w8_grouped"]
+W8_KERNELS = ["gemm_decode_w8", "gemm_decode_w8_wide", "gemm_decode_w8_grouped", "gemm_decode_w8_grouped_wide"]
 CONTRACT_ON |= set(W8_KERNELS)
 # module -> (kernels, bindings source, extra hipcc flags)
 MODULES = {"_C": (KERNELS, "bindings", []), "_C_kv8": (KV8_KERNELS, "bindings_kv8", KV8_FLAGS),

@@ -319,8 +319,8 @@ class CausalLM:
         """Make this MoE model one with FP8 expert weights: w13 and w2 of every layer are quantised to e4m3 with one
         power-of-two fp32 scale per output row per expert (ops.quantize_weights_fp8 on the [E * rows, K] view), the
         bf16 tensors are overwritten with the dequantised values - exactly the numbers the FP8 copies hold, so
-        prefill, steps above 32 tokens and every fallback compute the same model - and the FP8 bytes are kept per
-        expert in the grouped W8 kernel's order for ops.moe_decode_tiles_w8's tiles with their scales (lw.w8["w13"],
+        prefill, steps above ops.w8.W8_MOE_MAX_T tokens and every fallback compute the same model - and the FP8 bytes
+        are kept per expert in the grouped W8 kernels' order for ops.moe_decode_tiles_w8's tiles with their scales (lw.w8["w13"],
         lw.w8["w2"]). qkv, o and the router stay bf16 (about 3 % of Mixtral's bytes) and the layer keeps its fused qkv
         -> attention -> o launches. ``layers``: only those (quantising quantised values again changes nothing).
         Returns the number of tensors quantised so far."""

@@ -21,6 +21,7 @@ from .decode_tiles import (DECODE_GEMM_MAX_M, DECODE_TILE_CFG, HALF_RING, MODE_B
 # the lossless 13-bit weight layout of the (128, 128) tile: packer and exact inverse (pure torch)
 from .p13 import P13_DEN, P13_NUM, P13_TILE, gd_pack_weights_p13, gd_unpack_weights_p13, p13_base7
 # FP8 (e4m3) weights of the W8A16 decode GEMM: tiles, packer, tile choice, quantiser (pure torch)
+from . import w8 as w8_cfg  # moe_apply reads W8_MOE_MAX_T there at every call (a switch, not a copied constant)
 from .w8 import (W8_BF16, W8_MAX_M, W8_SILU, W8_SLAB, W8_TILES, W8_WIDE_BUCKETS, W8_WIDE_MAX_M, decode_sk_w8,
                  decode_tile_w8, dequantize_weights_fp8, gd_pack_experts_w8, gd_pack_weights_w8, gd_unpack_experts_w8,
                  gd_unpack_weights_w8, moe_decode_tiles_w8, quantize_weights_fp8, ring_slots_w8, ring_slots_w8_wide,
@@ -974,6 +975,20 @@ def gemm_decode_w8_grouped(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tens
     return out
 
 
+def gemm_decode_w8_grouped_wide(x: torch.Tensor, wq: torch.Tensor, scales: torch.Tensor, offsets: torch.Tensor,
+                                mode: int, wr: int, kc: int, rows: Optional[torch.Tensor] = None, k: int = 1,
+                                max_rows: int = W8_WIDE_MAX_M, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`gemm_decode_w8_grouped` for groups of at most ``max_rows`` <= 128 rows each
+    (csrc/kernels/gemm_decode_w8_grouped_wide.hip): the same operands, the same packed bytes, the same modes; every
+    workgroup picks its group's 16-, 32-, 64- or 128-row image. A missing kernel or a refused shape raises."""
+    r = x.shape[0] if rows is None else rows.numel()
+    if out is None:
+        out = torch.empty(r, wq.shape[1] // 2 if mode == W8_SILU else wq.shape[1], dtype=x.dtype, device=x.device)
+    _kern_w8().gemm_decode_w8_grouped_wide(out, x, wq, scales, offsets, mode, wr, kc,
+                                           rows if rows is not None else _NO_ROWS(x.device), k, max_rows)
+    return out
+
+
 def fused_add_rms_norm_slab(slab: torch.Tensor, residual: torch.Tensor, w: torch.Tensor, eps: float,
                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """residual += slab.sum(0) (bf16, in place); returns rms_norm(residual) * w."""
@@ -1082,7 +1097,8 @@ def moe_apply(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, w: torch.Ten
     extra groups are not computed (their weight must be 0).
     ``w8`` = ((q13, s13), (q2, s2), ((wr, kc), (wr, kc))): the experts' FP8 copies (q [E, rows, K] packed by
     gd_pack_experts_w8 for its tile, s [E, rows] fp32) of which ``w13`` / ``w2`` hold the dequantised values. GPU steps
-    of <= W8_MAX_M tokens run the two grouped W8 launches on them in place of the two bf16 ones; every other case
+    of <= ops.w8.W8_MOE_MAX_T tokens run the two grouped W8 launches on them in place of the two bf16 ones (up to W8_MAX_M
+    tokens the 32-row kernel, above it the wide grouped one on the same bytes); every other case
     reads ``w13`` / ``w2`` as without it (on the CPU: ref.moe_experts on the dequantised copies, the same numbers)."""
     e = w13.shape[0]
     if residual is not None and not (x.is_cuda and x.shape[0] <= MOE_DECODE_MAX_T):
@@ -1103,13 +1119,14 @@ def moe_apply(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, w: torch.Ten
     # rows of the extra groups are never computed: zero them so that weight 0 x row stays 0
     ys = (torch.zeros if groups > e else torch.empty)(t * k, hdim, dtype=x.dtype, device=x.device)
     x = x.contiguous()
-    if w8 is not None and t <= W8_MAX_M and groups == e:
+    if w8 is not None and t <= w8_cfg.W8_MOE_MAX_T and groups == e:
         # decode on FP8 expert weights: the same two launches, one byte streamed per weight; each workgroup picks
-        # its group's 16- or 32-row image itself
+        # its group's row image itself (16 or 32 rows; above W8_MAX_M tokens the wide kernel, also 64 or 128)
         (q13, s13), (q2, s2), ((wr1, kc1), (wr2, kc2)) = w8
         a = torch.empty(t * k, inter, dtype=x.dtype, device=x.device)
-        gemm_decode_w8_grouped(x, q13, s13, offsets, W8_SILU, wr1, kc1, rows=sorted_idx, k=k, max_rows=t, out=a)
-        gemm_decode_w8_grouped(a, q2, s2, offsets, W8_BF16, wr2, kc2, max_rows=t, out=ys)
+        grouped = gemm_decode_w8_grouped if t <= W8_MAX_M else gemm_decode_w8_grouped_wide
+        grouped(x, q13, s13, offsets, W8_SILU, wr1, kc1, rows=sorted_idx, k=k, max_rows=t, out=a)
+        grouped(a, q2, s2, offsets, W8_BF16, wr2, kc2, max_rows=t, out=ys)
         if residual is not None:
             kern.moe_combine_residual(ssp, residual, ys, pos, w)
             return residual

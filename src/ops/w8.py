@@ -200,8 +200,26 @@ def gd_unpack_experts_w8(packed: torch.Tensor, wr: int, kc: int = 256, silu: boo
 W8_MOE_TILE_CFG = {
     # Mixtral-8x7B: gate/up 188.7 / 181.6 vs bf16 308.6 / 271.7 ((64, 256): 241.5 / 220.8, (32, 256): 352.5 / 308.6);
     #               down     100.0 /  98.4 vs bf16 155.8 / 137.1 ((64, 256): 127.4 / 121.9, (32, 256): 184.8 / 179.4)
+    # at 64 / 128 tokens (the wide grouped kernel on the same bytes; profiles/w8_moe_wide_micro_and_engine.jsonl):
+    #               gate/up 201.5 / 253.8 vs bf16 342.9 / 449.7 ((64, 256): 259.0 / 339.1, (32, 256): 395.8 / 538.1);
+    #               down    109.6 / 161.9 vs bf16 247.6 / 303.6 ((64, 256): 133.3 / 185.5, (32, 256): 199.9 / 269.2)
+    # the same tile wins at every token count: the packed bytes serve all of them at their best tile
     (4096, 14336): ((128, 256), (128, 256)),
 }
+# The largest token count at which ops.moe_apply runs the grouped W8 launches on the experts' FP8 copies: up to W8_MAX_M
+# tokens the 32-row grouped kernel, above it the wide grouped one (csrc/kernels/gemm_decode_w8_grouped_wide.hip, groups
+# of up to 128 rows on the same packed bytes); above W8_MOE_MAX_T the bf16 grouped GEMM on the dequantised experts.
+# 32, 64 or 128; ops.moe_apply reads it here at every call (a decode hipGraph keeps what it read at capture).
+# 128, because the engine measured faster with it at both batches (MI355X, Mixtral-8x7B shapes, fp8_experts engines of
+# 128 sequences, one wave of batch x (512 -> 128), bench/w8_moe_wide_engine_cost.py,
+# profiles/w8_moe_wide_micro_and_engine.jsonl; two engines each, alternating, two waves each; 32 runs what every
+# fp8_experts engine ran above 32 tokens before the wide grouped kernel existed):
+# batch 64: 2.248 - 2.252 s per wave with 128 against 3.311 - 3.314 s with 32 (28.4 against 19.3 req/s);
+# batch 128: 3.462 - 3.479 s against 4.675 - 4.687 s (36.9 against 27.3 req/s).
+# Thin evidence (one session, one card), but the smallest gap (1.06 s, 1.20 s) is 60 times the largest spread seen
+# between like engines (0.004 s, 0.017 s). Rule: 128 if faster at both batches by more than that spread, 64 if only at
+# batch 64, else 32.
+W8_MOE_MAX_T = 128
 MOE_ACTIVE_EXPERTS = 8   # groups with rows in a decode step, as the rule counts them (Mixtral at batch 32: all 8)
 
 
