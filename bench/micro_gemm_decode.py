@@ -61,7 +61,9 @@ def main():
     if len(sys.argv) > 2 and sys.argv[2] == "deep":
         return main_deep(m)
     if len(sys.argv) > 2 and sys.argv[2] == "moe":
-        return main_moe_w8(m) if "--w8" in sys.argv[3:] else main_moe(m)
+        if "--w8" in sys.argv[3:] or "--w4" in sys.argv[3:]:
+            return main_moe_w8(m, w4="--w4" in sys.argv[3:])
+        return main_moe(m)
     if len(sys.argv) > 2 and sys.argv[2] == "chain":
         return main_chain(m)
     if "--w8" in sys.argv[2:]:
@@ -264,14 +266,16 @@ def main_moe(m):
                           "xr16": xr16, "us": round(us, 2), "GBps": round(wbytes / us / 1e3, 1)}), flush=True)
 
 
-def main_moe_w8(m, reps=5, seed=0):
+def main_moe_w8(m, reps=5, seed=0, w4=False):
     """`M moe --w8`: Mixtral-8x7B's grouped expert GEMMs at m tokens (top-2 of 8, routing drawn from `seed`), the
     grouped W8 launch (ops.gemm_decode_w8_grouped up to 32 tokens, ops.gemm_decode_w8_grouped_wide above, up to 128;
     every W8 tile) against the grouped bf16 launch at its tuned tile.
     Cold weights: two copies of each stacked tensor are cycled (>= 0.9 GiB each, beyond the Infinity Cache). All
     variants of a shape are captured first and then replayed in turn, `reps` rounds: the line of a variant carries the
     best, the median and the worst round. W8 bytes are random codes (no NaN): the time does not depend on the layout,
-    so one pair of copies serves the three tiles. gate/up gathers its rows from the token order in both kernels."""
+    so one pair of copies serves the three tiles. gate/up gathers its rows from the token order in both kernels.
+    `M moe --w4` (M <= 32) adds the grouped W4 launch (ops.gemm_decode_w4_grouped on MXFP4 bytes, every W4 tile) to the
+    same alternation; its bytes are random codes with every scale byte 2^-7, E * rows * (K / 2 + K / 32) of them."""
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(seed)
     e, h, inter, k = 8, 4096, 14336, 2
@@ -288,6 +292,12 @@ def main_moe_w8(m, reps=5, seed=0):
         ws = [torch.randn(e, rows, kk, device=dev, dtype=torch.bfloat16) / 64 for _ in range(2)]
         qs = [torch.randint(0, 0x78, (e, rows, kk), device=dev, dtype=torch.uint8) for _ in range(2)]
         sc = torch.full((e, rows), 2.0 ** -8, device=dev)
+        q4 = []
+        for _ in range(2 if w4 else 0):
+            q = torch.randint(0, 256, (e, rows, kk // 2 + kk // 32), device=dev, dtype=torch.uint8)
+            for wr, kc in ops.W4_TILES:   # a chunk's scale bytes end its record: the last 1 / 17 of it, whatever the tile
+                q.view(-1, ops.w4_cfg.record_bytes(wr, kc))[:, ops.w4_cfg.chunk_bytes(wr, kc):] = 120
+            q4.append(q)
         if silu:
             variants = [("bf16", t1, ws, lambda w: kern.gemm_decode_grouped(out13, x, w, offsets, MODE_SILU, *t1,
                                                                             sorted_idx, k, m, 1))]
@@ -298,6 +308,12 @@ def main_moe_w8(m, reps=5, seed=0):
                                                                             m, 1))]
             variants += [("w8", t, qs, lambda q, t=t: gw8(a, q, sc, offsets, ops.W8_BF16, *t, max_rows=m, out=ys))
                          for t in ops.W8_TILES]
+        if w4 and silu:
+            variants += [("w4", t, q4, lambda q, t=t: ops.gemm_decode_w4_grouped(
+                x, q, offsets, ops.W4_SILU, *t, rows=sorted_idx, k=k, max_rows=m, out=out13)) for t in ops.W4_TILES]
+        elif w4:
+            variants += [("w4", t, q4, lambda q, t=t: ops.gemm_decode_w4_grouped(
+                a, q, offsets, ops.W4_BF16, *t, max_rows=m, out=ys)) for t in ops.W4_TILES]
         graphs, iters = [], 8
         for _, _, bufs, fn in variants:
             for i in range(3):
@@ -325,7 +341,7 @@ def main_moe_w8(m, reps=5, seed=0):
                               "kc": t[1], "rows_per_expert": (offsets[1:] - offsets[:-1]).tolist(),
                               "us_best": round(ts[0], 2), "us_median": round(ts[len(ts) // 2], 2),
                               "us_worst": round(ts[-1], 2), "weight_GBps": round(wbytes / ts[0] / 1e3, 1)}), flush=True)
-        del ws, qs, graphs
+        del ws, qs, q4, graphs
 
 
 def main_chain(m):

@@ -5,7 +5,9 @@ layer of a decode step of <= 32 tokens: the grouped bf16 GEMMs, or the grouped W
 one line: the planned block count, the FP8 copies' bytes, and per timed wave (after a warm-up wave) the wall time, the
 requests per second and the time per decode step, taken as (wave - a wave of the same prompts with one generated token)
 / (gen - 1). No speed-up is promised: the line says what it is.
-python bench/w8_moe_engine_cost.py [preset] [batch] [prompt] [gen] [runs]"""
+A sixth argument lists the weight dtypes to alternate, comma-separated (default auto,fp8_experts; mxfp4_experts: the
+grouped W4A16 GEMMs on 17 / 64 of the bytes; "fp8_copies_GiB" counts whichever quantised copies the engine keeps).
+python bench/w8_moe_engine_cost.py [preset] [batch] [prompt] [gen] [runs] [dtypes]"""
 import gc
 import json
 import os
@@ -33,9 +35,10 @@ def main():
     preset = sys.argv[1] if len(sys.argv) > 1 else "mixtral-8x7b"
     b, p, g = (int(x) for x in sys.argv[2:5]) if len(sys.argv) > 4 else (32, 512, 128)
     runs = int(sys.argv[5]) if len(sys.argv) > 5 else 2
+    dtypes = tuple(sys.argv[6].split(",")) if len(sys.argv) > 6 else ("auto", "fp8_experts")
     rng = random.Random(0)
     for run in range(runs):
-        for dtype in ("auto", "fp8_experts"):
+        for dtype in dtypes:
             cfg = EngineConfig(max_num_seqs=b, max_num_batched_tokens=b * p, max_latency_ms=0.0, weight_dtype=dtype,
                                enable_prefix_caching=False)
             print(f"building {preset} weight_dtype={dtype} (run {run})", file=sys.stderr, flush=True)
@@ -54,7 +57,8 @@ def main():
             print(json.dumps({"bench": "w8_moe_engine_cost", "preset": preset, "weight_dtype": dtype, "run": run,
                               "batch": b, "prompt": p, "gen": g, "kv_blocks": eng.pool.num_blocks,
                               "fp8_copies_GiB": round(eng.model._w8_bytes() / 2**30, 2),
-                              "w8_moe_tiles": eng.model.w8_moe_tiles, "waves": waves}), flush=True)
+                              "w8_moe_tiles": eng.model.w8_moe_tiles, "w4_moe_tiles": eng.model.w4_moe_tiles,
+                              "waves": waves}), flush=True)
             del eng
             gc.collect()  # a dead engine is a cycle: freed before the next one is built
             torch.cuda.empty_cache()

@@ -7,8 +7,8 @@ kernels and the torch bindings into ``src/_C*.so`` and the host runtime
     python -m src._build --force
 
 The kernels are compiled once here with ``hipcc --offload-arch=gfx950`` and the
-``.so`` files (``_C``, ``_C_kv8``: the FP8 KV-cache kernels, ``_C_w8``: the FP8-weight decode GEMM, and ``_runtime``)
-travel with the repo snapshot to the GPU box.
+``.so`` files (``_C``, ``_C_kv8``: the FP8 KV-cache kernels, ``_C_w8``: the FP8-weight decode GEMM, ``_C_w4``: the
+MXFP4-weight grouped decode GEMM, and ``_runtime``) travel with the repo snapshot to the GPU box.
 """
 
 from __future__ import annotations
@@ -46,9 +46,12 @@ KV8_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 # fp32 forms) and, as the bf16 decode GEMM, with multiply-adds fused per source expression only
 W8_KERNELS = ["gemm_decode_w8", "gemm_decode_w8_wide", "gemm_decode_w8_grouped", "gemm_decode_w8_grouped_wide"]
 CONTRACT_ON |= set(W8_KERNELS)
+# the grouped W4A16 decode GEMM (MXFP4 expert weights): a fourth module (src/_C_w4*.so), built like the W8 kernels
+W4_KERNELS = ["gemm_decode_w4_grouped"]
+CONTRACT_ON |= set(W4_KERNELS)
 # module -> (kernels, bindings source, extra hipcc flags)
 MODULES = {"_C": (KERNELS, "bindings", []), "_C_kv8": (KV8_KERNELS, "bindings_kv8", KV8_FLAGS),
-           "_C_w8": (W8_KERNELS, "bindings_w8", KV8_FLAGS)}
+           "_C_w8": (W8_KERNELS, "bindings_w8", KV8_FLAGS), "_C_w4": (W4_KERNELS, "bindings_w4", KV8_FLAGS)}
 
 
 def _torch_paths():
@@ -77,7 +80,7 @@ def _headers(d: str):
 
 
 def build_kernels(force: bool = False, jobs: int = 8, verbose: bool = False, module: str = "_C") -> str:
-    """Compile one extension module of MODULES: `_C`, `_C_kv8` or `_C_w8` (its kernels + its bindings source)."""
+    """Compile one extension module of MODULES: `_C`, `_C_kv8`, `_C_w8` or `_C_w4` (its kernels + its bindings source)."""
     os.makedirs(OBJ, exist_ok=True)
     kernels, bname, extra = MODULES[module]
     out = os.path.join(ROOT, "src", module + EXT_SUFFIX)
@@ -138,6 +141,7 @@ def build_all(force: bool = False, verbose: bool = False) -> None:
     build_kernels(force, verbose=verbose)
     build_kernels(force, verbose=verbose, module="_C_kv8")
     build_kernels(force, verbose=verbose, module="_C_w8")
+    build_kernels(force, verbose=verbose, module="_C_w4")
 
 
 def main(argv=None) -> int:
@@ -151,6 +155,7 @@ def main(argv=None) -> int:
         print(build_kernels(a.force, verbose=a.verbose))
         print(build_kernels(a.force, verbose=a.verbose, module="_C_kv8"))
         print(build_kernels(a.force, verbose=a.verbose, module="_C_w8"))
+        print(build_kernels(a.force, verbose=a.verbose, module="_C_w4"))
     return 0
 
 

@@ -52,7 +52,9 @@ class ModelConfig:
     kv_cache_dtype: str = "auto"
     # "auto": bf16 weights; "fp8": the layers' projections quantised to OCP e4m3 with per-row scales, decode steps of
     # <= 32 rows stream the one-byte copies (one GPU, dense models: see LLMEngine); "fp8_experts": a MoE model's expert
-    # weights likewise, through the grouped W8A16 decode GEMM (one GPU; qkv, o and the router stay bf16)
+    # weights likewise, through the grouped W8A16 decode GEMM (one GPU; qkv, o and the router stay bf16);
+    # "mxfp4_experts": a MoE model's expert weights in OCP MXFP4 (e2m1, one e8m0 scale per 32), decode steps of <= 32
+    # tokens stream the 4-bit copies through the grouped W4A16 decode GEMM (one GPU)
     weight_dtype: str = "auto"
     enable_prefix_caching: bool = True
     use_cuda_graph: bool = True        # hipGraph capture of decode steps
@@ -88,6 +90,7 @@ class EngineConfig:
     num_kv_blocks: Optional[int] = None
     kv_cache_dtype: str = "auto"       # "auto" (bf16) | "fp8" (e4m3 pool, per-layer k / v scales)
     # "auto" (bf16) | "fp8" (e4m3 projections, per-row scales, W8A16 decode GEMM) | "fp8_experts" (MoE: e4m3 experts)
+    # | "mxfp4_experts" (MoE: MXFP4 experts, grouped W4A16 decode GEMM)
     weight_dtype: str = "auto"
     gpu_memory_fraction: float = 0.90
     enable_prefix_caching: bool = True

@@ -66,8 +66,9 @@ class LLMBackend:
             raise ValueError(f"kv_cache_dtype='fp8' is not available on a disaggregated {config.role} worker")
         if config.kv_cache_dtype == "fp8" and config.tp_size > 1:
             raise ValueError("kv_cache_dtype='fp8' is not available on a tensor-parallel engine")
-        if config.weight_dtype not in ("auto", "fp8", "fp8_experts"):
-            raise ValueError(f"weight_dtype must be auto / fp8 / fp8_experts, not {config.weight_dtype!r}")
+        if config.weight_dtype not in ("auto", "fp8", "fp8_experts", "mxfp4_experts"):
+            raise ValueError("weight_dtype must be auto / fp8 / fp8_experts / mxfp4_experts, "
+                             f"not {config.weight_dtype!r}")
         if config.weight_dtype != "auto" and config.tp_size > 1:
             raise ValueError(f"weight_dtype={config.weight_dtype!r} is not available on a tensor-parallel engine")
         if engine is None:

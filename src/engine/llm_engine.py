@@ -61,10 +61,11 @@ def check_kv_cache_dtype(cfg: EngineConfig, model: CausalLM) -> None:
 
 def check_weight_dtype(cfg: EngineConfig, model: CausalLM) -> bool:
     """Whether the engine serves FP8 weights (weight_dtype="fp8": a dense model's qkv, o, gate/up and down;
-    "fp8_experts": a MoE model's expert weights); what they do not serve is refused when the engine is built."""
+    "fp8_experts": a MoE model's expert weights) or MXFP4 ones ("mxfp4_experts": a MoE model's expert weights); what
+    they do not serve is refused when the engine is built."""
     mode = getattr(cfg, "weight_dtype", "auto")
-    if mode not in ("auto", "fp8", "fp8_experts"):
-        raise ValueError(f"weight_dtype must be auto / fp8 / fp8_experts, not {mode!r}")
+    if mode not in ("auto", "fp8", "fp8_experts", "mxfp4_experts"):
+        raise ValueError(f"weight_dtype must be auto / fp8 / fp8_experts / mxfp4_experts, not {mode!r}")
     if mode == "auto":
         return False
     if model.tp.enabled:
@@ -72,12 +73,12 @@ def check_weight_dtype(cfg: EngineConfig, model: CausalLM) -> bool:
     if mode == "fp8" and model.arch.is_moe:
         raise ValueError("weight_dtype='fp8' (qkv, o, gate/up and down) is not available on a MoE model: "
                          "weight_dtype='fp8_experts' serves its expert weights in FP8")
-    if mode == "fp8_experts":
+    if mode in ("fp8_experts", "mxfp4_experts"):
         if not model.arch.is_moe:
-            raise ValueError("weight_dtype='fp8_experts' is not available on a dense model: it has no experts "
+            raise ValueError(f"weight_dtype={mode!r} is not available on a dense model: it has no experts "
                              "(weight_dtype='fp8' serves its projections in FP8)")
         if getattr(cfg, "kv_cache_dtype", "auto") == "fp8":
-            raise ValueError("weight_dtype='fp8_experts' is not available with kv_cache_dtype='fp8': the FP8 KV "
+            raise ValueError(f"weight_dtype={mode!r} is not available with kv_cache_dtype='fp8': the FP8 KV "
                              "cache is not available on a MoE model")
     return True
 
@@ -171,6 +172,16 @@ class LLMEngine:
             logger.info("FP8 expert weights: %d tensors quantised (e4m3, per-row scales per expert), %s, +%.2f GiB of "
                         "FP8 copies", model.w8_stats["quantized"],
                         "grouped W8 decode GEMM" if tiles is not None else "no W8 tile divides the experts: bf16 paths",
+                        model.decode_copy_bytes(()) / 2**30)
+        elif self.weight_dtype == "mxfp4_experts":
+            # likewise: the experts' MXFP4 copies are made before the KV pool takes the free HBM
+            if getattr(model, "weight_dtype", "auto") != "mxfp4_experts":
+                model.quantize_expert_weights_mxfp4()
+            tiles = model.w4_moe_tiles
+            self.decode_weight_layout = "mxfp4_experts" if tiles is not None else "row-major"
+            logger.info("MXFP4 expert weights: %d tensors quantised (e2m1, one e8m0 scale per 32), %s, +%.2f GiB of "
+                        "4-bit copies", model.w4_stats["quantized"],
+                        "grouped W4 decode GEMM" if tiles is not None else "no W4 tile divides the experts: bf16 paths",
                         model.decode_copy_bytes(()) / 2**30)
         elif self.weight_fp8:
             # quantised before anything else is packed and before the KV pool takes the free HBM: the projections
@@ -840,6 +851,7 @@ class LLMEngine:
         s["p13_tensors_packed"], s["p13_tensors_raw"] = p13["packed"], p13["raw"]
         s["weight_dtype"] = self.weight_dtype
         s["fp8_tensors_quantized"] = (getattr(self.model, "w8_stats", None) or {"quantized": 0})["quantized"]
+        s["fp4_tensors_quantized"] = (getattr(self.model, "w4_stats", None) or {"quantized": 0})["quantized"]
         s["logprob_launches"] = getattr(self.runner, "logprob_launches", 0)  # ops.token_logprobs launches
         s["logit_process_launches"] = getattr(self.runner, "logit_process_launches", 0)  # ops.logit_process
         s["token_guide_launches"] = getattr(self.runner, "token_guide_launches", 0)  # ops.token_guide

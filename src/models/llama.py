@@ -65,13 +65,16 @@ class LayerWeights:
     # tiled: decode-GEMM tile-order copies {(projection, wr, kc): tensor} (CausalLM.pack_decode_weights)
     # w8: FP8 decode copies {projection: (packed e4m3 bytes, scales [N] fp32)} (CausalLM.quantize_weights_fp8), or of
     # a MoE layer {"w13" / "w2": (packed bytes [E, rows, K], scales [E, rows])} (CausalLM.quantize_expert_weights_fp8)
-    __slots__ = ("ln1", "ln2", "qkv", "o", "gate_up", "down", "router", "w13", "w2", "tiled", "w8")
+    # w4: MXFP4 decode copies of a MoE layer {"w13" / "w2": packed codes and block scales [E, rows, K / 2 + K / 32]}
+    # (CausalLM.quantize_expert_weights_mxfp4)
+    __slots__ = ("ln1", "ln2", "qkv", "o", "gate_up", "down", "router", "w13", "w2", "tiled", "w8", "w4")
 
     def __init__(self):
         for s in self.__slots__:
             setattr(self, s, None)
         self.tiled = {}
         self.w8 = {}
+        self.w4 = {}
 
 
 # LDS staging area of the fused decode attention's prologue (csrc/kernels/attention.hip V3_MERGE)
@@ -139,6 +142,10 @@ class CausalLM:
         self._w8_bucket_plans: dict = {}  # row bucket above 32 -> w8_plan with that bucket's split-K (_w8_step_plan)
         self.w8_moe_tiles = None
         self.w8_stats = {"quantized": 0}
+        # "mxfp4_experts" once quantize_expert_weights_mxfp4 has run (MoE): w13 / w2 hold dequantised MXFP4 values and
+        # decode steps of <= 32 tokens stream their 4-bit copies (lw.w4) on w4_moe_tiles
+        self.w4_moe_tiles = None
+        self.w4_stats = {"quantized": 0}
         self.layers: List[LayerWeights] = []
         self._init_random(seed, init_std)
         self.cos_sin = rope_cos_sin(self.max_position, a.head_dim, a.rope_theta, self.device, a.rope_scaling)
@@ -251,6 +258,8 @@ class CausalLM:
             self.quantize_weights_fp8(layers)
         elif self.weight_dtype == "fp8_experts":  # the fold leaves w13 / w2 alone; the copies are re-made all the same
             self.quantize_expert_weights_fp8(layers)
+        elif self.weight_dtype == "mxfp4_experts":
+            self.quantize_expert_weights_mxfp4(layers)
 
     W8_PROJECTIONS = ("qkv", "o", "gate_up", "down")
 
@@ -352,6 +361,45 @@ class CausalLM:
         if self.weight_dtype != "fp8_experts" or "w13" not in lw.w8:
             return None
         return lw.w8["w13"], lw.w8["w2"], self.w8_moe_tiles
+
+    @torch.inference_mode()
+    def quantize_expert_weights_mxfp4(self, layers: Optional[List[int]] = None) -> int:
+        """Make this MoE model one with MXFP4 expert weights: w13 and w2 of every layer are quantised to e2m1 codes with
+        one e8m0 scale per 32 input features of a row (ops.quantize_weights_mxfp4 on the [E * rows, K] view), the bf16
+        tensors are overwritten with the dequantised values - exactly the numbers the 4-bit copies hold, so prefill,
+        steps above ops.w4.W4_MOE_MAX_T tokens and every fallback compute the same model - and codes and scales are
+        kept per expert in the grouped W4 kernel's record order for ops.moe_decode_tiles_w4's tiles (lw.w4["w13"],
+        lw.w4["w2"]). qkv, o and the router stay bf16 and the layer keeps its fused qkv -> attention -> o launches.
+        ``layers``: only those (quantising quantised values again changes nothing). Returns the number of tensors
+        quantised so far."""
+        if not self.arch.is_moe or self.tp.enabled:
+            raise ValueError("weight_dtype='mxfp4_experts' is for a MoE model on one GPU")
+        e, rows13, h = self.layers[0].w13.shape
+        self.weight_dtype = "mxfp4_experts"
+        self.w4_moe_tiles = ops.moe_decode_tiles_w4(h, rows13 // 2, min(e, ops.w4.MOE_ACTIVE_EXPERTS))
+        todo = set(range(len(self.layers)) if layers is None else layers)
+        for i in sorted(todo):
+            lw = self.layers[i]
+            lw.w4 = {}
+            for name, ti, silu in (("w13", 0, True), ("w2", 1, False)):
+                w = getattr(lw, name)
+                codes, sb = ops.quantize_weights_mxfp4(w.view(-1, w.shape[2]))
+                w.copy_(ops.dequantize_weights_mxfp4(codes, sb).to(w.dtype).view(w.shape))
+                if self.w4_moe_tiles is not None:
+                    lw.w4[name] = ops.gd_pack_experts_w4(codes.view(*w.shape[:2], -1), sb.view(*w.shape[:2], -1),
+                                                         *self.w4_moe_tiles[ti], silu=silu)
+        if layers is not None:
+            todo |= self.w4_stats.get("layers", set())
+        self.w4_stats = {"quantized": 2 * len(todo), "layers": todo}
+        if self.device.type == "cuda":
+            torch.cuda.empty_cache()  # the packing transients, before the KV pool is sized
+        return self.w4_stats["quantized"]
+
+    def _moe_w4(self, lw: LayerWeights):
+        """ops.moe_apply's ``w4`` of a layer: its MXFP4 expert copies and their tiles, or None where it has none."""
+        if self.weight_dtype != "mxfp4_experts" or "w13" not in lw.w4:
+            return None
+        return lw.w4["w13"], lw.w4["w2"], self.w4_moe_tiles
 
     def pack_lm_head(self) -> bool:
         """Re-lay the LM head IN PLACE in the decode GEMM's tile order (one copy: its only consumer is the
@@ -481,7 +529,7 @@ class CausalLM:
                            if k not in ("layers", "embed", "norm", "lm_head", "cos_sin")})
         m.device, m.dtype = torch.device(device), dtype
         # the (dequantised) values are carried over, not the FP8 copies
-        m.weight_dtype, m.w8_plan, m.w8_moe_tiles = "auto", None, None
+        m.weight_dtype, m.w8_plan, m.w8_moe_tiles, m.w4_moe_tiles = "auto", None, None, None
 
         def conv(t):
             return None if t is None else t.detach().to(device=device, dtype=dtype)
@@ -507,9 +555,10 @@ class CausalLM:
         return tot * self.embed.element_size() + self._w8_bytes()
 
     def _w8_bytes(self) -> int:
-        """HBM of the FP8 decode copies and their scales."""
-        return sum(q.numel() * q.element_size() + sc.numel() * sc.element_size()
-                   for lw in self.layers for q, sc in lw.w8.values())
+        """HBM of the FP8 decode copies and their scales, and of the MXFP4 ones (their scales inside)."""
+        return (sum(q.numel() * q.element_size() + sc.numel() * sc.element_size()
+                    for lw in self.layers for q, sc in lw.w8.values())
+                + sum(q.numel() for lw in self.layers for q in lw.w4.values()))
 
     # --------------------------------------------------------------- forward
     def forward(self, input_ids: torch.Tensor, positions: torch.Tensor, meta: AttnMetadata,
@@ -662,7 +711,7 @@ class CausalLM:
         if a.is_moe:
             w, ids = ops.moe_route(x, lw.router, a.top_k)  # one fused launch at decode sizes
             return ops.moe_forward_routed(x, lw.w13, lw.w2, w, ids, expert0=self.expert0 if self.ep else None,
-                                          w8=self._moe_w8(lw))
+                                          w8=self._moe_w8(lw), w4=self._moe_w4(lw))
         return ops.linear(ops.linear_silu_mul(x, lw.gate_up), lw.down)
 
     def _forward_sp(self, residual_full: torch.Tensor, positions: torch.Tensor, meta: AttnMetadata,
@@ -956,7 +1005,7 @@ class CausalLM:
     def decode_copy_bytes(self, buckets) -> int:
         """HBM the decode weight copies take: the tile-order copies (0 where none are made), or an FP8-weight
         model's e4m3 copies and scales."""
-        if self.weight_dtype in ("fp8", "fp8_experts"):
+        if self.weight_dtype in ("fp8", "fp8_experts", "mxfp4_experts"):
             return self._w8_bytes()
         if not self.tiled_decode_weights or self.arch.is_moe or not self.norms_folded:
             return 0
@@ -1057,7 +1106,8 @@ class CausalLM:
                     self.tp.all_reduce_residual(self._mlp(lw, x), h, ssp_b)
                 else:  # combine + residual add + statistics in one launch
                     wr_, ids_ = ops.moe_route(x, lw.router, a.top_k)
-                    ops.moe_forward_routed(x, lw.w13, lw.w2, wr_, ids_, residual=h, ssp=ssp_b, w8=self._moe_w8(lw))
+                    ops.moe_forward_routed(x, lw.w13, lw.w2, wr_, ids_, residual=h, ssp=ssp_b, w8=self._moe_w8(lw),
+                                           w4=self._moe_w4(lw))
             else:
                 wg, kg = plan["gate_up"]
                 gsk = plan.get("gate_up_sk", 1)

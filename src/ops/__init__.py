@@ -26,6 +26,11 @@ from .w8 import (W8_BF16, W8_MAX_M, W8_SILU, W8_SLAB, W8_TILES, W8_WIDE_BUCKETS,
                  decode_tile_w8, dequantize_weights_fp8, gd_pack_experts_w8, gd_pack_weights_w8, gd_unpack_experts_w8,
                  gd_unpack_weights_w8, moe_decode_tiles_w8, quantize_weights_fp8, ring_slots_w8, ring_slots_w8_wide,
                  w8_tile_valid)
+# MXFP4 weights of the grouped W4A16 decode GEMM: tiles, packer, tile choice, quantiser (pure torch)
+from . import w4 as w4_cfg  # moe_apply reads W4_MOE_MAX_T there at every call, as W8_MOE_MAX_T
+from .w4 import (W4_BF16, W4_MAX_M, W4_SILU, W4_TILES, dequantize_experts_w4, dequantize_weights_mxfp4,
+                 gd_pack_experts_w4, gd_unpack_experts_w4, moe_decode_tiles_w4, quantize_weights_mxfp4, ring_slots_w4,
+                 w4_tile_valid)
 
 _C = None
 _C_ERR: Optional[BaseException] = None
@@ -53,8 +58,25 @@ except Exception as e:  # pragma: no cover - depends on build state
     _C_W8_ERR = e
 
 
+# the grouped W4A16 decode GEMM (MXFP4 weights) likewise (csrc/bindings_w4.cpp)
+_C_w4 = None
+_C_W4_ERR: Optional[BaseException] = None
+try:
+    from src import _C_w4  # type: ignore  # noqa: F811
+except Exception as e:  # pragma: no cover - depends on build state
+    _C_W4_ERR = e
+
+
 def native_available() -> bool:
     return _C is not None
+
+
+def _kern_w4():
+    if _C_w4 is None:
+        raise RuntimeError(
+            "HIP kernel extension src/_C_w4 (MXFP4 weights) is not built or failed to load "
+            f"({_C_W4_ERR!r}); run `python -m src._build` (hipcc --offload-arch=gfx950)")
+    return _C_w4
 
 
 def _kern_w8():
@@ -989,6 +1011,23 @@ def gemm_decode_w8_grouped_wide(x: torch.Tensor, wq: torch.Tensor, scales: torch
     return out
 
 
+def gemm_decode_w4_grouped(x: torch.Tensor, wq: torch.Tensor, offsets: torch.Tensor, mode: int, wr: int, kc: int,
+                           rows: Optional[torch.Tensor] = None, k: int = 1, max_rows: int = W4_MAX_M,
+                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Raw access to the grouped (MoE) W4A16 decode GEMM (csrc/kernels/gemm_decode_w4_grouped.hip): for every group e
+    of ``offsets`` [E + 1] (int32; at most ``max_rows`` <= 32 rows each) out[off[e]:off[e + 1]] = xrows @
+    dequant(wq[e])^T, with ``wq`` [E, N, K / 2 + K / 32] the experts' MXFP4 codes and block scales packed by
+    gd_pack_experts_w4 for (wr, kc) (W4_SILU: with silu=True). ``rows`` (int32 [T k], moe_align's sorted order): x is in
+    token order and the kernel gathers row rows[j] // k; without it x is in the sorted order. ``mode``: W4_BF16 or
+    W4_SILU (bf16 silu(gate) * up, [., N / 2]). A missing kernel or a refused shape raises."""
+    r = x.shape[0] if rows is None else rows.numel()
+    if out is None:
+        out = torch.empty(r, wq.shape[1] // 2 if mode == W4_SILU else wq.shape[1], dtype=x.dtype, device=x.device)
+    _kern_w4().gemm_decode_w4_grouped(out, x, wq, offsets, mode, wr, kc,
+                                      rows if rows is not None else _NO_ROWS(x.device), k, max_rows)
+    return out
+
+
 def fused_add_rms_norm_slab(slab: torch.Tensor, residual: torch.Tensor, w: torch.Tensor, eps: float,
                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """residual += slab.sum(0) (bf16, in place); returns rms_norm(residual) * w."""
@@ -1067,15 +1106,15 @@ def moe_route(x: torch.Tensor, router: torch.Tensor, k: int, renorm: bool = True
 
 def moe_forward_routed(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, w: torch.Tensor, ids: torch.Tensor,
                        expert0: Optional[int] = None, residual: Optional[torch.Tensor] = None,
-                       ssp: Optional[torch.Tensor] = None, w8=None) -> torch.Tensor:
+                       ssp: Optional[torch.Tensor] = None, w8=None, w4=None) -> torch.Tensor:
     """:func:`moe_forward` after routing (``w``, ``ids`` [T, k] over ALL routed experts). With
     ``residual``/``ssp``: residual += output and ssp[0, :T] = its row sums of squares (returns residual).
-    ``w8``: the experts' FP8 copies (:func:`moe_apply`; not with ``expert0``)."""
+    ``w8`` / ``w4``: the experts' FP8 or MXFP4 copies (:func:`moe_apply`; not with ``expert0``)."""
     e = w13.shape[0]
     if expert0 is not None:
         w, ids = expert_parallel_local(w, ids, expert0, e)
         return moe_apply(x, w13, w2, w, ids, e + 1, residual, ssp)
-    return moe_apply(x, w13, w2, w, ids, e, residual, ssp, w8)
+    return moe_apply(x, w13, w2, w, ids, e, residual, ssp, w8, w4)
 
 
 def moe_forward(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, gating: torch.Tensor, k: int,
@@ -1091,7 +1130,7 @@ def moe_forward(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, gating: to
 
 def moe_apply(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, w: torch.Tensor, ids: torch.Tensor,
               groups: int, residual: Optional[torch.Tensor] = None, ssp: Optional[torch.Tensor] = None,
-              w8=None) -> torch.Tensor:
+              w8=None, w4=None) -> torch.Tensor:
     """out[t] = sum_j w[t, j] * expert_{ids[t, j]}(x[t]) for given routing (w [T, k] fp32, ids [T, k]
     int32). ``groups`` may exceed the number of local experts ``w13.shape[0]``: assignments to those
     extra groups are not computed (their weight must be 0).
@@ -1099,11 +1138,21 @@ def moe_apply(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, w: torch.Ten
     gd_pack_experts_w8 for its tile, s [E, rows] fp32) of which ``w13`` / ``w2`` hold the dequantised values. GPU steps
     of <= ops.w8.W8_MOE_MAX_T tokens run the two grouped W8 launches on them in place of the two bf16 ones (up to W8_MAX_M
     tokens the 32-row kernel, above it the wide grouped one on the same bytes); every other case
-    reads ``w13`` / ``w2`` as without it (on the CPU: ref.moe_experts on the dequantised copies, the same numbers)."""
+    reads ``w13`` / ``w2`` as without it (on the CPU: ref.moe_experts on the dequantised copies, the same numbers).
+    ``w4`` = (q13, q2, ((wr, kc), (wr, kc))): the experts' MXFP4 copies (q [E, rows, K / 2 + K / 32] packed by
+    gd_pack_experts_w4 for its tile, block scales inside) of which ``w13`` / ``w2`` hold the dequantised values. GPU
+    steps of <= ops.w4.W4_MOE_MAX_T tokens run the two grouped W4 launches on them in place of the two bf16 ones; every
+    other case as with ``w8``. Not both."""
+    if w8 is not None and w4 is not None:
+        raise ValueError("moe_apply: w8 and w4 are two copies of the same experts, pass one")
     e = w13.shape[0]
     if residual is not None and not (x.is_cuda and x.shape[0] <= MOE_DECODE_MAX_T):
-        return residual_add_sumsq(residual, moe_apply(x, w13, w2, w, ids, groups, w8=w8), ssp)
+        return residual_add_sumsq(residual, moe_apply(x, w13, w2, w, ids, groups, w8=w8, w4=w4), ssp)
     if not x.is_cuda:
+        if w4 is not None:
+            q13, q2, ((wr1, kc1), (wr2, kc2)) = w4
+            w13 = dequantize_experts_w4(q13, wr1, kc1, silu=True).to(w13.dtype)
+            w2 = dequantize_experts_w4(q2, wr2, kc2).to(w2.dtype)
         if w8 is not None:
             (q13, s13), (q2, s2), ((wr1, kc1), (wr2, kc2)) = w8
             w13 = dequantize_weights_fp8(gd_unpack_experts_w8(q13, wr1, kc1, silu=True), s13).to(w13.dtype)
@@ -1127,6 +1176,18 @@ def moe_apply(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, w: torch.Ten
         grouped = gemm_decode_w8_grouped if t <= W8_MAX_M else gemm_decode_w8_grouped_wide
         grouped(x, q13, s13, offsets, W8_SILU, wr1, kc1, rows=sorted_idx, k=k, max_rows=t, out=a)
         grouped(a, q2, s2, offsets, W8_BF16, wr2, kc2, max_rows=t, out=ys)
+        if residual is not None:
+            kern.moe_combine_residual(ssp, residual, ys, pos, w)
+            return residual
+        out = torch.empty_like(x)
+        kern.moe_combine(out, ys, pos, w)
+        return out
+    if w4 is not None and t <= w4_cfg.W4_MOE_MAX_T and groups == e:
+        # decode on MXFP4 expert weights: the same two launches, 17 / 32 of a byte streamed per weight
+        q13, q2, ((wr1, kc1), (wr2, kc2)) = w4
+        a = torch.empty(t * k, inter, dtype=x.dtype, device=x.device)
+        gemm_decode_w4_grouped(x, q13, offsets, W4_SILU, wr1, kc1, rows=sorted_idx, k=k, max_rows=t, out=a)
+        gemm_decode_w4_grouped(a, q2, offsets, W4_BF16, wr2, kc2, max_rows=t, out=ys)
         if residual is not None:
             kern.moe_combine_residual(ssp, residual, ys, pos, w)
             return residual

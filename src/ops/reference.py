@@ -199,6 +199,46 @@ def linear_w8(x: torch.Tensor, q: torch.Tensor, s: torch.Tensor, mode: str = "bf
     return y.to(x.dtype)
 
 
+# ---- OCP MXFP4 weights: W[n, k] = e2m1(code[n, k]) * 2^(sb[n, k // 32] - 127), one e8m0 scale byte per 32 k of a row
+W4_BLOCK = 32
+W4_MIN_EXP = -125   # smallest block exponent: the smallest non-zero product 0.5 * 2^e is then a normal bf16
+W4_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)   # e2m1 magnitudes by index; a code is sign << 3 | index
+
+
+def quantize_weights_mxfp4(w: torch.Tensor):
+    """(codes uint8 [N, K / 2], sb uint8 [N, K / 32]) of a [N, K] weight, K % 32 == 0. Per block of 32 consecutive k
+    of a row: e = floor(log2(amax)) - 2 clamped to [W4_MIN_EXP, 125], sb = e + 127 (127 for a block whose codes are all
+    zero, an all-zero block among them); the elements w / 2^e (exact) are rounded to the nearest of W4_VALUES, ties to
+    the even mantissa (the even index), saturating at 6; a zero has no sign. Element 2 j is the low nibble of byte j,
+    element 2 j + 1 the high one. An e2m1 value times a power of two >= 2^-125 is a bf16:
+    bf16(:func:`dequantize_weights_mxfp4`) is exact. amax lands on 4 or 6 times 2^e, so quantising the dequantised
+    values finds the same e and reproduces codes and scales."""
+    n, k = w.shape
+    assert k % W4_BLOCK == 0
+    wf = w.float().view(n, k // W4_BLOCK, W4_BLOCK)
+    _, ex = torch.frexp(wf.abs().amax(dim=2))            # amax = m 2^ex, m in [0.5, 1): floor(log2(amax)) = ex - 1
+    e = (ex - 3).clamp(W4_MIN_EXP, 125)
+    a = torch.ldexp(wf, -e[..., None])                   # 2^125 and 2^-125 are both normal floats
+    m = a.abs()
+    idx = ((m > 0.25).to(torch.uint8) + (m >= 0.75) + (m > 1.25) + (m >= 1.75) + (m > 2.5) + (m >= 3.5) + (m > 5.0))
+    idx = idx.to(torch.uint8)
+    c = (idx | (((a < 0) & (idx > 0)).to(torch.uint8) << 3)).view(n, k)
+    sb = torch.where((idx > 0).any(dim=2), e + 127, torch.full_like(e, 127)).to(torch.uint8)
+    return c[:, 0::2] | (c[:, 1::2] << 4), sb
+
+
+def dequantize_weights_mxfp4(codes: torch.Tensor, sb: torch.Tensor) -> torch.Tensor:
+    """fp32 [..., N, K] of MXFP4 codes [..., N, K / 2] and scale bytes [..., N, K / 32]: a 16-entry table times
+    2^(sb - 127)."""
+    mag = torch.tensor(W4_VALUES, dtype=torch.float32, device=codes.device)
+    table = torch.cat([mag, -mag])
+    v = torch.stack([table[(codes & 15).long()], table[(codes >> 4).long()]], dim=-1)
+    v = v.view(*codes.shape[:-1], sb.shape[-1], W4_BLOCK)
+    ex = sb.to(torch.int32) - 127
+    s = torch.ldexp(torch.ones_like(ex, dtype=torch.float32), ex)
+    return (v * s[..., None]).view(*codes.shape[:-1], -1)
+
+
 def sample(logits, temperature=None, top_k=None, top_p=None, seeds=None, steps=None):
     """Greedy where temperature==0; otherwise a (non-bit-exact) torch sampler
     with the same filtering semantics (top-k, then top-p on the renormalised set)."""

@@ -414,10 +414,11 @@ def build_arg_parser():
     p.add_argument("--kv-cache-dtype", choices=["auto", "fp8"], default="auto",
                    help="fp8: the KV pool holds e4m3 bytes, twice the blocks in the same memory (one GPU, dense "
                         "models, role both)")
-    p.add_argument("--weight-dtype", choices=["auto", "fp8", "fp8_experts"], default="auto",
+    p.add_argument("--weight-dtype", choices=["auto", "fp8", "fp8_experts", "mxfp4_experts"], default="auto",
                    help="fp8: the layers' projections are quantised to e4m3 with per-row scales and decode steps "
                         "stream the one-byte weights (one GPU, dense models); fp8_experts: a MoE model's expert "
-                        "weights likewise (one GPU)")
+                        "weights likewise (one GPU); mxfp4_experts: a MoE model's expert weights in OCP MXFP4, "
+                        "decode steps of up to 32 tokens stream the 4-bit weights (one GPU)")
     p.add_argument("--kv-capacity-priority", action="store_true",
                    help="the KV pool is the constraint: decode weights in one layout (EngineConfig)")
     p.add_argument("--preproc-processes", type=int, default=0,
