@@ -274,8 +274,9 @@ def main_moe_w8(m, reps=5, seed=0, w4=False):
     variants of a shape are captured first and then replayed in turn, `reps` rounds: the line of a variant carries the
     best, the median and the worst round. W8 bytes are random codes (no NaN): the time does not depend on the layout,
     so one pair of copies serves the three tiles. gate/up gathers its rows from the token order in both kernels.
-    `M moe --w4` (M <= 32) adds the grouped W4 launch (ops.gemm_decode_w4_grouped on MXFP4 bytes, every W4 tile) to the
-    same alternation; its bytes are random codes with every scale byte 2^-7, E * rows * (K / 2 + K / 32) of them."""
+    `M moe --w4` adds the grouped W4 launch (ops.gemm_decode_w4_grouped on MXFP4 bytes up to 32 tokens,
+    ops.gemm_decode_w4_grouped_wide on the same bytes above, up to 128; every W4 tile) to the same alternation; its
+    bytes are random codes with every scale byte 2^-7, E * rows * (K / 2 + K / 32) of them."""
     dev = torch.device("cuda:0")
     g = torch.Generator(device=dev).manual_seed(seed)
     e, h, inter, k = 8, 4096, 14336, 2
@@ -288,6 +289,7 @@ def main_moe_w8(m, reps=5, seed=0, w4=False):
     kern, none = ops._kern(), torch.empty(0, dtype=torch.int32, device=dev)
     t1, t2 = ops.moe_decode_tiles(h, inter, m)
     gw8 = ops.gemm_decode_w8_grouped if m <= ops.W8_MAX_M else ops.gemm_decode_w8_grouped_wide
+    gw4 = ops.gemm_decode_w4_grouped if m <= ops.W4_MAX_M else ops.gemm_decode_w4_grouped_wide
     for nm, rows, kk, silu in (("moe_w13", 2 * inter, h, True), ("moe_w2", h, inter, False)):
         ws = [torch.randn(e, rows, kk, device=dev, dtype=torch.bfloat16) / 64 for _ in range(2)]
         qs = [torch.randint(0, 0x78, (e, rows, kk), device=dev, dtype=torch.uint8) for _ in range(2)]
@@ -309,10 +311,10 @@ def main_moe_w8(m, reps=5, seed=0, w4=False):
             variants += [("w8", t, qs, lambda q, t=t: gw8(a, q, sc, offsets, ops.W8_BF16, *t, max_rows=m, out=ys))
                          for t in ops.W8_TILES]
         if w4 and silu:
-            variants += [("w4", t, q4, lambda q, t=t: ops.gemm_decode_w4_grouped(
+            variants += [("w4", t, q4, lambda q, t=t: gw4(
                 x, q, offsets, ops.W4_SILU, *t, rows=sorted_idx, k=k, max_rows=m, out=out13)) for t in ops.W4_TILES]
         elif w4:
-            variants += [("w4", t, q4, lambda q, t=t: ops.gemm_decode_w4_grouped(
+            variants += [("w4", t, q4, lambda q, t=t: gw4(
                 a, q, offsets, ops.W4_BF16, *t, max_rows=m, out=ys)) for t in ops.W4_TILES]
         graphs, iters = [], 8
         for _, _, bufs, fn in variants:

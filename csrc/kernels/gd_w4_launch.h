@@ -1,4 +1,4 @@
-// Host launcher of the grouped W4A16 decode GEMM (gemm_decode_w4_grouped.hip). As launchers.h: raw pointers and an
+// Host launchers of the grouped W4A16 decode GEMM (gemm_decode_w4_grouped.hip, gemm_decode_w4_grouped_wide.hip). As launchers.h: raw pointers and an
 // explicit stream, no allocation, no synchronisation.
 #pragma once
 
@@ -21,5 +21,12 @@ namespace die {
 hipError_t launch_gemm_decode_w4_grouped(bf16_t* Y, int64_t ldy, const bf16_t* X, int64_t ldx, const uint8_t* Wq,
                                          const int* offsets, const int* rows, int k, int E, int T, int R, int N, int K,
                                          int mode, int wr, int kc, int max_rows, hipStream_t s);
+
+// The same product on the same packed bytes for groups of at most max_rows <= 128 rows each
+// (gemm_decode_w4_grouped_wide.hip): the kernel chooses the 16-, 32-, 64- or 128-row image per group. Same arguments,
+// same clamping, same refusals with max_rows outside [1, 128].
+hipError_t launch_gemm_decode_w4_grouped_wide(bf16_t* Y, int64_t ldy, const bf16_t* X, int64_t ldx, const uint8_t* Wq,
+                                              const int* offsets, const int* rows, int k, int E, int T, int R, int N,
+                                              int K, int mode, int wr, int kc, int max_rows, hipStream_t s);
 
 }  // namespace die

@@ -47,7 +47,7 @@ KV8_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 W8_KERNELS = ["gemm_decode_w8", "gemm_decode_w8_wide", "gemm_decode_w8_grouped", "gemm_decode_w8_grouped_wide"]
 CONTRACT_ON |= set(W8_KERNELS)
 # the grouped W4A16 decode GEMM (MXFP4 expert weights): a fourth module (src/_C_w4*.so), built like the W8 kernels
-W4_KERNELS = ["gemm_decode_w4_grouped"]
+W4_KERNELS = ["gemm_decode_w4_grouped", "gemm_decode_w4_grouped_wide"]
 CONTRACT_ON |= set(W4_KERNELS)
 # module -> (kernels, bindings source, extra hipcc flags)
 MODULES = {"_C": (KERNELS, "bindings", []), "_C_kv8": (KV8_KERNELS, "bindings_kv8", KV8_FLAGS),

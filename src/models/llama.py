@@ -143,7 +143,7 @@ class CausalLM:
         self.w8_moe_tiles = None
         self.w8_stats = {"quantized": 0}
         # "mxfp4_experts" once quantize_expert_weights_mxfp4 has run (MoE): w13 / w2 hold dequantised MXFP4 values and
-        # decode steps of <= 32 tokens stream their 4-bit copies (lw.w4) on w4_moe_tiles
+        # decode steps of <= ops.w4.W4_MOE_MAX_T tokens stream their 4-bit copies (lw.w4) on w4_moe_tiles
         self.w4_moe_tiles = None
         self.w4_stats = {"quantized": 0}
         self.layers: List[LayerWeights] = []

@@ -28,9 +28,9 @@ from .w8 import (W8_BF16, W8_MAX_M, W8_SILU, W8_SLAB, W8_TILES, W8_WIDE_BUCKETS,
                  w8_tile_valid)
 # MXFP4 weights of the grouped W4A16 decode GEMM: tiles, packer, tile choice, quantiser (pure torch)
 from . import w4 as w4_cfg  # moe_apply reads W4_MOE_MAX_T there at every call, as W8_MOE_MAX_T
-from .w4 import (W4_BF16, W4_MAX_M, W4_SILU, W4_TILES, dequantize_experts_w4, dequantize_weights_mxfp4,
-                 gd_pack_experts_w4, gd_unpack_experts_w4, moe_decode_tiles_w4, quantize_weights_mxfp4, ring_slots_w4,
-                 w4_tile_valid)
+from .w4 import (W4_BF16, W4_MAX_M, W4_SILU, W4_TILES, W4_WIDE_MAX_M, dequantize_experts_w4,
+                 dequantize_weights_mxfp4, gd_pack_experts_w4, gd_unpack_experts_w4, moe_decode_tiles_w4,
+                 quantize_weights_mxfp4, ring_slots_w4, ring_slots_w4_wide, w4_tile_valid)
 
 _C = None
 _C_ERR: Optional[BaseException] = None
@@ -1028,6 +1028,20 @@ def gemm_decode_w4_grouped(x: torch.Tensor, wq: torch.Tensor, offsets: torch.Ten
     return out
 
 
+def gemm_decode_w4_grouped_wide(x: torch.Tensor, wq: torch.Tensor, offsets: torch.Tensor, mode: int, wr: int, kc: int,
+                                rows: Optional[torch.Tensor] = None, k: int = 1, max_rows: int = W4_WIDE_MAX_M,
+                                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """:func:`gemm_decode_w4_grouped` for groups of at most ``max_rows`` <= 128 rows each
+    (csrc/kernels/gemm_decode_w4_grouped_wide.hip): the same operands, the same packed bytes, the same modes; every
+    workgroup picks its group's 16-, 32-, 64- or 128-row image. A missing kernel or a refused shape raises."""
+    r = x.shape[0] if rows is None else rows.numel()
+    if out is None:
+        out = torch.empty(r, wq.shape[1] // 2 if mode == W4_SILU else wq.shape[1], dtype=x.dtype, device=x.device)
+    _kern_w4().gemm_decode_w4_grouped_wide(out, x, wq, offsets, mode, wr, kc,
+                                           rows if rows is not None else _NO_ROWS(x.device), k, max_rows)
+    return out
+
+
 def fused_add_rms_norm_slab(slab: torch.Tensor, residual: torch.Tensor, w: torch.Tensor, eps: float,
                             out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """residual += slab.sum(0) (bf16, in place); returns rms_norm(residual) * w."""
@@ -1141,8 +1155,9 @@ def moe_apply(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, w: torch.Ten
     reads ``w13`` / ``w2`` as without it (on the CPU: ref.moe_experts on the dequantised copies, the same numbers).
     ``w4`` = (q13, q2, ((wr, kc), (wr, kc))): the experts' MXFP4 copies (q [E, rows, K / 2 + K / 32] packed by
     gd_pack_experts_w4 for its tile, block scales inside) of which ``w13`` / ``w2`` hold the dequantised values. GPU
-    steps of <= ops.w4.W4_MOE_MAX_T tokens run the two grouped W4 launches on them in place of the two bf16 ones; every
-    other case as with ``w8``. Not both."""
+    steps of <= ops.w4.W4_MOE_MAX_T tokens run the two grouped W4 launches on them in place of the two bf16 ones (up to
+    W4_MAX_M tokens the 32-row kernel, above it the wide grouped one on the same bytes); every other case as with
+    ``w8``. Not both."""
     if w8 is not None and w4 is not None:
         raise ValueError("moe_apply: w8 and w4 are two copies of the same experts, pass one")
     e = w13.shape[0]
@@ -1183,11 +1198,13 @@ def moe_apply(x: torch.Tensor, w13: torch.Tensor, w2: torch.Tensor, w: torch.Ten
         kern.moe_combine(out, ys, pos, w)
         return out
     if w4 is not None and t <= w4_cfg.W4_MOE_MAX_T and groups == e:
-        # decode on MXFP4 expert weights: the same two launches, 17 / 32 of a byte streamed per weight
+        # decode on MXFP4 expert weights: the same two launches, 17 / 32 of a byte streamed per weight (16 or 32 rows
+        # per group; above W4_MAX_M tokens the wide kernel, also 64 or 128)
         q13, q2, ((wr1, kc1), (wr2, kc2)) = w4
         a = torch.empty(t * k, inter, dtype=x.dtype, device=x.device)
-        gemm_decode_w4_grouped(x, q13, offsets, W4_SILU, wr1, kc1, rows=sorted_idx, k=k, max_rows=t, out=a)
-        gemm_decode_w4_grouped(a, q2, offsets, W4_BF16, wr2, kc2, max_rows=t, out=ys)
+        grouped = gemm_decode_w4_grouped if t <= W4_MAX_M else gemm_decode_w4_grouped_wide
+        grouped(x, q13, offsets, W4_SILU, wr1, kc1, rows=sorted_idx, k=k, max_rows=t, out=a)
+        grouped(a, q2, offsets, W4_BF16, wr2, kc2, max_rows=t, out=ys)
         if residual is not None:
             kern.moe_combine_residual(ssp, residual, ys, pos, w)
             return residual

@@ -24,6 +24,10 @@ W4_TILES = ((64, 256), (128, 256))
 W4_MAX_M = 32            # activation images of 16 and 32 rows
 W4_IMAGES = (16, 32)
 SCALE_LDS = 1024         # the scale area of a ring slot: 256 bytes per wave
+# the wide grouped kernel (_C_w4.gemm_decode_w4_grouped_wide, csrc/kernels/gd_w4_wide.h): groups of up to 128 rows on the
+# same packed bytes, in activation images of 64 and 128 rows next to the two above
+W4_WIDE_MAX_M = 128
+W4_WIDE_IMAGES = (64, 128)
 
 
 def chunk_bytes(wr: int, kc: int) -> int:
@@ -55,6 +59,18 @@ def ring_slots_w4(wr: int, kc: int, xr: int) -> int:
     """LDS ring depth: the deepest that fits RING_BYTES, MAX_SLOTS and the 6-bit vmcnt."""
     s = min(MAX_SLOTS, RING_BYTES // slot_bytes_w4(wr, kc, xr))
     while s > 2 and (s - 1) * per_wave_w4(wr, kc, xr) > 63:
+        s -= 1
+    return s
+
+
+def ring_slots_w4_wide(wr: int, xr: int) -> int:
+    """LDS ring depth of the wide grouped kernel's xr-row body (mirror of gd_w4_wide.h ring_slots): a slot is half a
+    chunk, wr * 64 nibble bytes, the scale area and xr rows of 256 bytes; a wave issues a quarter of the slot's 1-KiB
+    pieces and one scale piece."""
+    slot = wr * 64 + SCALE_LDS + xr * 256
+    per_wave = (wr * 64 + xr * 256) // 1024 // 4 + 1
+    s = min(MAX_SLOTS, RING_BYTES // slot)
+    while s > 2 and (s - 1) * per_wave > 63:
         s -= 1
     return s
 
@@ -160,9 +176,21 @@ W4_MOE_TILE_CFG = {
     #               down     72.3 /  70.1 vs W8  99.4 /  98.5 vs bf16 156.0 / 137.4 ((64, 256): 100.5 /  98.9)
     (4096, 14336): ((128, 256), (128, 256)),
 }
-# The largest token count at which ops.moe_apply runs the grouped W4 launches on the experts' MXFP4 copies; above it the
-# bf16 grouped GEMM on the dequantised experts (a wide form for 33 to 128 tokens does not exist yet).
-W4_MOE_MAX_T = 32
+# The largest token count at which ops.moe_apply runs the grouped W4 launches on the experts' MXFP4 copies: up to W4_MAX_M
+# tokens the 32-row grouped kernel, above it the wide grouped one (csrc/kernels/gemm_decode_w4_grouped_wide.hip, groups
+# of up to 128 rows on the same packed bytes); above W4_MOE_MAX_T the bf16 grouped GEMM on the dequantised experts.
+# 128, and not 32, by measurement (Mixtral-8x7B, random weights, one MI355X, one session, mxfp4_experts engines of 128
+# sequences, one wave of batch x (512 -> 128), bench/w8_moe_wide_engine_cost.py ... mxfp4_experts,
+# profiles/w4_moe_wide_micro_and_engine.jsonl; two engines each, alternating with an fp8_experts engine, two waves each;
+# 32 runs what every mxfp4_experts engine ran above 32 tokens before the wide grouped kernel existed):
+# batch 64: 1.966 - 1.972 s per wave with 128 against 3.305 - 3.313 s with 32 (32.5 against 19.3 req/s; FP8 experts 2.249
+# - 2.257 s); batch 128: 3.321 - 3.329 s against 4.672 - 4.687 s (38.5 against 27.4 req/s; FP8 experts 3.484 - 3.495 s).
+# Thin evidence (one session, one card), but the gaps (1.33 s, 1.34 s) are more than 80 times the largest spread seen
+# between like engines (0.008 s, 0.015 s). W8_MOE_MAX_T's rule: 128 if faster at both batches by more than that spread,
+# 64 if only at batch 64, else 32. At 64 / 128 tokens the kernel itself ((128, 256), us, `M moe --w4`): gate/up 154.0 /
+# 209.3 vs W8 199.8 / 252.5 vs bf16 339.5 / 451.2 ((64, 256): 215.6 / 304.9); down 83.4 / 150.3 vs W8 108.3 / 162.1 vs
+# bf16 245.3 / 303.6 ((64, 256): 110.5 / 171.1): W4_MOE_TILE_CFG's tile wins at every token count.
+W4_MOE_MAX_T = 128
 
 
 def moe_decode_tiles_w4(hdim: int, inter: int, experts: int = MOE_ACTIVE_EXPERTS):
